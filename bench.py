@@ -29,9 +29,15 @@ which also carries the barriers and the max-over-ranks of the elapsed time: torc
 collective of the data path is the engine's own).  Prints ONE JSON line on rank 0.
 
 Timing: the K timed steps run with plain kernel launches (ssde_set_option(SSDE_OPT_KERNEL_STAMPS, 0): what a fitting
-host runs); the dominant kernel's duration comes from a second, untimed pass over the SAME K parameter vectors with
-every launch stamped by HIP events on its own stream (`roofline.kernel_ms`; `ms_per_step_stamped` is that pass's wall
-time per step, for comparison)."""
+host runs).  A plain run stops there: set-up, warm-up, the K steps, the outputs if asked for, the line.
+
+`--full` adds everything else the line has carried: the dominant kernel's duration from a second, untimed pass over the
+SAME K parameter vectors with every launch stamped by HIP events on its own stream (`roofline.kernel_ms`;
+`ms_per_step_stamped` is that pass's wall time per step, for comparison), the roofline, `per_rank`, the weak-scaling
+probe at N > 1, the secondary workloads and the CPU baseline (`--no-secondary`, `--no-cpu-baseline` leave those out).
+
+`--dump-outputs DIR` writes, on rank 0, what the last timed step returned: DIR/nllk.npy (one value per handle) and
+DIR/grad.npy (the handles' gradients, concatenated), float64."""
 import argparse
 import ctypes as C
 import json
@@ -645,8 +651,12 @@ def main():
     ap.add_argument("--rows", type=int, default=None, help="rows per track (c5: of the longest track)")
     ap.add_argument("--model", default="CTCRW", help="c2p / c4 only")
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the irregular-grid / missing-row workloads")
+    ap.add_argument("--full", action="store_true",
+                    help="also the stamped pass, roofline, per-rank account, secondary workloads and CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's value(s) and gradient as DIR/nllk.npy, DIR/grad.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the irregular-grid / missing-row workloads")
     args = ap.parse_args()
     args.tracks = args.tracks or CONFIGS[args.config]["tracks"]
     args.rows = args.rows or CONFIGS[args.config]["rows"]
@@ -746,7 +756,8 @@ def main():
                 t = torch.from_numpy(host[:, :1 + npmax].copy())
                 dist.all_reduce(t)
                 host[:, :1 + npmax] = t.numpy()
-            last["val"] = float(sum(host[i, 0] for i in range(len(handles))))
+            last["vals"] = [float(host[i, 0]) for i in range(len(handles))]
+            last["val"] = sum(last["vals"])
             last["grad"] = np.concatenate([host[i, 1:1 + h.npar] for i, h in enumerate(handles)])
             last["check"] = float(max(host[i, 1 + h.npar] for i, h in enumerate(handles)))
 
@@ -781,6 +792,77 @@ def main():
     assert np.isfinite(val) and np.all(np.isfinite(grad_last)), (val, grad_last)
     assert check_max <= capi.WINDOW_TOL, f"window hand-over check failed: {check_max}"
     assert all(i["n_memo_hits"] == 0 for i in infos), "a timed step was answered from the memo"
+
+    rows_rank = sum(h.rows_local for h in handles)
+    rows_t = torch.tensor([float(rows_rank)], dtype=torch.float64)
+    if use_comm:
+        dist.all_reduce(rows_t)
+    total_rows = int(rows_t.item())
+    value = total_rows * args.steps / elapsed
+
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path received in the last step (every rank holds the sum over ranks)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "nllk.npy"), np.array(last.get("vals", [val]), dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, "grad.npy"), grad_last.astype(np.float64))
+
+    def headline(infos, info0):
+        M, T = args.tracks, args.rows
+        if args.config == "c5":
+            wl = (f"{CONFIGS['c5']['label']}: BM_SSM + OU_SSM + CTCRW sub-batches of {M} tracks each, ragged lengths U[{T // 2}, {T}], d=2, "
+                  f"sigma_obs=0.1, 5 % of the rows missing (column 0 only / every column), every parameter free, three handles evaluated "
+                  f"concurrently; {total_rows} rows in total")
+        else:
+            wl = (f"{CONFIGS[args.config]['label']}: {M} {args.model} tracks x {T} rows, d=2, constant coefficients, sigma_obs/tau/nu free, "
+                  f"mu fixed, dt=1")
+        wl += (f"; {args.scaling} scaling: " + ("the batch split into whole-track shards over the ranks" if args.scaling == "strong"
+                                                 else "that many tracks on EVERY rank"))
+        return {
+            "metric": "track-timesteps/s nllk+grad",
+            "value": value, "unit": "track-timesteps/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": 1e3 * elapsed / args.steps,
+            "extra": {"ms_per_step_median": float(np.median(step_ms)), "ms_per_step_min": float(np.min(step_ms)),
+                      "ms_per_step_p90": float(np.percentile(step_ms, 90)), "ms_per_step_max": float(np.max(step_ms)),
+                      "note": "spread of THIS rank's timed steps (one clock read after every synchronous step); `value` is all rows over "
+                              "the whole timed region, max over ranks"},
+            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+            "dtype": "f64", "data": "synthetic",
+            "config": {"workload": wl, "config": args.config, "tracks": M, "rows_per_track": T, "total_rows": total_rows,
+                       "rows_this_rank": rows_rank, "seed": args.seed,
+                       "nllk_at_last_step": val,                # the same number at every N under strong scaling (same batch, same theta)
+                       "n_free_par": [i["n_free"] for i in infos] if concurrent else info0["n_free"],
+                       "engine_path": capi.PATH_NAMES[info0["path"]], "engine_kernel": capi.KERNEL_NAMES.get(info0["kernel_id"], "?"),
+                       "comm_ranks_requested": max(i["comm_ranks"] for i in infos) if use_comm else 0,
+                       "comm_ranks_reported": max(i["comm_ranks_reported"] for i in infos),       # ncclCommCount of the joined communicator (0: none)
+                       "uniform_dt": info0["uniform_dt"], "workgroups": info0["n_kernel_blocks"],
+                       "rows_tiled": info0["n_rows_tiled"], "groups": info0["n_groups"], "clean_groups": info0["n_clean_groups"],
+                       "lanes_per_track": info0["lanes_per_track"], "window_rows": info0["window"],
+                       "window_check": check_max, "window_retries": sum(i["window_retries"] for i in infos),
+                       "parallelism": f"tracks x{world}" + ("" if not use_comm else
+                                                             ((", ONE ncclAllReduce of the three handles' 2+p doubles per step (ssde_comm_allreduce)" if concurrent
+                                                               else ", in-engine ncclAllReduce of 2+p doubles")
+                                                              if not host_reduce else
+                                                              f", HOST all-reduce over gloo after every evaluation (RCCL could not be brought up: {host_reduce})")),
+                       "api": "ssde_eval_device on one stream per handle + one read-back" if concurrent else "ssde_eval (synchronous C ABI call)",
+                       "data_generator": "ssde_simulate (HIP, Philox4x32-10 keyed by seed / global track / row)"},
+        }
+
+    def emit(line):
+        sys.stdout.flush()
+        if rank == 0:
+            os.write(json_fd, (json.dumps(line) + "\n").encode())
+        os.close(json_fd)
+        if use_comm:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:
+        line = headline(infos, infos[0])          # (c5: the engine fields name the first handle; --full names the dominant one)
+        for h in handles:
+            h.eng.close()
+        emit(line)
+        return
 
     # ---- second pass, untimed for `value`: the same K evaluations with every dominant kernel stamped by HIP events on its own
     # stream; the engine keeps the last 64 pairs, read in batches after the calls
@@ -831,13 +913,6 @@ def main():
         torch.cuda.synchronize(dev)
         eval_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
         host_enq_ms = 1e3 * float(np.mean(enq))
-
-    rows_rank = sum(h.rows_local for h in handles)
-    rows_t = torch.tensor([float(rows_rank)], dtype=torch.float64)
-    if use_comm:
-        dist.all_reduce(rows_t)
-    total_rows = int(rows_t.item())
-    value = total_rows * args.steps / elapsed
 
     def roof(h, info):
         # Bytes of the rows that launch scores.  `required`: what the resident layout has to read (the `times` stream is
@@ -918,47 +993,8 @@ def main():
         per_rank = [mine]
 
     M, T = args.tracks, args.rows
-    if args.config == "c5":
-        wl = (f"{CONFIGS['c5']['label']}: BM_SSM + OU_SSM + CTCRW sub-batches of {M} tracks each, ragged lengths U[{T // 2}, {T}], d=2, "
-              f"sigma_obs=0.1, 5 % of the rows missing (column 0 only / every column), every parameter free, three handles evaluated "
-              f"concurrently; {total_rows} rows in total")
-    else:
-        wl = (f"{CONFIGS[args.config]['label']}: {M} {args.model} tracks x {T} rows, d=2, constant coefficients, sigma_obs/tau/nu free, "
-              f"mu fixed, dt=1")
-    wl += (f"; {args.scaling} scaling: " + ("the batch split into whole-track shards over the ranks" if args.scaling == "strong"
-                                             else "that many tracks on EVERY rank"))
-    line = {
-        "metric": "track-timesteps/s nllk+grad",
-        "value": value, "unit": "track-timesteps/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps, "ms_per_step_stamped": stamped_ms,
-        "extra": {"ms_per_step_median": float(np.median(step_ms)), "ms_per_step_min": float(np.min(step_ms)),
-                  "ms_per_step_p90": float(np.percentile(step_ms, 90)), "ms_per_step_max": float(np.max(step_ms)),
-                  "note": "spread of THIS rank's timed steps (one clock read after every synchronous step); `value` is all rows over "
-                          "the whole timed region, max over ranks"},
-        "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic",
-        "config": {"workload": wl, "config": args.config, "tracks": M, "rows_per_track": T, "total_rows": total_rows,
-                   "rows_this_rank": rows_rank, "seed": args.seed,
-                   "nllk_at_last_step": val,                # the same number at every N under strong scaling (same batch, same theta)
-                   "n_free_par": [i["n_free"] for i in infos] if concurrent else info0["n_free"],
-                   "engine_path": capi.PATH_NAMES[info0["path"]], "engine_kernel": capi.KERNEL_NAMES.get(info0["kernel_id"], "?"),
-                   "comm_ranks_requested": max(i["comm_ranks"] for i in infos) if use_comm else 0,
-                   "comm_ranks_reported": max(i["comm_ranks_reported"] for i in infos),       # ncclCommCount of the joined communicator (0: none)
-                   "uniform_dt": info0["uniform_dt"], "workgroups": info0["n_kernel_blocks"],
-                   "rows_tiled": info0["n_rows_tiled"], "groups": info0["n_groups"], "clean_groups": info0["n_clean_groups"],
-                   "lanes_per_track": info0["lanes_per_track"], "window_rows": info0["window"],
-                   "window_check": check_max, "window_retries": sum(i["window_retries"] for i in infos),
-                   "parallelism": f"tracks x{world}" + ("" if not use_comm else
-                                                         ((", ONE ncclAllReduce of the three handles' 2+p doubles per step (ssde_comm_allreduce)" if concurrent
-                                                           else ", in-engine ncclAllReduce of 2+p doubles")
-                                                          if not host_reduce else
-                                                          f", HOST all-reduce over gloo after every evaluation (RCCL could not be brought up: {host_reduce})")),
-                   "api": "ssde_eval_device on one stream per handle + one read-back" if concurrent else "ssde_eval (synchronous C ABI call)",
-                   "data_generator": "ssde_simulate (HIP, Philox4x32-10 keyed by seed / global track / row)"},
-        "roofline": roofline,
-        "per_rank": per_rank,
-    }
+    line = headline(infos, info0)
+    line.update({"ms_per_step_stamped": stamped_ms, "roofline": roofline, "per_rank": per_rank})
     for h in handles:
         h.eng.close()
     del handles
@@ -1023,13 +1059,7 @@ def main():
         except Exception as e:  # the baseline must never take the bench line down
             line["cpu_baseline"] = {"value": None, "unit": "track-timesteps/s", "cores": os.cpu_count(),
                                     "kind": "port", "sample": f"failed: {e}"}
-    sys.stdout.flush()
-    if rank == 0:
-        os.write(json_fd, (json.dumps(line) + "\n").encode())
-    os.close(json_fd)
-    if use_comm:
-        dist.barrier()
-        dist.destroy_process_group()
+    emit(line)
 
 
 if __name__ == "__main__":

@@ -1,7 +1,7 @@
 """GPU suite (-m gpu): bench.py's one-line contract, on a small batch (the driver runs the full size).
 
-One JSON object on stdout and nothing else: the keys the driver reads, a roofline object whose fraction is formed on the
-bytes the resident layout has to read and never exceeds 1, the secondary workloads, the CPU baseline."""
+One JSON object on stdout and nothing else: the keys the driver reads; with --full also a roofline object whose fraction is
+formed on the bytes the resident layout has to read and never exceeds 1, the secondary workloads, the CPU baseline."""
 import json
 
 import numpy as np
@@ -25,7 +25,7 @@ def _run(*extra):
 
 
 def test_bench_line_has_what_the_driver_reads():
-    d = _run()
+    d = _run("--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -85,7 +85,7 @@ def test_bench_line_has_what_the_driver_reads():
 def test_one_rank_communicator_rehearsal_prints_one_line_too():
     env = dict(os.environ, SSDE_BENCH_SELF_LAUNCH="1", SSDE_BENCH_FORCE_COMM="1")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--tracks", "640", "--rows", "800", "--steps", "4", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-secondary"], capture_output=True, text=True, timeout=600, env=env)
+                        "--no-cpu-baseline", "--no-secondary", "--full"], capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -107,7 +107,7 @@ def test_strong_scaling_line_carries_the_weak_scaling_reading_of_the_same_launch
     engines and collective; its failure modes end in an entry with `error`, never in a missing line"""
     env = dict(os.environ, SSDE_BENCH_SELF_LAUNCH="1", SSDE_BENCH_FORCE_COMM="1", SSDE_BENCH_WEAK_PROBE="1")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--tracks", "640", "--rows", "800", "--steps", "4", "--warmup", "1",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env)
+                        "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -145,9 +145,9 @@ def test_strong_and_weak_modes_with_one_rank_time_the_same_batch():
 
 
 def test_config_c4_and_c5_lines():
-    d = _run("--no-cpu-baseline", "--config", "c4")
+    d = _run("--full", "--no-cpu-baseline", "--config", "c4")
     assert d["config"]["config"] == "c4" and "C4" in d["config"]["workload"] and 0 < d["roofline"]["frac"] <= 1.0
-    d = _run("--no-cpu-baseline", "--config", "c5")
+    d = _run("--full", "--no-cpu-baseline", "--config", "c5")
     c = d["config"]
     assert c["config"] == "c5" and "concurrently" in c["workload"] and len(c["n_free_par"]) == 3
     # ragged lengths U[T/2, T]: three sub-batches of 640 tracks
@@ -157,3 +157,24 @@ def test_config_c4_and_c5_lines():
     assert all(0 < h["frac"] <= 1.0 and h["kernel_ms"] > 0 for h in hs)
     assert c["window_check"] <= 1e-11 and d["value"] > 0
     assert abs(d["value"] - c["total_rows"] * 5 / (d["ms_per_step"] * 5e-3)) <= 1e-6 * d["value"]
+
+
+def test_plain_line_times_the_steps_and_dumps_what_the_last_step_returned(tmp_path):
+    """Without --full the line carries the headline only; --dump-outputs writes the last timed step's value and gradient, and the
+    same arguments give the same outputs in a second process."""
+    d = _run("--dump-outputs", str(tmp_path / "a"))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "config"):
+        assert k in d, k
+    for k in ("roofline", "per_rank", "ms_per_step_stamped", "secondary", "cpu_baseline"):
+        assert k not in d, k
+    assert d["steps"] == 5 and d["warmup"] == 2 and abs(d["value"] - 640 * 800 * 5 / (d["ms_per_step"] * 5e-3)) <= 1e-6 * d["value"]
+    nllk, grad = np.load(tmp_path / "a" / "nllk.npy"), np.load(tmp_path / "a" / "grad.npy")
+    assert nllk.dtype == np.float64 and grad.dtype == np.float64
+    assert nllk.shape == (1,) and nllk[0] == d["config"]["nllk_at_last_step"] and grad.shape == (5,) and np.all(np.isfinite(grad))
+    _run("--dump-outputs", str(tmp_path / "b"))
+    assert np.array_equal(np.load(tmp_path / "b" / "nllk.npy"), nllk) and np.array_equal(np.load(tmp_path / "b" / "grad.npy"), grad)
+    # c5: one value per handle (their sum is the line's), the three gradients side by side
+    e = _run("--config", "c5", "--dump-outputs", str(tmp_path / "c5"))
+    v = np.load(tmp_path / "c5" / "nllk.npy")
+    assert v.shape == (3,) and sum(v.tolist()) == e["config"]["nllk_at_last_step"]
+    assert np.load(tmp_path / "c5" / "grad.npy").shape == (sum(e["config"]["n_free_par"]),)     # (c5: every parameter free)

@@ -9,18 +9,18 @@ ROOT=$PWD
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-BENCH="python3 $ROOT/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-secondary"
+BENCH="python3 $ROOT/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-secondary"
 cd /tmp
 rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o stats --output-format csv -- $BENCH > "$OUT/bench_under_rocprof.log" 2>&1
 echo "[collect] kernel stats done"
 find "$OUT/stats" -name "*kernel_trace*" -delete        # 10^5 records of the synthetic-data generator's kernels
-PMCBENCH="python3 $ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-secondary"
+PMCBENCH="python3 $ROOT/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-secondary"
 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "ssde" -d "$OUT/pmc_fetch" -o fetch --output-format csv -- $PMCBENCH > "$OUT/pmc_fetch.log" 2>&1 || echo "[collect] FETCH_SIZE pass exited non-zero"
 echo "[collect] FETCH_SIZE done"
 rocprofv3 --pmc WRITE_SIZE --kernel-include-regex "ssde" -d "$OUT/pmc_write" -o write --output-format csv -- $PMCBENCH > "$OUT/pmc_write.log" 2>&1 || echo "[collect] WRITE_SIZE pass exited non-zero"
 echo "[collect] WRITE_SIZE done"
 cd "$ROOT"
-python3 bench.py > "$OUT/bench_line.json" 2> "$OUT/bench.err"
+python3 bench.py --full > "$OUT/bench_line.json" 2> "$OUT/bench.err"
 echo "[collect] bench line done"
 python3 tools/bench_configs.py > "$OUT/other_configs.txt" 2> "$OUT/other_configs.err"
 echo "[collect] other configs done"
@@ -33,8 +33,8 @@ echo "[collect] strong-scaling shares done"
 python3 tools/bench_drift.py 10000 10000 9 > "$OUT/drift.txt" 2> "$OUT/drift.err"
 python3 tools/bench_drift.py 10000 1000 18 CTCRW 2 >> "$OUT/drift.txt" 2>> "$OUT/drift.err"
 echo "[collect] drift kernel done"
-python3 bench.py --config c4 --no-cpu-baseline > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.err"
-python3 bench.py --config c5 --no-cpu-baseline > "$OUT/bench_c5.json" 2> "$OUT/bench_c5.err"
+python3 bench.py --full --config c4 --no-cpu-baseline > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.err"
+python3 bench.py --full --config c5 --no-cpu-baseline > "$OUT/bench_c5.json" 2> "$OUT/bench_c5.err"
 echo "[collect] c4 / c5 lines done"
 bash tools/pmc_kernel.sh "iso_shared" ${TAG}_share8 -- python3 $ROOT/tools/bench_strong.py --ranks 8 --evals 20 > /dev/null 2>&1 || true
 bash tools/pmc_kernel.sh "iso_drift" ${TAG}_drift -- python3 $ROOT/tools/bench_drift.py 10000 10000 9 > /dev/null 2>&1 || true
