@@ -75,7 +75,7 @@
 extern "C" {
 #endif
 
-#define SSDE_ABI_VERSION 10
+#define SSDE_ABI_VERSION 11
 
 /* model codes: DATA_STRING(type) of src/smoothSDE.cpp:12-27 */
 enum {
@@ -285,6 +285,9 @@ typedef struct ssde_info_t {
                                echoes the caller's argument -- ABI 10 */
     int32_t exact_hess_scope; /* what ssde_hess is exact over on this handle: 0 nothing (difference the gradient), 1 the drift coefficients
                                  (+ log_lambda), 2 every coefficient of a direct family (+ log_lambda), 3 every free entry (was reserved: 0) */
+    int64_t lagstat_rows;   /* rows of the last evaluation taken from the lag statistics built at create instead of streamed (DESIGN.md
+                               §3.3d; 0: every row was streamed) -- ABI 11 */
+    double  lagstat_create_ms; /* what building those statistics cost ssde_create (0: none built) -- ABI 11 */
 } ssde_info_t;
 
 /* Create an engine: validates the descriptor, finds the ID segments, uploads the
@@ -459,6 +462,16 @@ void ssde_destroy(ssde_handle *h);
 const char *ssde_last_error(const ssde_handle *h);
 
 int ssde_abi_version(void);
+/* The lag statistics ssde_create builds for a stationary batch, computed on the host track by track: the reference
+   the device pass is checked against (through ssde_lagstats_read).  y: the tracks' rows one track after the other, rows[k] rows of d doubles each (row-major;
+   row t of a track here is its tiled row t); M: n_taps x n_taps doubles, s: 2 x n_taps, n_bulk: one double.  With y == NULL only
+   *n_taps and *first_row (the bulk's first row) are written.  Returns SSDE_OK, or SSDE_ERR_ARG for d outside 1..2. */
+int ssde_lagstats_host(const double *y, const int64_t *rows, int64_t n_tracks, int d, double *M, double *s, double *n_bulk,
+                       int32_t *n_taps, int32_t *first_row);
+/* The lag statistics a handle built at create, read back from the device (M: n_taps x n_taps, s: 2 x n_taps, n_bulk: one double; the
+   sizes of ssde_lagstats_host).  SSDE_ERR_ARG when the handle holds none (the dispatch rule did not build them, or a multi-device
+   parent: ask its shards). */
+int ssde_lagstats_read(const ssde_handle *h, double *M, double *s, double *n_bulk);
 
 #ifdef __cplusplus
 }

@@ -17,7 +17,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 MODEL_CODES = {"BM": 0, "OU": 1, "BM_SSM": 2, "OU_SSM": 3, "CTCRW": 4, "BM_t": 5, "ESEAL_SSM": 6, "CIR": 7}
 KALMAN_MODELS = ("BM_SSM", "OU_SSM", "CTCRW")
@@ -95,6 +95,7 @@ class SsdeInfo(C.Structure):
         ("n_rows_tiled", C.c_int64), ("n_groups", C.c_int32), ("n_clean_groups", C.c_int32),
         ("quiet_window", C.c_int32), ("kernel_id", C.c_int32), ("quiet_share", C.c_double),
         ("comm_ranks_reported", C.c_int32), ("exact_hess_scope", C.c_int32),
+        ("lagstat_rows", C.c_int64), ("lagstat_create_ms", C.c_double),
     ]
 
     def as_dict(self):
@@ -496,6 +497,11 @@ def load_library():
     lib.ssde_destroy.restype = None
     lib.ssde_last_error.argtypes = [C.c_void_p]
     lib.ssde_last_error.restype = C.c_char_p
+    lib.ssde_lagstats_host.argtypes = [_dp, C.POINTER(C.c_int64), C.c_int64, C.c_int, _dp, _dp, _dp,
+                                       C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.ssde_lagstats_host.restype = C.c_int
+    lib.ssde_lagstats_read.argtypes = [C.c_void_p, _dp, _dp, _dp]
+    lib.ssde_lagstats_read.restype = C.c_int
     lib.ssde_abi_version.argtypes = []
     lib.ssde_abi_version.restype = C.c_int
     lib.ssde_laplace_eval.argtypes = [C.c_void_p, _dp, C.c_int32, C.c_int32, _dp, _dp, _dp, C.POINTER(SsdeLaplaceOpts)]
@@ -535,7 +541,24 @@ WINDOW_TOL = 1e-11  # largest tolerated relative hand-over disagreement between 
 
 EXPORTED_SYMBOLS = ("ssde_create", "ssde_eval", "ssde_eval_device", "ssde_penalty", "ssde_report", "ssde_widen_windows", "ssde_relax_windows",
                     "ssde_info", "ssde_destroy", "ssde_last_error", "ssde_abi_version", "ssde_comm_unique_id", "ssde_comm_init_rank", "ssde_forget", "ssde_laplace_eval", "ssde_last_kernel_ms", "ssde_kernel_ms_history",
-                    "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce")
+                    "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read")
+
+def lagstats_host(tracks):
+    """The lag statistics ssde_create builds for a stationary batch, computed on the host: `tracks` is a list of
+    (rows x d) arrays of tiled rows.  Returns (M, s, n_bulk, first_row): M (taps x taps), s (2 x taps), the bulk rows, the bulk's first row."""
+    lib = load_library()
+    nt, a0 = C.c_int32(0), C.c_int32(0)
+    lib.ssde_lagstats_host(None, None, 0, 1, None, None, None, C.byref(nt), C.byref(a0))
+    d = int(tracks[0].shape[1])
+    y = np.ascontiguousarray(np.concatenate([np.asarray(t, dtype=np.float64) for t in tracks]))
+    rows = np.array([t.shape[0] for t in tracks], dtype=np.int64)
+    M = np.zeros((nt.value, nt.value)); s = np.zeros((2, nt.value)); n = np.zeros(1)
+    st = lib.ssde_lagstats_host(y.ctypes.data_as(_dp), rows.ctypes.data_as(C.POINTER(C.c_int64)), len(tracks), d,
+                                M.ctypes.data_as(_dp), s.ctypes.data_as(_dp), n.ctypes.data_as(_dp), C.byref(nt), C.byref(a0))
+    if st != 0:
+        raise ValueError(f"ssde_lagstats_host: status {st}")
+    return M, s, float(n[0]), int(a0.value)
+
 
 COMM_ID_BYTES = 128
 
@@ -624,6 +647,17 @@ class Engine:
             err = EngineError(f"ssde call failed ({st}): {msg.decode() if msg else ''}")
             err.status = int(st)
             raise err
+
+    def lagstats(self):
+        """The lag statistics this engine built at create, read back from the device: (M, s, n_bulk), or None when it built none
+        (the host reference is lagstats_host)."""
+        nt, a0 = C.c_int32(0), C.c_int32(0)
+        self.lib.ssde_lagstats_host(None, None, 0, 1, None, None, None, C.byref(nt), C.byref(a0))
+        M = np.zeros((nt.value, nt.value)); s = np.zeros((2, nt.value)); n = np.zeros(1)
+        st = self.lib.ssde_lagstats_read(self._h, M.ctypes.data_as(_dp), s.ctypes.data_as(_dp), n.ctypes.data_as(_dp))
+        if st != 0:
+            return None
+        return M, s, float(n[0])
 
     def info(self) -> dict:
         inf = SsdeInfo()

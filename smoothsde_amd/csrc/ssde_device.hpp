@@ -289,6 +289,11 @@ hipError_t launch_window_check(int model, int d, const IsoArgs& a, hipStream_t s
 struct ReduceArgs;
 // the hand-over checks and the final sums of an isotropic evaluation in ONE launch (the checks raise out[n_out])
 hipError_t launch_iso_finalize(int model, int d, const IsoArgs& a, const ReduceArgs& r, hipStream_t s);
+// lag statistics of a stationary batch (k_lagstats.hip, ssde_lagstats.hpp): per-group Toeplitz sums Qg [G][LAG_N], end corrections
+// Dg [G][LAG_N][LAG_N] and s [G][2][LAG_N], and their fixed-order sums over the groups into Q, D, s
+hipError_t launch_lagstats(const TileView& tv, int d, double* Qg, double* Dg, double* sg, double* Q, double* D, double* s, hipStream_t st);
+struct LagFormArgs;
+hipError_t launch_lag_forms(const LagFormArgs& a, hipStream_t s);
 void fill_stat_consts(int model, int d, IsoArgs& a);
 int iso_nstate(int model, int d);
 

@@ -52,6 +52,7 @@ void release_device(ssde_handle* h) {
                 h->trace_us[4] / h->trace_n);
     destroy_dist(h);
     h->bnd.release(); h->chk.release(); h->group_flags.release(); h->gain_ring.release(); h->pad_pos.release(); h->dirty_groups.release(); h->lap_out.release(); h->nan_bits.release(); h->quiet_flag.release();
+    h->lag_M.release(); h->lag_s.release(); h->lag_glen.release(); h->lag_ns.release(); h->lag_flag.release();
     if (h->gain_pinned) (void)hipHostFree(h->gain_pinned);
     for (int i = 0; i < 2; i++) { if (h->aux[i]) (void)hipStreamDestroy(h->aux[i]); if (h->ev_join[i]) (void)hipEventDestroy(h->ev_join[i]); }
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
@@ -241,6 +242,37 @@ int eval_device(ssde_handle* h, const double* par, int order, double* out_dev, h
 extern "C" {
 
 int ssde_abi_version(void) { return SSDE_ABI_VERSION; }
+
+int ssde_lagstats_host(const double* y, const int64_t* rows, int64_t n_tracks, int d, double* M, double* s, double* n_bulk,
+                       int32_t* n_taps, int32_t* first_row) {
+    if (n_taps) *n_taps = LAG_N;
+    if (first_row) *first_row = LAG_A;
+    if (!y) return SSDE_OK;
+    if (d < 1 || d > 2 || !rows || !M || !s || !n_bulk) return SSDE_ERR_ARG;
+    std::vector<double> Q(LAG_N, 0.0), D((size_t)LAG_N * LAG_N, 0.0), sv(2 * LAG_N, 0.0);
+    double n = 0.0;
+    int64_t off = 0;
+    for (int64_t k = 0; k < n_tracks; k++) {
+        if (rows[k] > LAG_A) {
+            lag_track_stats(y + off * d, (int)rows[k], d, Q.data(), D.data(), sv.data());
+            n += (double)(rows[k] - LAG_A);
+        }
+        off += rows[k];
+    }
+    lag_assemble(Q.data(), D.data(), M);
+    for (int i = 0; i < 2 * LAG_N; i++) s[i] = sv[i];
+    *n_bulk = n;
+    return SSDE_OK;
+}
+
+int ssde_lagstats_read(const ssde_handle* h, double* M, double* s, double* n_bulk) {
+    if (!h || !M || !s || !n_bulk || !h->lag_ready) return SSDE_ERR_ARG;
+    if (hipSetDevice(h->device) != hipSuccess) return SSDE_ERR_HIP;
+    if (hipMemcpy(M, h->lag_M.p, h->lag_M.n * 8, hipMemcpyDeviceToHost) != hipSuccess) return SSDE_ERR_HIP;
+    if (hipMemcpy(s, h->lag_s.p, h->lag_s.n * 8, hipMemcpyDeviceToHost) != hipSuccess) return SSDE_ERR_HIP;
+    *n_bulk = h->lag_n;
+    return SSDE_OK;
+}
 
 int ssde_create(const ssde_desc* desc, ssde_handle** out) {
     if (!desc || !out) { g_create_error = "NULL argument"; return SSDE_ERR_ARG; }
@@ -502,7 +534,7 @@ int run_checked(ssde_handle* h, const double* par, int order, std::vector<double
         }
         // (one window has no hand-over to disagree -- unless quiet rows ran: their switch check is folded into the same
         //  value, and a longer memory, finally none at all, is the repair)
-        if (!dist && h->last_chunks <= 1 && h->last_quiet_window == 0) break;
+        if (!dist && h->last_chunks <= 1 && h->last_quiet_window == 0 && h->last_lag_rows == 0) break;
         // a non-finite nllk is rejected by the caller whatever the windows did: no retry, and no lasting
         // widening of the plan because an optimiser probed an absurd parameter once
         if (!std::isfinite(o[0])) break;
@@ -824,7 +856,7 @@ int ssde_info(const ssde_handle* h, ssde_info_t* info) {
             const bool first_part = k % P == 0;
             if (k == 0) *info = si;
             else {
-                if (first_part) { info->n_tracks += si.n_tracks; info->n_rows += si.n_rows; info->n_steps += si.n_steps; info->main_kernel_rows += si.main_kernel_rows; }
+                if (first_part) { info->n_tracks += si.n_tracks; info->n_rows += si.n_rows; info->n_steps += si.n_steps; info->main_kernel_rows += si.main_kernel_rows; info->lagstat_rows += si.lagstat_rows; info->lagstat_create_ms = std::max(info->lagstat_create_ms, si.lagstat_create_ms); }
                 info->hbm_bytes += si.hbm_bytes;
                 info->n_rows_tiled += si.n_rows_tiled; info->n_groups += si.n_groups; info->n_clean_groups += si.n_clean_groups;
                 info->quiet_window = std::max(info->quiet_window, si.quiet_window); info->quiet_share = std::max(info->quiet_share, si.quiet_share);
@@ -906,10 +938,10 @@ int ssde_info(const ssde_handle* h, ssde_info_t* info) {
     // rows scored by the dominant launch: everything, except on the shared-covariance path where the
     // windows that touch the covariance transient run in the small concurrent launch
     info->main_kernel_rows = h->n_steps;
-    if (h->path == PATH_ISO && h->last_s_stat >= 0 && h->rows_key[0] == h->last_chunks &&
+    if (h->path == PATH_ISO && h->last_lag_rows == 0 && h->last_s_stat >= 0 && h->rows_key[0] == h->last_chunks &&
         h->rows_key[1] == h->last_window && h->rows_key[2] == h->last_s_stat + 100000 * h->last_t0) {
         info->main_kernel_rows = h->rows_cached;
-    } else if (h->path == PATH_ISO && h->last_s_stat >= 0) {
+    } else if (h->path == PATH_ISO && h->last_lag_rows == 0 && h->last_s_stat >= 0) {
         int64_t rows = 0;
         const int nc = h->last_chunks;
         for (int g = 0; g < h->n_groups; g++) {
@@ -928,6 +960,10 @@ int ssde_info(const ssde_handle* h, ssde_info_t* info) {
         h->rows_cached = rows;
         h->rows_key[0] = h->last_chunks; h->rows_key[1] = h->last_window; h->rows_key[2] = h->last_s_stat + 100000 * h->last_t0;
     }
+    // (rows past LAG_A taken from the lag statistics were not streamed by any launch)
+    if (h->path == PATH_ISO && h->last_lag_rows > 0) info->main_kernel_rows = h->n_steps - h->last_lag_rows;
+    info->lagstat_rows = h->path == PATH_ISO ? h->last_lag_rows : 0;
+    info->lagstat_create_ms = h->lag_create_ms;
     return SSDE_OK;
 }
 

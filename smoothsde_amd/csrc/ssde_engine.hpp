@@ -17,6 +17,7 @@
 #include "../../include/ssde.h"
 #include "ssde_device.hpp"
 #include "ssde_host.hpp"
+#include "ssde_lagstats.hpp"
 #include "ssde_tv.hpp"
 
 namespace ssde_engine {
@@ -299,6 +300,14 @@ struct ssde_handle {
     int comm_ranks = 1;                       // ranks of a multi-process communicator (the caller's argument)
     int comm_ranks_reported = 0;              // ... what ncclCommCount says about it (0: no communicator)
     bool comm_defer = false;                  // SSDE_OPT_COMM_DEFER: ssde_eval_device leaves the rank's partial result to the caller's own collective
+    // the bulk of a stationary batch from lag statistics (ssde_lagstats.hpp): built at create when the rule engages it
+    bool lag_ready = false;
+    DevBuf<double> lag_M, lag_s;           // [LAG_N][LAG_N], [2][LAG_N]
+    DevBuf<int32_t> lag_glen, lag_ns;      // group_len / lane_nsteps capped at LAG_A: what the streamed head launch walks
+    DevBuf<double> lag_flag;               // the bulk's check value (one word, zero between launches; the finalize launch folds it in)
+    double lag_n = 0.0;                    // bulk rows (past LAG_A) of the batch
+    int64_t lag_rows = 0, last_lag_rows = 0;   // ... and those the last evaluation took from the statistics (0: streamed)
+    double lag_create_ms = 0.0;            // what building them cost at create
     int last_kernel_id = 0;                   // SSDE_KERNEL_*: the family that ran the last evaluation's rows
     // where a stamped synchronous evaluation spent its time (ssde_last_phase_ms): events on the evaluation's stream
     hipEvent_t ev_ph[3] = {nullptr, nullptr, nullptr};   // first operation | end of the finalising launch | end of the all-reduce

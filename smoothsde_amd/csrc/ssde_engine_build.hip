@@ -130,6 +130,58 @@ int lattice_pad(const ssde_desc* d, ssde_handle* h, const std::vector<int64_t>& 
 namespace ssde_engine {
 constexpr int SSDE_RETRY_WITHOUT_DRIFT = -77;     // internal: the drift layout was tried and the data do not qualify
 constexpr int SSDE_RETRY_WITHOUT_PP = -78;        // internal: the drift's blocks were tiled as covariates and the lanes that would read them are the general ones
+// The lag statistics of a stationary batch (ssde_lagstats.hpp): CTCRW on the shared-covariance path, every group
+// complete, regular grid, no drift.  The rule is the measured crossover (profiles/r06_c_lagstats_crossover.txt: bench.py both ways
+// at 7e6 - 2e7 bulk rows): an evaluation on the path costs ~0.07 ms whatever the batch (the head launch's ~256-row critical path,
+// the forms' launch, the fixed costs), the streamed one grows with the rows; the two meet at 1.2 - 1.4e7 rows past LAG_A (7.4e6:
+// 0.072 against 0.067 ms, 1.24e7: 0.072 / 0.077, 1.74e7: 0.072 / 0.096).  Built from LAG_MIN_BULK_ROWS, above every crossover seen.
+constexpr double LAG_MIN_BULK_ROWS = 1.6e7;
+static int build_lagstats(ssde_handle* h, int G, const std::vector<int32_t>& lane_ns, const std::vector<int32_t>& glen) {
+    if (const char* e = getenv("SSDE_LAGSTATS")) if (atoi(e) == 0) return SSDE_OK;
+    if (!(h->model == SSDE_MODEL_CTCRW && h->use_shared && !h->drift && h->n_clean_groups == G && h->uniform_dt && h->iso_parts == 1 &&
+          (h->d == 1 || h->d == 2) && h->glen_max > LAG_A))
+        return SSDE_OK;
+    int64_t bulk = 0;
+    for (int32_t ns : lane_ns) bulk += ns > LAG_A ? ns - LAG_A : 0;
+    const bool forced = getenv("SSDE_LAGSTATS") && atoi(getenv("SSDE_LAGSTATS")) == 2;     // (testing: whatever the rule says)
+    if (!forced && (double)bulk < LAG_MIN_BULK_ROWS) return SSDE_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    TileView tv;
+    tv.tiles = h->tiles.p; tv.group_off = h->group_off.p; tv.group_len = h->group_len.p; tv.lane_nsteps = h->lane_nsteps.p;
+    tv.a0 = h->a0.p; tv.n_groups = G; tv.C = h->C; tv.c_obs = h->c_obs; tv.dt_all = h->dt_all;
+    DevBuf<double> Qg, Dg, sg, sums;
+    const size_t NN = (size_t)LAG_N * LAG_N;
+    // The per-group temporaries (Dg: G x LAG_N^2 doubles, 46 MB at 10^4 tracks) are an optimisation's: a device that cannot hold them
+    // streams every row, as without the statistics
+    if (Qg.alloc((size_t)G * LAG_N) != hipSuccess || Dg.alloc((size_t)G * NN) != hipSuccess || sg.alloc((size_t)G * 2 * LAG_N) != hipSuccess ||
+        sums.alloc(LAG_N + NN + 2 * LAG_N) != hipSuccess) {
+        (void)hipGetLastError();
+        Qg.release(); Dg.release(); sg.release(); sums.release();
+        return SSDE_OK;
+    }
+    HIPCHK(h, launch_lagstats(tv, h->d, Qg.p, Dg.p, sg.p, sums.p, sums.p + LAG_N, sums.p + LAG_N + NN, 0));
+    std::vector<double> host(sums.n), M(NN);
+    HIPCHK(h, hipMemcpy(host.data(), sums.p, host.size() * 8, hipMemcpyDeviceToHost));
+    Qg.release(); Dg.release(); sg.release(); sums.release();
+    lag_assemble(host.data(), host.data() + LAG_N, M.data());
+    HIPCHK(h, h->lag_M.upload(M));
+    HIPCHK(h, h->lag_s.upload(std::vector<double>(host.begin() + LAG_N + NN, host.end())));
+    std::vector<int32_t> cg(glen.begin(), glen.end()), cn(lane_ns.begin(), lane_ns.end());
+    for (auto& v : cg) v = std::min(v, (int32_t)LAG_A);
+    for (auto& v : cn) v = std::min(v, (int32_t)LAG_A);
+    HIPCHK(h, h->lag_glen.upload(cg));
+    HIPCHK(h, h->lag_ns.upload(cn));
+    HIPCHK(h, h->lag_flag.alloc(1));
+    HIPCHK(h, hipMemset(h->lag_flag.p, 0, 8));
+    HIPCHK(h, hipDeviceSynchronize());
+    h->lag_rows = bulk;
+    h->lag_n = (double)bulk;
+    h->lag_ready = true;
+    h->lag_create_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    h->hbm_bytes += (int64_t)(NN + 2 * LAG_N) * 8;
+    return SSDE_OK;
+}
+
 // ---- step 5 (register path): which lanes run it (shared covariance / own covariance, with or without drift columns), how many
 // time windows, and the buffers of the hand-over check.  gflags[g] != 0: group g has no missing row; glen: padded steps per group ----
 static int plan_register_path(ssde_handle* h, int G, const std::vector<int32_t>& gflags, const std::vector<int32_t>& lane_ns,
@@ -437,7 +489,7 @@ static int plan_register_path(ssde_handle* h, int G, const std::vector<int32_t>&
     h->partial_doubles = (size_t)std::max(MAX_PARTS, CV_WAVES) * buf_chunks * std::max(NACC_MAX, 2 + CV_KC + 2) * G;
     if (h->cv_adj) h->partial_doubles = std::max(h->partial_doubles, (size_t)buf_chunks * adj_nacc(h->model, h->d, h->n_stream_cols, true) * G);
     h->hbm_bytes += (int64_t)(h->bnd.n + h->chk.n) * 8;
-    return SSDE_OK;
+    return build_lagstats(h, G, lane_ns, glen);
 }
 
 static int build_impl(const ssde_desc* d, ssde_handle* h, const ParLayout* part_layout, bool allow_drift);

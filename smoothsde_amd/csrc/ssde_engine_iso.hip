@@ -2,6 +2,7 @@
 // window plan, the gain table of the shared-covariance kernels, the launches (shared / general / drift / mixed batch) and
 // the finalising launch (hand-over checks + fixed-order sums).  Called from eval_device (ssde_engine.hip).
 #include "ssde_engine.hpp"
+#include "ssde_tf.hpp"
 
 #include <chrono>
 
@@ -234,6 +235,38 @@ int build_gain_table(ssde_handle* h, IsoArgs& a, int mask, hipStream_t s, double
     return SSDE_OK;
 }
 
+// The bulk's forms at this evaluation (ssde_lagstats.hpp): the taps are the impulse responses of the lanes' own stationary step
+// (TfCtcrw::step_stat, ssde_tf.hpp, here on the host) to a unit increment -- u for lam, r for rr -- and the constants those lanes
+// finish with.  K taps for the forms, K - LAG_CHECK for the check.
+void lag_form_args(ssde_handle* h, const IsoArgs& a, int order, int K, LagFormArgs& f) {
+    TfCtcrw<1, DIR_SIG | DIR_MU> T;
+    T.setup(a);
+    T.cm[0] = 0.0;                              // (the mu dt terms enter through s and n)
+    double y = 0.0;
+    T.init(&y);
+    y = 1.0;                                    // dy_0 = 1, then 0
+    for (int t = 0; t < LAG_N; t++) {
+        T.reset_acc();
+        T.step_stat(&y);
+        f.lam[t] = t <= K ? T.su[0] : 0.0;
+        f.rr[t] = t <= K ? T.r1[0] : 0.0;
+    }
+    f.M = h->lag_M.p; f.s = h->lag_s.p; f.n = h->lag_n;
+    f.K = K; f.Kc = K - LAG_CHECK; f.d = h->d; f.mask = order >= 1 ? a.part_mask[0] : 0;
+    for (int c = 0; c < 2; c++) {
+        const int k = c ? f.Kc : f.K;
+        double sl = 0.0, sr[3] = {0.0, 0.0, 0.0};
+        for (int i = 0; i <= k; i++) sl += f.lam[i];
+        for (int j = 0; j < 3; j++)
+            for (int i = j + 1; i <= k; i++) sr[j] += f.rr[i - j - 1];
+        f.sum_lam[c] = sl;
+        for (int j = 0; j < 3; j++) f.sum_rho[c][j] = sr[j];
+    }
+    for (int i = 0; i < 2; i++) f.cm[i] = i < h->d ? a.statc[29 + i] : 0.0;
+    for (int i = 0; i < 48; i++) f.statc[i] = a.statc[i];
+    f.n_groups = h->n_groups;
+}
+
 }  // namespace
 
 namespace ssde_engine {
@@ -242,6 +275,7 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
     const ParLayout& L = h->L;
     IsoArgs a;
     memset(&a, 0, sizeof(a));
+    h->last_lag_rows = 0;
     a.tv.tiles = h->tiles.p; a.tv.group_off = h->group_off.p; a.tv.group_len = h->group_len.p;
     a.tv.lane_nsteps = h->lane_nsteps.p; a.tv.a0 = h->a0.p; a.tv.n_groups = h->n_groups; a.tv.C = h->C; a.tv.c_obs = h->c_obs; a.tv.dt_all = h->dt_all;
     a.partials = h->partials.p;
@@ -340,6 +374,7 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
     a.group_flags = h->group_flags.p;
     a.group_mode = 0;
     double add[4] = {0, 0, 0, 0};
+    int lag_K = 0;                           // > 0: rows past LAG_A from the lag statistics, with this many taps
     if (!h->use_shared && h->quiet_ok) {
         int st = (h->d == 1) ? build_gain_table<1>(h, a, h->iso_free_mask, s, add) : build_gain_table<2>(h, a, h->iso_free_mask, s, add);
         if (st) return st;
@@ -352,6 +387,25 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
         if (st) return st;
         if (h->trace) { const double t = tick(); h->trace_us[1] += t - tk0; tk0 = t; }
         a.group_mode = 3;
+        // Rows past LAG_A from the lag statistics, decided here for this evaluation: the cut K the window plan asks
+        // for must fit the statistics (K <= LAG_KMAX) and the head (the stationary gains from row s_stat, K rows before LAG_A);
+        // a plan that has given up, or gains that never became stationary, stream every row
+        if (h->lag_ready && !h->drift && !h->hess_req && a.n_parts == 1 && !h->gave_up && h->gain_stationary && a.gain_stat[0] != 0.0 &&
+            h->plan_warmup > 0) {
+            const int s_stat = (a.gain_last + SHARED_U - 1) / SHARED_U * SHARED_U;
+            if (h->plan_warmup <= LAG_KMAX && s_stat + h->plan_warmup <= LAG_A) lag_K = h->plan_warmup;
+        }
+        if (lag_K > 0) {
+            // the head: every track capped at LAG_A rows, planned as a batch of that length
+            a.tv.group_len = h->lag_glen.p; a.tv.lane_nsteps = h->lag_ns.p;
+            const int gl = h->glen_max;
+            h->glen_max = LAG_A;
+            plan_windows(h, a, &a.n_chunks, &a.window);
+            h->glen_max = gl;
+            h->last_chunks = a.n_chunks; h->last_window = a.window;
+            h->last_lag_rows = h->lag_rows;
+        }
+        const int glen = lag_K > 0 ? LAG_A : h->glen_max;
         // the covariance transient gets its own short window [0, t0): every other window (warm-up
         // included) then lies in the stationary regime and runs the lean kernel
         // A batch with more track groups than SIMDs needs no time windows to fill the chip, but the lean
@@ -365,13 +419,13 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
             a.n_chunks = 1; a.window = h->plan_warmup;
             const int s_stat0 = (a.gain_last + SHARED_U - 1) / SHARED_U * SHARED_U;
             const int t0c = (s_stat0 + a.window + WIN_ALIGN - 1) / WIN_ALIGN * WIN_ALIGN;
-            if (t0c + 2 * a.window < h->glen_max) { a.t0 = t0c; a.n_chunks = 2; h->last_window = a.window; }
+            if (t0c + 2 * a.window < glen) { a.t0 = t0c; a.n_chunks = 2; h->last_window = a.window; }
             else a.window = 0;
         } else
         if (a.n_chunks > 1) {
             const int s_stat = (a.gain_last + SHARED_U - 1) / SHARED_U * SHARED_U;
             a.t0 = (s_stat + a.window + WIN_ALIGN - 1) / WIN_ALIGN * WIN_ALIGN;
-            if (a.t0 + 2 * a.window >= h->glen_max) { a.t0 = 0; }            // tracks too short to bother
+            if (a.t0 + 2 * a.window >= glen) { a.t0 = 0; }                   // tracks too short to bother
             else if (a.n_chunks < h->max_chunks) a.n_chunks += 1;           // window 0 + the planned ones
         }
         h->last_chunks = a.n_chunks;
@@ -434,6 +488,8 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
         ra.n_parts = a.n_parts * ncr; ra.nacc = nacc; ra.n_blocks = h->n_groups;
         ra.n_value_parts = ncr; ra.chunks_per_part = ncr;
         ra.chk = h->chk.p; ra.n_chk = a.n_chunks > 1 ? a.n_parts * (a.n_chunks - 1) * h->n_groups : 0;
+        // the bulk's forms: one more window of the partial sums (group 0; lag_forms_kernel), summed with the others in the same order
+        if (lag_K > 0) { ra.n_parts += 1; ra.n_value_parts += 1; ra.chunks_per_part += 1; }
         if (order >= 1 && h->cv_adj) {
             // accumulators of k_iso_adj.hip: [value | log sigma_obs | mu_a | par[d] | par[d + 1] | per streamed column: par[d], par[d + 1] (, mu_a)]
             const int nkp = h->model == SSDE_MODEL_BM_SSM ? 1 : 2, nk = adj_nk(h->model, h->d, a.cv_mu_cols != 0);
@@ -502,6 +558,7 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
                 HIPCHK(h, hipMemsetAsync(h->partials.p, 0, (size_t)std::max(a.n_chunks, ad.n_chunks) * (4 + h->d) * h->n_groups * 8, s));
             }
         }
+        if (lag_K > 0 && !fused) a.quiet_flag = h->lag_flag.p;     // (the finalize launch folds the bulk's check into out[n_out])
         IsoArgs b = a;
         b.group_mode = 2;
         if (!h->wave_clock_file.empty()) {
@@ -531,6 +588,15 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
                 b.fused = 1;
                 b.fuse_arrive = h->fuse_words.p + 4; b.fuse_done = h->fuse_words.p;
                 b.chk_out = (double*)(h->fuse_words.p + 2);         // (its own word, zero between launches: the last wave moves it to out[n_out])
+            }
+            if (lag_K > 0) {
+                // the forms first: their partial sums and check are in place before the head's reduction runs (either form)
+                LagFormArgs f;
+                memset(&f, 0, sizeof(f));
+                lag_form_args(h, a, order, lag_K, f);
+                f.partials = h->partials.p; f.chunk = a.n_chunks; f.kfast = fused ? 1 : 0;
+                f.chk = fused ? b.chk_out : h->lag_flag.p;
+                HIPCHK(h, launch_lag_forms(f, s));
             }
             HIPCHK(h, launch_iso_shared(h->model, h->d, b, ra, s, h->stamps ? h->ev_k0 : nullptr, h->stamps ? h->ev_k1 : nullptr));
         }

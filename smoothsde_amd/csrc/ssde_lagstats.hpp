@@ -1,0 +1,77 @@
+// ssde_lagstats.hpp -- the bulk of a stationary batch from lag statistics.
+//
+// Past the covariance transient the CTCRW filter on a regular grid is linear and time-invariant in the increments
+// dy_t = y_t - y_{t-1} - mu dt (ssde_tf.hpp): the innovation and the r signal of the transfer-function lanes are
+//     u_t = sum_i lam_i dy_{t-i},     r_{t-k} = sum_i rr_{i-k} dy_{t-i},
+// with impulse responses that decay like rho^i.  Cut at K taps (the warm-up the window plan asks for), every sum the stationary
+// lanes accumulate over rows t >= A (S = sum u^2, C_k = sum u r_{t-k}, su = sum u) is a quadratic or linear form in the data with
+// coefficients that depend on theta only through the taps:
+//     sum_t u_t v_t = lam' M v - ...  (the mu dt terms: s and n below),
+// where, per batch (summed over tracks, and over the response coordinates for M),
+//     M_ik = sum_{t = A}^{n - 1} Dy_{t-i} Dy_{t-k},   s_{a,i} = sum_{t = A}^{n - 1} Dy_{a, t-i},   n = rows past A,
+// Dy = y_t - y_{t-1}.  M is built at create as Toeplitz lag sums plus the corrections at the bulk's two ends:
+//     M_{i, i+l} = Q_l + sum_{m < i} (h_m h_{m+l} - g_m g_{m+l}),    Q_l = sum_{t = A}^{n - 1} Dy_t Dy_{t-l},
+// h_j = Dy_{A-1-j} (head), g_j = Dy_{n-1-j} (tail); s telescopes: s_{a,i} = y_{n-1-i} - y_{A-1-i}.
+#pragma once
+#include <stdint.h>
+
+namespace ssde {
+
+constexpr int LAG_N = 192;            // taps held: K_max + 1
+constexpr int LAG_KMAX = LAG_N - 1;   // the longest cut an evaluation may ask for
+constexpr int LAG_A = 256;            // first bulk row (multiple of WIN_ALIGN); rows [0, LAG_A) of every track are streamed
+constexpr int LAG_CHECK = 16;         // the bulk's check: the same forms with this many taps fewer
+constexpr int LAG_LB = 32;            // lags per work item of the Toeplitz pass (k_lagstats.hip)
+static_assert(LAG_A > LAG_N, "the head and the lag window of the first bulk row must lie inside the track");
+static_assert(LAG_N % LAG_LB == 0 && LAG_N % 64 == 0, "lag blocks");
+
+// M (LAG_N x LAG_N, symmetric) from the Toeplitz sums Q[l] and D[p * LAG_N + q] = sum (h_p h_q - g_p g_q); fixed order
+inline void lag_assemble(const double* Q, const double* D, double* M) {
+    for (int l = 0; l < LAG_N; l++) {
+        double run = Q[l];
+        for (int i = 0; i + l < LAG_N; i++) {
+            M[(int64_t)i * LAG_N + i + l] = M[(int64_t)(i + l) * LAG_N + i] = run;
+            run += D[(int64_t)i * LAG_N + i + l];
+        }
+    }
+}
+
+// The same statistics on the host, track by track (the CPU reference of ssde_lagstats_host): y[track][row][coordinate] with
+// rows[track] rows each, stored one track after the other.  Q, D accumulate over tracks and coordinates, s[a][i] per coordinate.
+inline void lag_track_stats(const double* y, int rows, int d, double* Q, double* D, double* s) {
+    const int n = rows;
+    if (n <= LAG_A) return;
+    auto Y = [&](int t, int a) { return y[(int64_t)t * d + a]; };
+    auto Dy = [&](int t, int a) { return Y(t, a) - Y(t - 1, a); };
+    for (int a = 0; a < d; a++) {
+        for (int l = 0; l < LAG_N; l++) {
+            double q = 0.0;
+            for (int t = LAG_A; t < n; t++) q += Dy(t, a) * Dy(t - l, a);
+            Q[l] += q;
+        }
+        for (int p = 0; p < LAG_N; p++)
+            for (int q = 0; q < LAG_N; q++)
+                D[(int64_t)p * LAG_N + q] += Dy(LAG_A - 1 - p, a) * Dy(LAG_A - 1 - q, a) - Dy(n - 1 - p, a) * Dy(n - 1 - q, a);
+        for (int i = 0; i < LAG_N; i++) s[a * LAG_N + i] += Y(n - 1 - i, a) - Y(LAG_A - 1 - i, a);
+    }
+}
+
+// the per-evaluation forms (k_lagstats.hip: lag_forms_kernel)
+struct LagFormArgs {
+    const double* M;                  // [LAG_N][LAG_N]
+    const double* s;                  // [2][LAG_N]
+    double n;                         // bulk rows
+    int K, Kc;                        // taps 0..K of the forms, 0..Kc of the check
+    int d, mask;                      // response coordinates, DIR_* bits of the evaluation
+    double lam[LAG_N];                // impulse response of u
+    double rr[LAG_N];                 // impulse response of r (r_{t-k}: rr shifted by k)
+    double sum_lam[2], sum_rho[2][3]; // sums of the taps 0..K (index 0) and 0..Kc (index 1)
+    double cm[2];                     // mu_a dt
+    double statc[48];                 // the stationary constants (IsoArgs.statc): tf_finish forms the accumulators from them
+    double* partials;                 // the evaluation's partial sums: this writes window `chunk` of every group
+    int chunk, n_groups, kfast;
+    double* chk;                      // raised to the relative difference between the two cuts (a non-negative double as its bit pattern)
+};
+static_assert(sizeof(LagFormArgs) <= 4096, "lag_forms_kernel takes its arguments by value");
+
+}  // namespace ssde

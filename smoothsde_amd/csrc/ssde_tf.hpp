@@ -23,6 +23,24 @@ namespace ssde {
 // this replaces, ~120 in the general filter), which moves the headline kernel from fp64 issue to HBM.
 // The hand-over dump converts back to the direction form the other kernels use (x, v and their
 // sensitivities are short linear combinations of y_{t-1}, w and r), so the window check is unchanged.
+// The accumulators [value | sigma_obs | mu_1 .. mu_d | par d | par d + 1] from the sums of the stationary rows: S = sum u^2,
+// C_k = sum u r_{t-k}, su_a = sum u_a, with the stationary constants c = IsoArgs.statc.  TfCtcrw::finish and the bulk's forms
+// (k_lagstats.hip: lag_forms_kernel) both end here.
+SSDE_HD void tf_finish(const double* c, int d, int mask, double S, double C1, double C2, double C3, const double* su, double* out) {
+    const double iF = c[0];
+    out[0] = 0.5 * iF * S;
+    const int slot[NDIRP] = {1, 2 + d, 3 + d};
+#pragma unroll
+    for (int k = 1; k < 4 + d; k++) out[k] = 0.0;
+#pragma unroll
+    for (int j = 0; j < NDIRP; j++)
+        if (mask & dir_bit(j)) out[slot[j]] = c[10 + j] * S + iF * (c[31 + j] * C1 + c[34 + j] * C2 + c[37 + j] * C3);
+    if (mask & DIR_MU) {
+#pragma unroll
+        for (int a = 0; a < d; a++) out[2 + a] = -iF * c[46] * su[a];
+    }
+}
+
 template <int D, int MASK>
 struct TfCtcrw {
     static constexpr int SD = 2 * D;
@@ -33,25 +51,25 @@ struct TfCtcrw {
     double e, nd1, nd2, cm[D];
     const double* c;   // the argument block's constants (scalar loads, used outside the row loop only)
 
-    __device__ __forceinline__ void setup(const IsoArgs& A) {
+    SSDE_HD void setup(const IsoArgs& A) {
         c = A.statc;
         e = c[5]; nd1 = c[26]; nd2 = c[27];
 #pragma unroll
         for (int a = 0; a < D; a++) cm[a] = c[29 + a];
     }
     // yprev = the observation of the row BEFORE the window's first row
-    __device__ __forceinline__ void init(const double* yprev) {
+    SSDE_HD void init(const double* yprev) {
 #pragma unroll
         for (int a = 0; a < D; a++) { yp[a] = yprev[a]; w1[a] = w2[a] = r1[a] = r2[a] = r3[a] = 0.0; }
         reset_acc();
     }
-    __device__ __forceinline__ void reset_acc() {
+    SSDE_HD void reset_acc() {
         acc2 = C1 = C2 = C3 = 0.0;
 #pragma unroll
         for (int a = 0; a < D; a++) su[a] = 0.0;
     }
-    __device__ __forceinline__ void step_table(const double*, const double*, const double*) {}  // never used
-    __device__ __forceinline__ void step_stat(const double* y) {
+    SSDE_HD void step_table(const double*, const double*, const double*) {}  // never used
+    SSDE_HD void step_stat(const double* y) {
 #pragma unroll
         for (int a = 0; a < D; a++) {
             const double dy = (y[a] - yp[a]) - cm[a];
@@ -70,20 +88,7 @@ struct TfCtcrw {
             w2[a] = w1[a]; w1[a] = w0;
         }
     }
-    __device__ __forceinline__ void finish(double* out) const {
-        const double iF = c[0];
-        out[0] = 0.5 * iF * acc2;
-        const int slot[NDIRP] = {1, 2 + D, 3 + D};
-#pragma unroll
-        for (int k = 1; k < 4 + D; k++) out[k] = 0.0;
-#pragma unroll
-        for (int j = 0; j < NDIRP; j++)
-            if (MASK & dir_bit(j)) out[slot[j]] = c[10 + j] * acc2 + iF * (c[31 + j] * C1 + c[34 + j] * C2 + c[37 + j] * C3);
-        if (MASK & DIR_MU) {
-#pragma unroll
-            for (int a = 0; a < D; a++) out[2 + a] = -iF * c[46] * su[a];
-        }
-    }
+    SSDE_HD void finish(double* out) const { tf_finish(c, D, MASK, acc2, C1, C2, C3, su, out); }
     // hand-over states in DIRECTION form (what the transient kernel and k_iso.hip dump): the state on
     // arrival at the next row t, from y_{t-1}, w_{t-1}, w_{t-2}, r_{t-1..t-3}
     //   x = y_{t-1} + mu dt - c1 w_{t-1} + d2 w_{t-2}          v = k2 w_{t-1} + mu
