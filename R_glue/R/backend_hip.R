@@ -36,7 +36,7 @@ pp_table <- function(sm, x) {
 #'
 #' @param sde SDE object (after initialize)
 #' @param tmb_dat,tmb_par,map the lists SDE$setup has just assembled (R/sde.R:504-536, 621-632)
-#' @return list(par, fn, gr, he, report, env) shaped like TMB::MakeADFun's value
+#' @return list(par, fn, gr, he, report, smooth, env) shaped like TMB::MakeADFun's value (smooth: ssde_smooth)
 #' @param random NULL (joint objective: every free entry is optimised, what tmb_obj_joint is, R/sde.R:666-668) or
 #'   "coeff_re": the returned fn / gr are the Laplace marginal over coeff_re (ssde_laplace_eval), log_lambda is a free
 #'   outer parameter, and env$last.par holds c(theta, u_hat) after every call -- the semantics of
@@ -143,6 +143,14 @@ make_hip_obj <- function(sde, tmb_dat, tmb_par, map, device = NULL, random = NUL
          report = function(x = par_full[free]) {
              full <- par_full; full[free] <- x
              list(aest_all = .Call("ssdeR_report", ptr, full, PACKAGE = "smoothSDE"))
+         },
+         # fixed-interval smoother of the state-space families (ssde_smooth): smoothed states, their covariances and the
+         # whitened one-step-ahead innovations (the Kalman models' residuals; NaN on each track's first row)
+         smooth = function(x = par_full[free]) {
+             full <- par_full; full[free] <- x
+             out <- .Call("ssdeR_smooth", ptr, full, as.integer(ncol(spec$obs)), PACKAGE = "smoothSDE")
+             dim(out$cov) <- c(nrow(out$mean), ncol(out$mean), ncol(out$mean))
+             out
          },
          env = env, ptr = ptr)
 }

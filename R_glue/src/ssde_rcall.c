@@ -11,6 +11,8 @@
  *   ssdeR_create(spec)              -> external pointer        (replaces MakeADFunObject)
  *   ssdeR_eval(ptr, par, order)     -> list(value=, gradient=) (replaces EvalADFunObject)
  *   ssdeR_report(ptr, par)          -> n x sdim matrix aest_all (replaces obj$report()$aest_all)
+ *   ssdeR_smooth(ptr, par, n_dim)   -> list(mean = n x sdim, cov = n * sdim * sdim values (dim() set in R), resid = n x n_dim):
+ *                                      the fixed-interval smoother and whitened innovations (ssde_smooth)
  *   ssdeR_laplace(ptr, par, order)  -> list(value=, gradient=, par=, hessian.random=): the Laplace marginal over
  *                                      coeff_re, i.e. what fn / gr ARE when MakeADFun gets random = "coeff_re"
  *                                      (R/sde.R:510-525, 656-658); par comes back with coeff_re at u_hat
@@ -216,6 +218,26 @@ SEXP ssdeR_report(SEXP ptr, SEXP par) {
     return out;
 }
 
+SEXP ssdeR_smooth(SEXP ptr, SEXP par, SEXP n_dim) {
+    ssde_handle *h = (ssde_handle *)R_ExternalPtrAddr(ptr);
+    if (!h) Rf_error("engine handle was destroyed (call $setup() again)");
+    ssde_info_t inf;
+    ssde_info(h, &inf);
+    int d = INTEGER(n_dim)[0];
+    SEXP mean = PROTECT(Rf_allocMatrix(REALSXP, (int)inf.n_rows, inf.sdim));
+    SEXP cov = PROTECT(Rf_allocVector(REALSXP, (R_xlen_t)inf.n_rows * inf.sdim * inf.sdim));
+    SEXP resid = PROTECT(Rf_allocMatrix(REALSXP, (int)inf.n_rows, d));
+    int st = ssde_smooth(h, REAL(par), (int)Rf_xlength(par), REAL(mean), REAL(cov), REAL(resid));
+    if (st != SSDE_OK) { UNPROTECT(3); Rf_error("ssde_smooth failed (%d): %s", st, ssde_last_error(h)); }
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 3));
+    SEXP nm = PROTECT(Rf_allocVector(STRSXP, 3));
+    SET_STRING_ELT(nm, 0, Rf_mkChar("mean")); SET_STRING_ELT(nm, 1, Rf_mkChar("cov")); SET_STRING_ELT(nm, 2, Rf_mkChar("resid"));
+    SET_VECTOR_ELT(out, 0, mean); SET_VECTOR_ELT(out, 1, cov); SET_VECTOR_ELT(out, 2, resid);
+    Rf_setAttrib(out, R_NamesSymbol, nm);
+    UNPROTECT(5);
+    return out;
+}
+
 /* he(x): exact second derivatives of the joint penalised nllk over the 0-based full-parameter indices `idx` (ssde_hess:
  * direct families BM / OU).  Returns NULL where the engine has no exact Hessian: the R side then differences gr(). */
 SEXP ssdeR_hess(SEXP ptr, SEXP par, SEXP idx) {
@@ -255,6 +277,7 @@ static const R_CallMethodDef ssde_calldefs[] = {
     {"ssdeR_eval", (DL_FUNC)&ssdeR_eval, 3},
     {"ssdeR_laplace", (DL_FUNC)&ssdeR_laplace, 3},
     {"ssdeR_report", (DL_FUNC)&ssdeR_report, 2},
+    {"ssdeR_smooth", (DL_FUNC)&ssdeR_smooth, 3},
     {"ssdeR_hess", (DL_FUNC)&ssdeR_hess, 3},
     {"ssdeR_info", (DL_FUNC)&ssdeR_info, 1},
     {NULL, NULL, 0}};

@@ -23,6 +23,8 @@
  *                         caller can all-reduce it over RCCL before reading it
  *   ssde_report        <- REPORT(aest_all)      (src/nllk/nllk_ctcrw.hpp:249,
  *                                                nllk_ou_ssm.hpp:215, nllk_bm_ssm.hpp:177)
+ *   ssde_smooth        <- (new) fixed-interval Kalman smoother and whitened innovations of the state-space families: what
+ *                         the reference's SDE$residuals() stops at (R/sde.R:1186-1228) and aest_all does not give
  *   ssde_penalty       <- smoothing penalty     (nllk_ctcrw.hpp:254-280, nllk_sde.hpp:89-124)
  *   ssde_info          <- InfoADFunObject       (src/init.c:7)
  *   ssde_forget        <- (new) drops the memo of ssde_eval
@@ -75,7 +77,7 @@
 extern "C" {
 #endif
 
-#define SSDE_ABI_VERSION 11
+#define SSDE_ABI_VERSION 12
 
 /* model codes: DATA_STRING(type) of src/smoothSDE.cpp:12-27 */
 enum {
@@ -323,6 +325,16 @@ int ssde_penalty(ssde_handle *h, const double *par, int32_t n_par_full, double *
 /* One-step-ahead predicted states for every row: aest_all [n x sdim] column-major. */
 int ssde_report(ssde_handle *h, const double *par, int32_t n_par_full, double *aest_all);
 
+/* Fixed-interval smoother of the Kalman families at `par` (definitions: DESIGN.md §3.9).  Any output may be NULL, not all:
+ *   a_smooth [n x sdim]        column-major, the aest_all layout: E[state at row i | the whole track]
+ *   P_smooth [n x sdim x sdim] element (i, r, c) at i + n * (r + sdim * c): its covariance
+ *   resid    [n x n_dim]       whitened one-step-ahead innovations C_i^-1 v_i (C_i the lower Cholesky factor of F_i)
+ * NaN on rows that carry no state (a track's first row, one-row tracks) and, for resid, on rows without an update (those, NA
+ * rows, detF <= 0).  SSDE_ERR_MODEL for the direct families and ESEAL_SSM (as ssde_report).  Leaves the memo, the window
+ * state and every later ssde_eval result as they were; the per-row records live in a buffer of the call's own, capped by
+ * SSDE_OPT_SMOOTH_BUDGET_MB (tracks are processed in chunks of whole wavefront groups; the result does not depend on it). */
+int ssde_smooth(ssde_handle *h, const double *par, int32_t n_par_full, double *a_smooth, double *P_smooth, double *resid);
+
 /* Multiply the warm-up overlap of the time windows by `factor` for all later evaluations
  * (factor <= 0: force one sequential window). */
 int ssde_widen_windows(ssde_handle *h, int32_t factor);
@@ -414,8 +426,10 @@ int ssde_comm_init_rank(ssde_handle *h, int32_t n_ranks, int32_t rank, const voi
  *   SSDE_OPT_COMM_DEFER (default 0): 1 = ssde_eval_device leaves this rank's PARTIAL [nllk, grad..., check] in the caller's
  *       buffer and the caller sums it over the ranks itself (ssde_comm_allreduce) -- a host that evaluates several handles
  *       side by side packs their result vectors and issues one collective for all of them instead of one per handle on
- *       as many streams.  ssde_eval ignores it. */
-enum { SSDE_OPT_KERNEL_STAMPS = 1, SSDE_OPT_COMM_DEFER = 2 };
+ *       as many streams.  ssde_eval ignores it.
+ *   SSDE_OPT_SMOOTH_BUDGET_MB (default 0 = a quarter of the device memory free when ssde_smooth is called): the largest record
+ *       buffer ssde_smooth allocates, in MiB (one wavefront group always goes, whatever the cap). */
+enum { SSDE_OPT_KERNEL_STAMPS = 1, SSDE_OPT_COMM_DEFER = 2, SSDE_OPT_SMOOTH_BUDGET_MB = 3 };
 int ssde_set_option(ssde_handle *h, int32_t option, int64_t value);
 
 /* Sum buf_dev[0 .. count) (doubles, HBM) over the ranks of the communicator `h` joined, in place, on `stream` (enqueue only:

@@ -17,7 +17,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 MODEL_CODES = {"BM": 0, "OU": 1, "BM_SSM": 2, "OU_SSM": 3, "CTCRW": 4, "BM_t": 5, "ESEAL_SSM": 6, "CIR": 7}
 KALMAN_MODELS = ("BM_SSM", "OU_SSM", "CTCRW")
@@ -72,7 +72,7 @@ class SsdeSimDesc(C.Structure):
                 ("reserved", C.c_int32)]
 
 
-OPT_KERNEL_STAMPS, OPT_COMM_DEFER = 1, 2
+OPT_KERNEL_STAMPS, OPT_COMM_DEFER, OPT_SMOOTH_BUDGET_MB = 1, 2, 3
 # ssde_info_t.kernel_id (include/ssde.h: SSDE_KERNEL_*): the kernel family that ran the rows of the last evaluation
 KERNEL_NAMES = {0: "none", 1: "direct_kernel", 2: "direct_fast_kernel", 3: "iso_shared_kernel", 4: "iso_mask_kernel",
                 5: "iso_mask_kernel<uniform grid>", 6: "iso_quiet_kernel", 7: "iso_shared_kernel + general kernel (mixed batch)",
@@ -487,6 +487,8 @@ def load_library():
     lib.ssde_penalty.restype = C.c_int
     lib.ssde_report.argtypes = [C.c_void_p, _dp, C.c_int32, _dp]
     lib.ssde_report.restype = C.c_int
+    lib.ssde_smooth.argtypes = [C.c_void_p, _dp, C.c_int32, _dp, _dp, _dp]
+    lib.ssde_smooth.restype = C.c_int
     lib.ssde_widen_windows.argtypes = [C.c_void_p, C.c_int32]
     lib.ssde_widen_windows.restype = C.c_int
     lib.ssde_relax_windows.argtypes = [C.c_void_p]
@@ -541,7 +543,7 @@ WINDOW_TOL = 1e-11  # largest tolerated relative hand-over disagreement between 
 
 EXPORTED_SYMBOLS = ("ssde_create", "ssde_eval", "ssde_eval_device", "ssde_penalty", "ssde_report", "ssde_widen_windows", "ssde_relax_windows",
                     "ssde_info", "ssde_destroy", "ssde_last_error", "ssde_abi_version", "ssde_comm_unique_id", "ssde_comm_init_rank", "ssde_forget", "ssde_laplace_eval", "ssde_last_kernel_ms", "ssde_kernel_ms_history",
-                    "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read")
+                    "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_smooth")
 
 def lagstats_host(tracks):
     """The lag statistics ssde_create builds for a stationary batch, computed on the host: `tracks` is a list of
@@ -782,6 +784,21 @@ class Engine:
         self._check(self.lib.ssde_report(self._h, par.ctypes.data_as(_dp), self.n_par_full,
                                          out.ctypes.data_as(_dp)))
         return out
+
+    def smooth(self, par, cov: bool = True, resid: bool = True) -> dict:
+        """Fixed-interval smoother at `par` (ssde_smooth): {"mean": (n x sdim), "cov": (n x sdim x sdim) or None,
+        "resid": (n x d) whitened one-step-ahead innovations or None}.  NaN on rows without a state (a track's first row) and, for
+        "resid", on rows without an update (those, NA rows)."""
+        par = np.ascontiguousarray(par, dtype=np.float64)
+        if par.shape != (self.n_par_full,):
+            raise ValueError(f"par must have length {self.n_par_full}")
+        n, sd, d = self.problem.n, self.problem.sdim, self.problem.n_dim
+        mean = np.zeros((n, sd), order="F")
+        P = np.zeros((n, sd, sd), order="F") if cov else None
+        e = np.zeros((n, d), order="F") if resid else None
+        self._check(self.lib.ssde_smooth(self._h, par.ctypes.data_as(_dp), self.n_par_full, mean.ctypes.data_as(_dp),
+                                         P.ctypes.data_as(_dp) if cov else None, e.ctypes.data_as(_dp) if resid else None))
+        return {"mean": mean, "cov": P, "resid": e}
 
     def close(self):
         if self._h:

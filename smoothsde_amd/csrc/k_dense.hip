@@ -9,14 +9,17 @@
 // the GPU); the throughput path for the headline configurations is k_iso.hip.
 #include "ssde_dense.hpp"
 #include "ssde_device.hpp"
+#include "ssde_smooth.hpp"
 
 namespace ssde {
 
-template <int MODEL, int D, int N, bool REPORT>
+// MODE 0: evaluation, 1: REPORT(aest_all), 2: the smoother's forward records (ssde_smooth.hpp; N = 0)
+template <int MODEL, int D, int N, int MODE>
 __global__ __launch_bounds__(WAVE) void dense_kernel(const DenseArgs A) {
     typedef DenseDims<MODEL, D> DM;
     constexpr int SD = DM::SD, Q = DM::Q;
-    const int g = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
+    constexpr bool REPORT = MODE == 1;
+    const int g = blockIdx.x + (MODE == 2 ? A.g0 : 0), b = blockIdx.y, lane = threadIdx.x;
     const TileView& tv = A.tv;
     const SlotTable* __restrict__ T = A.slots;
     const int C = tv.C;
@@ -86,13 +89,18 @@ __global__ __launch_bounds__(WAVE) void dense_kernel(const DenseArgs A) {
                 for (int s = 0; s < N; s++) par[jj].d[s] += (j == jj && dkind[s] == 2 && dslot[s] == k) ? w : 0.0;
             }
         }
+        if constexpr (MODE == 2) {
+            // records of the group at srec_off[g] (chunk-relative), double k of step s at (s * R + k) * 64 + lane
+            double* rp = A.srec + (A.srec_off[g] - A.srec_base) + (int64_t)s0 * SmoothRec<MODEL, D>::R * WAVE + lane;
+            smooth_record_row<MODEL, D>(S, par, H, dt, y, is_na(y[0], A.any_nan), [&](int k) -> double& { return rp[(int64_t)k * WAVE]; });
+        }
         dense_step<MODEL, D, N>(S, par, H, dt, y, is_na(y[0], A.any_nan));
         if (REPORT) {
 #pragma unroll
             for (int c = 0; c < SD; c++) A.report[row0 + 1 + s0 + (int64_t)c * A.n] = S.a[c].v;
         }
     }
-    if (REPORT) return;
+    if (MODE != 0) return;
     double t = wave_sum(S.nll.v);
     if (lane == 0) A.partials[((int64_t)b * (1 + N) + 0) * tv.n_groups + g] = t;
 #pragma unroll
@@ -106,12 +114,14 @@ hipError_t launch_dense_wide(const DenseArgs& a, bool want_grad, hipStream_t s);
 
 #define SSDE_L(MODEL, D)                                                                          \
     if (a.model == MODEL && a.d == D) {                                                           \
-        if (a.report)                                                                             \
-            hipLaunchKernelGGL((dense_kernel<MODEL, D, 0, true>), dim3(a.tv.n_groups, 1), block, 0, s, a); \
+        if (a.srec)                                                                               \
+            hipLaunchKernelGGL((dense_kernel<MODEL, D, 0, 2>), dim3(a.srec_groups, 1), block, 0, s, a); \
+        else if (a.report)                                                                        \
+            hipLaunchKernelGGL((dense_kernel<MODEL, D, 0, 1>), dim3(a.tv.n_groups, 1), block, 0, s, a); \
         else if (!want_grad)                                                                      \
-            hipLaunchKernelGGL((dense_kernel<MODEL, D, 0, false>), dim3(a.tv.n_groups, 1), block, 0, s, a); \
+            hipLaunchKernelGGL((dense_kernel<MODEL, D, 0, 0>), dim3(a.tv.n_groups, 1), block, 0, s, a); \
         else                                                                                      \
-            hipLaunchKernelGGL((dense_kernel<MODEL, D, DENSE_NT, false>), dim3(a.tv.n_groups, a.n_dirblocks), block, 0, s, a); \
+            hipLaunchKernelGGL((dense_kernel<MODEL, D, DENSE_NT, 0>), dim3(a.tv.n_groups, a.n_dirblocks), block, 0, s, a); \
         return hipGetLastError();                                                                 \
     }
 #ifndef SSDE_DENSE_WIDE_TU

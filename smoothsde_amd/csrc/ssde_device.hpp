@@ -493,6 +493,11 @@ struct DenseArgs {
     int64_t n;
     double last_dt;              // dtimes(n-1), see IngestArgs
     PpDrift pp;                  // pp.nb > 0: the tiles hold covariates, the slots' columns come out of the blocks' tables (REPORT of such a handle)
+    // the smoother's forward records (ssde_smooth, k_smooth.hip): srec != NULL runs groups [g0, g0 + srec_groups) in record mode
+    double* srec;                // group g's records at srec + srec_off[g] - srec_base
+    const int64_t* srec_off;     // [n_groups] in doubles, over all groups
+    int64_t srec_base;           // srec_off[g0]
+    int g0, srec_groups;
 };
 hipError_t launch_dense(const DenseArgs& a, bool want_grad, hipStream_t s);
 
@@ -555,6 +560,27 @@ struct TvArgs {
     double* chk_items;           // pinned, [n_items]: each item's hand-over check (NULL: atomicMax into out[n_out])
 };
 hipError_t launch_tv_weights(const TvArgs& a, hipStream_t s);
+
+// ---- fixed-interval smoother (k_smooth.hip, ssde_smooth.hpp) ----------------------------------------
+// Records of SmoothRec<MODEL, D>::R doubles per state row, one group (64 lanes = tracks) after another; double k of step s of a lane at
+// rec + (rec_off[g] - rec_base) + (s * R + k) * 64 + lane.  Outputs in the long (possibly lattice-padded) layout of n_out rows.
+struct SmoothArgs {
+    int model, d;
+    double* rec;
+    const int64_t* rec_off;      // [n_groups]
+    int64_t rec_base;
+    int g0, n_groups;            // this chunk's groups
+    const int64_t* lane_row0;    // [groups * 64]: the lane's track's first row (its state rows follow)
+    const int32_t* lane_ns;      // [groups * 64]: state rows of the lane's track (rows - 1)
+    int64_t n_lanes;
+    double* am;                  // [n_out x sdim] or NULL
+    double* Vm;                  // [n_out x sdim x sdim] or NULL
+    double* em;                  // [n_out x d] or NULL
+    int64_t n_out;
+};
+int smooth_rec_doubles(int model, int d);
+hipError_t launch_smooth_back(const SmoothArgs& a, hipStream_t s);
+hipError_t launch_smooth_tv_record(const TvArgs& t, const SmoothArgs& a, hipStream_t s);   // PATH_TV: lane = track, long-format rows
 hipError_t launch_tv_a0(const TvArgs& a, const double* a0_src, const int64_t* trk_seg, int64_t n_seg, int sdim,
                         double* a0_dst, hipStream_t s);
 hipError_t launch_tv_prepare(const TvArgs& a, hipStream_t s);

@@ -51,7 +51,7 @@ void release_device(ssde_handle* h) {
                 h->trace_us[0] / h->trace_n, h->trace_us[1] / h->trace_n, h->trace_us[2] / h->trace_n, h->trace_us[3] / h->trace_n,
                 h->trace_us[4] / h->trace_n);
     destroy_dist(h);
-    h->bnd.release(); h->chk.release(); h->group_flags.release(); h->gain_ring.release(); h->pad_pos.release(); h->dirty_groups.release(); h->lap_out.release(); h->nan_bits.release(); h->quiet_flag.release();
+    h->bnd.release(); h->chk.release(); h->group_flags.release(); h->gain_ring.release(); h->pad_pos.release(); h->pad_row.release(); h->dirty_groups.release(); h->lap_out.release(); h->nan_bits.release(); h->quiet_flag.release();
     h->lag_M.release(); h->lag_s.release(); h->lag_glen.release(); h->lag_ns.release(); h->lag_flag.release();
     if (h->gain_pinned) (void)hipHostFree(h->gain_pinned);
     for (int i = 0; i < 2; i++) { if (h->aux[i]) (void)hipStreamDestroy(h->aux[i]); if (h->ev_join[i]) (void)hipEventDestroy(h->ev_join[i]); }
@@ -791,6 +791,12 @@ int ssde_set_option(ssde_handle* h, int32_t option, int64_t value) {
     if (option == SSDE_OPT_KERNEL_STAMPS) {
         h->stamps = value != 0;
         for (ssde_handle* s : h->shards) s->stamps = h->stamps;
+        return SSDE_OK;
+    }
+    if (option == SSDE_OPT_SMOOTH_BUDGET_MB) {
+        if (value < 0) { h->err = "SSDE_OPT_SMOOTH_BUDGET_MB: a size in MiB, 0 for the default"; return SSDE_ERR_ARG; }
+        h->smooth_budget_mb = value;
+        for (ssde_handle* s : h->shards) s->smooth_budget_mb = value;
         return SSDE_OK;
     }
     if (option == SSDE_OPT_COMM_DEFER) {

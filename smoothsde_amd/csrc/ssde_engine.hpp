@@ -281,6 +281,7 @@ struct ssde_handle {
     // reported state is caller row i's (ssde_report)
     int64_t n_pad = 0;
     DevBuf<int64_t> pad_pos;
+    DevBuf<int64_t> pad_row;       // the lattice row of caller row i itself (ssde_smooth: the state AT the row, not predicted past it)
     double pad_step = 0.0;
     double snap_dt = 0.0;          // > 0: a grid that is regular to SSDE_GRID_RTOL (last-bit jitter of decimal steps): this step is hoisted
 
@@ -299,6 +300,7 @@ struct ssde_handle {
     bool shards_share_device = false;         // rehearsal on a one-GPU machine: shards summed by a kernel, not RCCL
     int comm_ranks = 1;                       // ranks of a multi-process communicator (the caller's argument)
     int comm_ranks_reported = 0;              // ... what ncclCommCount says about it (0: no communicator)
+    int64_t smooth_budget_mb = 0;             // SSDE_OPT_SMOOTH_BUDGET_MB: cap on ssde_smooth's record buffer (0: a quarter of the free memory)
     bool comm_defer = false;                  // SSDE_OPT_COMM_DEFER: ssde_eval_device leaves the rank's partial result to the caller's own collective
     // the bulk of a stationary batch from lag statistics (ssde_lagstats.hpp): built at create when the rule engages it
     bool lag_ready = false;
@@ -366,6 +368,7 @@ int reduce_shards(ssde_handle* parent);
 // all-reduce one handle's out buffer over its multi-process communicator -- enqueue only
 int reduce_ranks(ssde_handle* h, double* buf, hipStream_t s);
 int report_sharded(ssde_handle* parent, const double* par, double* aest_all);
+int smooth_sharded(ssde_handle* parent, const double* par, double* a_smooth, double* P_smooth, double* resid);
 void destroy_dist(ssde_handle* h);
 hipError_t launch_sum_into(double* dst, const double* src, int n, hipStream_t s);   // k_reduce.hip
 

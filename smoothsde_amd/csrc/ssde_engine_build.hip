@@ -119,6 +119,7 @@ int lattice_pad(const ssde_desc* d, ssde_handle* h, const std::vector<int64_t>& 
     // REPORT(aest_all): row i of the reference holds the state AFTER row i's step, i.e. predicted to the time of row i + 1
     // (nllk_ctcrw.hpp:246) -- on the lattice that is the row just before row i + 1's (lattice_maps_kernel)
     h->pad_pos.p = rep.p; h->pad_pos.n = rep.n; rep.p = nullptr; rep.n = 0;
+    h->pad_row.p = pos.p; h->pad_row.n = pos.n; pos.p = nullptr; pos.n = 0;
     h->n_pad = np; h->pad_step = delta;
     cleanup();
 #undef LP_CHK

@@ -1,0 +1,198 @@
+// ssde_engine_smooth.hip -- ssde_smooth: the fixed-interval smoother of the Kalman families.
+//
+// A forward pass in record mode (dense_kernel MODE 2 on the tiled routes, smooth_tv_record_kernel on PATH_TV) writes every state
+// row's record, smooth_back_kernel walks them back and writes the smoothed mean, covariance and whitened innovation in the long
+// format.  Groups of 64 tracks are independent, so the records are produced and consumed chunk by chunk (SSDE_OPT_SMOOTH_BUDGET_MB)
+// and the result does not depend on the chunking.  Every buffer is the call's own: the handle's record / stats buffers, memo and
+// window state are not touched.
+#include <cmath>
+#include <cstring>
+#include <functional>
+#include <limits>
+
+#include "ssde_engine.hpp"
+
+using namespace ssde_engine;
+
+namespace {
+
+struct SmoothBufs {
+    std::vector<DevBuf<double>*> d;
+    std::vector<DevBuf<int64_t>*> i;
+    ~SmoothBufs() { for (auto* b : d) b->release(); for (auto* b : i) b->release(); }
+};
+
+// chunk the groups [0, G) so that each chunk's records fit `budget` doubles (at least one group per chunk)
+std::vector<int> chunk_groups(const std::vector<int64_t>& goff, int64_t budget) {
+    const int G = (int)goff.size() - 1;
+    std::vector<int> cut(1, 0);
+    int g0 = 0;
+    for (int g = 0; g < G; g++)
+        if (g > g0 && goff[g + 1] - goff[g0] > budget) { cut.push_back(g); g0 = g; }
+    cut.push_back(G);
+    return cut;
+}
+
+int smooth_single(ssde_handle* h, const double* par, double* a_smooth, double* P_smooth, double* resid) {
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(0));
+    const int sd = h->sdim, d = h->d;
+    const int R = smooth_rec_doubles(h->model, d);
+    if (R <= 0) { h->err = "ssde_smooth: no smoother for this response width"; return SSDE_ERR_MODEL; }
+    const bool tv = h->path == PATH_TV;
+    const int64_t nt = (!tv && h->n_pad > 0) ? h->n_pad : h->n;        // rows of the layout the kernels write
+    DevBuf<double> am, Vm, em, rec, pbuf;
+    DevBuf<int64_t> offb;
+    SmoothBufs guard{{&am, &Vm, &em, &rec, &pbuf}, {&offb}};
+    // the outputs, NaN (all bits set) where no state row writes
+    if (a_smooth) { HIPCHK(h, am.alloc((size_t)nt * sd)); HIPCHK(h, hipMemset(am.p, 0xff, (size_t)nt * sd * 8)); }
+    if (P_smooth) { HIPCHK(h, Vm.alloc((size_t)nt * sd * sd)); HIPCHK(h, hipMemset(Vm.p, 0xff, (size_t)nt * sd * sd * 8)); }
+    if (resid) { HIPCHK(h, em.alloc((size_t)nt * d)); HIPCHK(h, hipMemset(em.p, 0xff, (size_t)nt * d * 8)); }
+    HIPCHK(h, pbuf.upload(std::vector<double>(par, par + h->L.n_full)));
+
+    // the groups' record offsets (doubles; 64-bit throughout)
+    std::vector<int32_t> glen;
+    int64_t n_lanes = 0;
+    if (tv) {
+        std::vector<int32_t> ns((size_t)h->n_seg);
+        if (h->n_seg) HIPCHK(h, hipMemcpy(ns.data(), h->tv_ns.p, (size_t)h->n_seg * 4, hipMemcpyDeviceToHost));
+        n_lanes = h->n_seg;
+        for (int64_t t = 0; t < h->n_seg; t += WAVE) {
+            int32_t m = 0;
+            for (int64_t k = t; k < std::min<int64_t>(t + WAVE, h->n_seg); k++) m = std::max(m, ns[k]);
+            glen.push_back(m);
+        }
+    } else {
+        glen.resize((size_t)h->n_groups);
+        if (h->n_groups) HIPCHK(h, hipMemcpy(glen.data(), h->group_len.p, (size_t)h->n_groups * 4, hipMemcpyDeviceToHost));
+        n_lanes = (int64_t)h->n_groups * WAVE;
+    }
+    const int G = (int)glen.size();
+    std::vector<int64_t> goff((size_t)G + 1, 0);
+    for (int g = 0; g < G; g++) goff[g + 1] = goff[g] + (int64_t)glen[g] * R * WAVE;
+    HIPCHK(h, offb.upload(goff));
+    int64_t budget;
+    if (h->smooth_budget_mb > 0) budget = h->smooth_budget_mb * (int64_t)(1 << 20) / 8;
+    else {
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
+        budget = (int64_t)(free_b / 4 / 8);
+    }
+    const std::vector<int> cut = chunk_groups(goff, budget);
+    int64_t biggest = 0;
+    for (size_t c = 0; c + 1 < cut.size(); c++) biggest = std::max(biggest, goff[cut[c + 1]] - goff[cut[c]]);
+    HIPCHK(h, rec.alloc((size_t)std::max<int64_t>(biggest, 1)));
+
+    SmoothArgs s;
+    memset(&s, 0, sizeof(s));
+    s.model = h->model; s.d = d; s.rec = rec.p; s.rec_off = offb.p;
+    s.am = am.p; s.Vm = Vm.p; s.em = em.p; s.n_out = nt; s.n_lanes = n_lanes;
+    TvArgs ta;
+    DenseArgs da;
+    SlotTable stab;
+    DevBuf<SlotTable> stb;
+    if (tv) {
+        tv_base_args(h, ta);
+        ta.par = pbuf.p;
+        const double sig = exp(par[0]);
+        ta.h = sig * sig;
+        s.lane_row0 = h->tv_row0.p; s.lane_ns = h->tv_ns.p;
+    } else {
+        memset(&stab, 0, sizeof(stab));
+        stab.n_slots = (int)h->slots.size(); stab.q = h->q;
+        for (size_t k = 0; k < h->slots.size(); k++) {
+            stab.par_j[k] = (int16_t)h->slots[k].par_j; stab.col[k] = (int16_t)h->slots[k].col;
+            stab.pidx[k] = (int16_t)h->slots[k].pidx; stab.is_free[k] = 0;
+        }
+        HIPCHK(h, stb.upload(std::vector<SlotTable>(1, stab)));
+        memset(&da, 0, sizeof(da));
+        da.tv.tiles = h->tiles.p; da.tv.group_off = h->group_off.p; da.tv.group_len = h->group_len.p;
+        da.tv.lane_nsteps = h->lane_nsteps.p; da.tv.a0 = h->a0.p; da.tv.n_groups = h->n_groups; da.tv.C = h->C; da.tv.c_obs = h->c_obs;
+        da.tv.dt_all = h->dt_all;
+        da.model = h->model; da.d = d; da.any_nan = h->na_any; da.has_h = h->has_h ? 1 : 0;
+        da.slots = stb.p; da.par = pbuf.p; da.n_slots = stab.n_slots;
+        for (int i = 0; i < 256; i++) da.p0[i] = h->p0_full[i];
+        da.n_dirblocks = 1; da.pp = h->pp_drift;
+        da.lane_row0 = h->lane_row0.p; da.n = nt; da.last_dt = h->last_dt;
+        da.srec = rec.p; da.srec_off = offb.p;
+        s.lane_row0 = h->lane_row0.p; s.lane_ns = h->lane_nsteps.p;
+    }
+    for (size_t c = 0; c + 1 < cut.size(); c++) {
+        const int g0 = cut[c], ng = cut[c + 1] - cut[c];
+        s.g0 = g0; s.n_groups = ng; s.rec_base = goff[g0];
+        if (tv) {
+            HIPCHK(h, launch_smooth_tv_record(ta, s, 0));
+        } else {
+            da.g0 = g0; da.srec_groups = ng; da.srec_base = goff[g0];
+            HIPCHK(h, launch_dense(da, false, 0));
+        }
+        HIPCHK(h, launch_smooth_back(s, 0));
+    }
+    // back to the caller's rows (a lattice-padded handle: the lattice row OF each caller row), then to the host
+    auto fetch = [&](DevBuf<double>& src, int ncol, double* dst) -> int {
+        if (!dst) return SSDE_OK;
+        if (nt != h->n) {
+            DevBuf<double> rows;
+            SmoothBufs g2{{&rows}, {}};
+            HIPCHK(h, rows.alloc((size_t)h->n * ncol));
+            HIPCHK(h, launch_lattice_gather(h->pad_row.p, src.p, h->n, nt, ncol, rows.p, 0));
+            HIPCHK(h, hipMemcpy(dst, rows.p, (size_t)h->n * ncol * 8, hipMemcpyDeviceToHost));
+        } else {
+            HIPCHK(h, hipMemcpy(dst, src.p, (size_t)h->n * ncol * 8, hipMemcpyDeviceToHost));
+        }
+        return SSDE_OK;
+    };
+    int st = fetch(am, sd, a_smooth);
+    if (!st) st = fetch(Vm, sd * sd, P_smooth);
+    if (!st) st = fetch(em, d, resid);
+    if (!st) HIPCHK(h, hipStreamSynchronize(0));
+    stb.release();
+    return st;
+}
+
+}  // namespace
+
+namespace ssde_engine {
+
+int smooth_sharded(ssde_handle* parent, const double* par, double* a_smooth, double* P_smooth, double* resid) {
+    const int64_t n = parent->n;
+    const int SD = parent->sdim, D = parent->d, per = parent->model == SSDE_MODEL_CTCRW ? 2 : 1;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    if (a_smooth) std::fill(a_smooth, a_smooth + (size_t)n * SD, nan);
+    if (P_smooth) std::fill(P_smooth, P_smooth + (size_t)n * SD * SD, 0.0);      // cross-pair blocks: zero
+    if (resid) std::fill(resid, resid + (size_t)n * D, nan);
+    for (size_t k = 0; k < parent->shards.size(); k++) {
+        ssde_handle* sh = parent->shards[k];
+        const int64_t lo = parent->shard_row0[k], m = parent->shard_nrows[k];
+        const int sd = sh->sdim, d = sh->d, c0 = parent->shard_col0[k], r0 = c0 / per;
+        std::vector<double> ta(a_smooth ? (size_t)m * sd : 0), tP(P_smooth ? (size_t)m * sd * sd : 0), te(resid ? (size_t)m * d : 0);
+        int st = ssde_smooth(sh, par, parent->L.n_full, a_smooth ? ta.data() : nullptr, P_smooth ? tP.data() : nullptr,
+                             resid ? te.data() : nullptr);
+        if (st) { parent->err = sh->err; return st; }
+        for (int c = 0; c < sd && a_smooth; c++) memcpy(a_smooth + (size_t)(c0 + c) * n + lo, ta.data() + (size_t)c * m, (size_t)m * 8);
+        for (int c = 0; c < d && resid; c++) memcpy(resid + (size_t)(r0 + c) * n + lo, te.data() + (size_t)c * m, (size_t)m * 8);
+        if (P_smooth) {
+            for (int c = 0; c < sd; c++)
+                for (int r = 0; r < sd; r++)
+                    memcpy(P_smooth + (size_t)n * ((c0 + r) + (size_t)SD * (c0 + c)) + lo, tP.data() + (size_t)m * (r + (size_t)sd * c), (size_t)m * 8);
+            for (int64_t i = 0; i < m; i++)                             // a row without a state has no covariance at all
+                if (std::isnan(tP[i]))
+                    for (int q = 0; q < SD * SD; q++) P_smooth[(size_t)n * q + lo + i] = nan;
+        }
+    }
+    return SSDE_OK;
+}
+
+}  // namespace ssde_engine
+
+extern "C" {
+
+int ssde_smooth(ssde_handle* h, const double* par, int32_t n_par_full, double* a_smooth, double* P_smooth, double* resid) {
+    if (!h || !par || (!a_smooth && !P_smooth && !resid)) { if (h) h->err = "ssde_smooth: no parameter vector, or no output asked for"; return SSDE_ERR_ARG; }
+    if (n_par_full != h->L.n_full) { h->err = "parameter vector has the wrong length"; return SSDE_ERR_ARG; }
+    if (!is_kalman(h->model)) { h->err = "the smoother serves the Kalman families only (the direct families have no state; ESEAL_SSM no REPORT)"; return SSDE_ERR_MODEL; }
+    if (!h->shards.empty()) return smooth_sharded(h, par, a_smooth, P_smooth, resid);
+    return smooth_single(h, par, a_smooth, P_smooth, resid);
+}
+
+}  // extern "C"

@@ -466,6 +466,64 @@ class SDE:
         n_lambda = 0 if not getattr(self, "laplace_", False) else self.problem_.n_smooth
         return 2.0 * self.out_["value"] + 2.0 * (len(self.out_["par"]) - n_lambda)   # R/sde.R:1340-1349
 
+    # -- state estimates and model checking (R/sde.R:1186-1228) -------------------------------------------------
+    def _current_par_full(self):
+        if self.engine_ is None:
+            raise RuntimeError("call setup() or fit() first")
+        full = getattr(self, "par_full_", None)
+        return self._par_full(self.problem_) if full is None else full
+
+    def smooth_states(self, cov=True):
+        """Smoothed states of a state-space model (CTCRW, OU_SSM, BM_SSM) at the current parameters: E[state at row i | the whole
+        track] and, with cov=True, its covariance (ssde_smooth).  Columns in the order of the reference's aest_all
+        (CTCRW: x, vx, y, vy, ...).  Returns {"mean": n x sdim, "cov": n x sdim x sdim or None}; NaN on a track's first row, which
+        carries no state (the prior is the state at the second row)."""
+        if self.type_ not in ("CTCRW", "OU_SSM", "BM_SSM"):
+            raise NotImplementedError(f"smooth_states: no latent state in the model {self.type_!r}")
+        out = self.engine_.smooth(self._current_par_full(), cov=cov, resid=False)
+        return {"mean": out["mean"], "cov": out["cov"]}
+
+    def residuals(self):
+        """Model residuals, iid N(0, 1) under the model (one column per response variable).
+
+        BM / BM_t / OU: the reference's SDE$residuals() (R/sde.R:1186-1228) on the host: row i holds the standardised transition
+        i -> i + 1 (for BM_t scaled by sqrt(df / (df - 2)), the t scale), and the LAST row of every track is NaN.
+        CTCRW / OU_SSM / BM_SSM (where the reference stops): the whitened one-step-ahead innovations C_i^-1 (y_i - Z a_i) of the
+        Kalman filter, C_i the lower Cholesky factor of the innovation covariance (ssde_smooth); row i is row i's own innovation,
+        so the FIRST row of every track is NaN (it carries no state), as is every row without an update (NA rows).
+        CIR / ESEAL_SSM raise NotImplementedError, as the reference stops."""
+        if self.type_ in ("CTCRW", "OU_SSM", "BM_SSM"):
+            if self.engine_ is None:
+                raise RuntimeError("call setup() or fit() first")
+            return self.engine_.smooth(self._current_par_full(), cov=False, resid=True)["resid"]
+        if self.type_ not in ("BM", "BM_t", "OU"):
+            raise NotImplementedError(f"Residuals not implemented for model {self.type_}")
+        ids = np.asarray(self.data_["ID"])
+        n = len(ids)
+        brk = np.nonzero(ids[1:] != ids[:-1])[0]
+        start = np.r_[0, brk + 1]
+        end = np.r_[brk, n - 1]
+        keep_from = np.setdiff1d(np.arange(n), end)                  # -end_ind
+        keep_to = np.setdiff1d(np.arange(n), start)                  # -start_ind
+        t = np.asarray(self.data_["time"], dtype=np.float64)
+        dt = t[keep_to] - t[keep_from]
+        par = self.par()
+        Z = self.obs()
+        mu = np.column_stack([par[k] for k in self.names_ if k.startswith("mu")])[keep_from]
+        if self.type_ in ("BM", "BM_t"):
+            mean = Z[keep_from] + mu * dt[:, None]
+            sd = (par["sigma"][keep_from] * np.sqrt(dt))[:, None]
+            if self.type_ == "BM_t":
+                df = self.other_data_["df"]
+                sd = sd / np.sqrt(df / (df - 2))                      # the t scale, not the sd
+        else:
+            tau, kappa = par["tau"][keep_from][:, None], par["kappa"][keep_from][:, None]
+            mean = mu + np.exp(-dt[:, None] / tau) * (Z[keep_from] - mu)
+            sd = np.sqrt(kappa * (1 - np.exp(-2 * dt[:, None] / tau)))
+        res = np.full((n, Z.shape[1]), np.nan)
+        res[keep_from] = (Z[keep_to] - mean) / sd
+        return res
+
     def par(self, t=None):
         """SDE parameters on the natural scale for every row (R/sde.R:749-856, new_data = NULL)."""
         out = {}
