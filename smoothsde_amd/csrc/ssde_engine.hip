@@ -27,11 +27,11 @@ namespace ssde_engine {
 
 // everything the handle holds on the device and in pinned memory (the handle itself stays)
 void release_device(ssde_handle* h) {
-    if (!h->wave_clock_file.empty() && h->wave_clock.p && h->wave_clock_items > 0) {
+    if (h->knobs.wave_clock && h->wave_clock.p && h->wave_clock_items > 0) {
         std::vector<double> w((size_t)4 * h->wave_clock_items);
         if (hipSetDevice(h->device) == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
             hipMemcpy(w.data(), h->wave_clock.p, w.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
-            if (FILE* f = fopen(h->wave_clock_file.c_str(), "w")) {
+            if (FILE* f = fopen(h->knobs.wave_clock->c_str(), "w")) {
                 fprintf(f, "# work item, start, end (100 MHz ticks), HW_ID, rows; windows %d, warm-up %d, t0 %d, t0_delta %d, groups %d, longest group %d\n", h->last_chunks, h->last_window, h->last_t0, h->last_t0_delta, h->n_groups, h->glen_max);
                 for (int i = 0; i < h->wave_clock_items; i++)
                     if (h->drift == 3) fprintf(f, "%d %.1f %.1f %.1f %.1f\n", i, w[4 * (size_t)i], w[4 * (size_t)i + 1], w[4 * (size_t)i + 2], w[4 * (size_t)i + 3]);
@@ -45,7 +45,7 @@ void release_device(ssde_handle* h) {
     h->cv_ranges.release(); h->cv_parts.release(); h->adj_ckpt.release(); h->fuse_words.release();
     if (h->cv_ranges_pinned) { (void)hipHostFree(h->cv_ranges_pinned); h->cv_ranges_pinned = nullptr; }
     h->hs_partials.release(); h->hs_hess.release(); h->hs_i16.release();
-    if (h->trace && h->trace_n > 0)
+    if (h->knobs.trace && h->trace_n > 0)
         fprintf(stderr, "[ssde trace] %lld isotropic evaluations, host us per evaluation: plan %.1f | gain table %.1f | main launch %.1f | "
                         "finalize launch %.1f | read-back (blocks until the GPU is done) %.1f\n", (long long)h->trace_n,
                 h->trace_us[0] / h->trace_n, h->trace_us[1] / h->trace_n, h->trace_us[2] / h->trace_n, h->trace_us[3] / h->trace_n,
@@ -76,7 +76,6 @@ void release_device(ssde_handle* h) {
     h->slot_table.release(); h->dirs.release(); h->par_ring.release();
     h->partials.release(); h->out.release();
     if (h->par_pinned) (void)hipHostFree(h->par_pinned);
-    if (h->out_pinned) (void)hipHostFree(h->out_pinned);
     if (h->pub_pinned) (void)hipHostFree(h->pub_pinned);
     h->pub_count.release();
     if (h->par_ev_ok)
@@ -135,7 +134,7 @@ int eval_device(ssde_handle* h, const double* par, int order, double* out_dev, h
     ra.n_out = 1 + L.n_full;
     ra.out = out_dev;
     for (int k = 0; k < MAX_PAR + 16; k++) ra.map[k] = -1;
-    if (h->pub_request && h->pub_ok && out_dev == h->out.p) {
+    if (h->pub_request && h->knobs.publish && out_dev == h->out.p) {
         // a synchronous evaluation: the reducing launch publishes the result itself (ssde_device.hpp: ReduceArgs.pub)
         ra.pub = h->pub_pinned; ra.pub_flag = h->pub_flag; ra.pub_seq = ++h->pub_seq; ra.pub_count = h->pub_count.p;
         h->pub_armed = true;
@@ -402,12 +401,8 @@ int run_once(ssde_handle* h, const double* par, int order, double* o) {
         }
         return SSDE_OK;
     }
-    // Stream discipline of the synchronous call: the NULL stream and a blocking 48-byte read-back.  The alternative --
-    // the handle's own non-blocking stream, an asynchronous copy into pinned memory and one stream synchronisation --
-    // saves 7.5 us in isolation (tools/microbench_graph.hip: 24 against 31.5 us of fixed overhead for copy + two
-    // launches + read-back; a hipGraph of the same four operations measures the same 24 us) but NOT inside the engine:
-    // same-session A/B (SSDE_SYNC_OWN_STREAM=1, tools/bench_c2.py) C2 0.0875 against 0.0872 ms; headline 0.315 against
-    // 0.3035 ms in one session, 0.3025 against 0.3029 ms in another.  No gain to be had: the null stream stays.
+    // Stream discipline of the synchronous call: the NULL stream and a blocking 48-byte read-back.  (An own non-blocking stream
+    // with an asynchronous copy into pinned memory wins 7.5 us in isolation and nothing inside the engine: DESIGN.md 3.3.)
     HIPCHK(h, hipSetDevice(h->device));
     if (h->async_pending) {              // an ssde_eval_device still running on the caller's stream shares the work buffers
         HIPCHK(h, hipStreamWaitEvent(0, h->ev_async, 0));
@@ -441,22 +436,11 @@ int run_once(ssde_handle* h, const double* par, int order, double* o) {
         h->ph_host_total_ms = ph_ms(ph_t0); h->ph_valid = ph; h->ph_has_comm = true;
         return SSDE_OK;
     }
-    if (h->path == PATH_TV && !h->env_no_graph && h->tv_stats_valid) {
+    if (h->path == PATH_TV && !h->knobs.no_graph && h->tv_stats_valid) {
         HIPCHK(h, hipSetDevice(h->device));
         h->n_evals++;
         next_stamp_pair(h);                                    // (a replayed graph carries no stamps: the slot stays invalid)
         return eval_tv_graph(h, par, order, o);
-    }
-    if (h->env_own_stream) {             // A/B (see above): own non-blocking stream, asynchronous read-back into pinned memory
-        if (!h->own_stream) HIPCHK(h, hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
-        h->sync_call = true;
-        int st1 = eval_device(h, par, order, h->out.p, h->own_stream);
-        h->sync_call = false;
-        if (st1) return st1;
-        HIPCHK(h, hipMemcpyAsync(h->out_pinned, h->out.p, nout * 8, hipMemcpyDeviceToHost, h->own_stream));
-        HIPCHK(h, hipStreamSynchronize(h->own_stream));
-        memcpy(o, h->out_pinned, nout * 8);
-        return SSDE_OK;
     }
     HIPCHK(h, ph_mark(0));
     h->sync_call = true;
@@ -496,7 +480,7 @@ int run_once(ssde_handle* h, const double* par, int order, double* o) {
     } else {
         HIPCHK(h, hipMemcpy(o, h->out.p, nout * 8, hipMemcpyDeviceToHost));
     }
-    if (h->trace) h->trace_us[4] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    if (h->knobs.trace) h->trace_us[4] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
     return SSDE_OK;
 }
 

@@ -17,6 +17,7 @@
 #include "../../include/ssde.h"
 #include "ssde_device.hpp"
 #include "ssde_host.hpp"
+#include "ssde_knobs.hpp"
 #include "ssde_lagstats.hpp"
 #include "ssde_tv.hpp"
 
@@ -135,7 +136,6 @@ struct ssde_handle {
     DevBuf<double> quiet_flag;
     int nan_words = 0;
     bool quiet_ok = false;
-    int env_quiet_window = 0;      // SSDE_QUIET_WINDOW (testing)
     double quiet_share = 0.0;      // share of the dirty groups' blocks that qualify (nominal 128-row memory)
     int last_quiet_window = 0;     // rows of memory the last launch used (0: no quiet rows)
     bool gain_stationary = false;  // the last gain recursion reached its stationary row
@@ -146,11 +146,7 @@ struct ssde_handle {
     int last_chunks = 1, last_window = 0;
     double last_check = 0.0;
     int n_retries = 0;
-    // testing / tuning knobs, read once at create: nothing calls getenv per evaluation
-    int env_window = 0, env_tv_waves = 0, env_tv_minlen = 0;
-    bool env_no_derive = false, env_no_graph = false, env_no_exact_hess = false;   // (SSDE_NO_EXACT_HESS: difference the gradient even where ssde_hess is exact)
-    double env_t0_cost = 3.0;
-    double env_w0_ratio = 1.2;     // (measured: 0 .. 1.45 swept, 3 % on CTCRW at 1.2, nothing on the scalar models) cost of a row of window 0 (every direction) over a row of a later window (one derived)
+    ssde_engine::Knobs knobs;      // testing / tuning knobs, read once, by build(): nothing reads the environment per evaluation
     // recovery from a widened plan (ssde_eval): after `cooldown` evaluations accepted at the first try the boost is
     // halved (or a given-up window plan restored) on probation; a failure on probation restores the level that worked
     // and doubles the cooldown
@@ -174,8 +170,7 @@ struct ssde_handle {
     bool cv_single = false;        // ... with constant tau / nu: one wave per (group, window) runs filter and tangents (iso_full_kernel)
     bool cv_few = false;           // few design columns, H = sigma_obs^2 I: one wave per (group, window) too (iso_few_kernel)
     DevBuf<unsigned> fuse_words;   // the fused finalising work of iso_shared_kernel: [0] finished work items, [2..3] the check word, [4..] arrivals per (boundary, group)
-    bool env_no_fused = false, last_fused = false;
-    int env_adj_tail = 0;          // testing (SSDE_ADJ_TAIL): rows past a window's end before its backward recursion starts
+    bool last_fused = false;
     bool cv_adj = false;           // gradient by a reverse sweep: one wave per (group, window), two passes (iso_adj_kernel)
     DevBuf<double> adj_ckpt;       // ... the state entering every adj_ckpt_rows-th row of every window (grown on demand)
     bool cv_one_wave() const { return cv_single || cv_few || cv_adj; }
@@ -206,7 +201,6 @@ struct ssde_handle {
     hipEvent_t ev_fork = nullptr, ev_join[2] = {nullptr, nullptr};
     hipEvent_t ev_async = nullptr;            // end of the last ssde_eval_device on the caller's stream: a synchronous call waits for it
     bool async_pending = false;
-    bool env_own_stream = false;
 
     // timing of the dominant kernel (recorded on the stream it is launched on)
     hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr;   // the CURRENT evaluation's pair: ev_ring[ev_idx % EV_RING]
@@ -255,18 +249,14 @@ struct ssde_handle {
     double* tv_out_pinned = nullptr;
     double* tv_chk_pinned = nullptr;          // [TV_LEAN_ITEMS] the items' hand-over checks of a lean replay (eval_tv_graph)
     bool tv_graph_lean[2] = {false, false};
-    bool env_tv_no_lean = false;
     DevBuf<double> lap_out;                   // ssde_laplace_eval: result vectors of a batch of asynchronous evaluations
-    double* out_pinned = nullptr;             // read-back target of the synchronous ssde_eval (2 + n_full doubles)
     // publication of a synchronous evaluation's result by its reducing launch (ReduceArgs.pub, ssde_device.hpp): the host spins
     // on a sequence word in pinned memory instead of issuing a read-back copy
     double* pub_pinned = nullptr;             // [2 + n_full] result, then (128-byte aligned) the sequence word
     unsigned long long* pub_flag = nullptr;
     unsigned long long pub_seq = 0;
     DevBuf<unsigned int> pub_count;
-    bool pub_ok = false;                      // buffers exist and SSDE_PUBLISH is set (opt-in)
     DevBuf<double> wave_clock;                // SSDE_WAVE_CLOCK=file: per-wave stamps of the last shared-covariance launch, written at destroy
-    std::string wave_clock_file;
     int wave_clock_items = 0;
     bool pub_request = false;                 // run_once asks the next eval_device to publish
     std::vector<double> gain_cum[4];          // build_gain_table's running sums
@@ -330,7 +320,6 @@ struct ssde_handle {
     double check_floor = 0.0;                 // > 0: a disagreement that a 4x longer warm-up did NOT reduce -- rounding in the states, not a short warm-up; accepted up to here
     // host-side phase clock of the isotropic path (SSDE_TRACE=1 at create; printed at destroy): plan, gain table,
     // main launch(es), finalize launch, read-back
-    bool trace = false;
     double trace_us[6] = {0, 0, 0, 0, 0, 0};
     int64_t trace_n = 0;
     int trace_skip = 0;

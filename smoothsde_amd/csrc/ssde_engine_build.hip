@@ -23,10 +23,8 @@ int choose_iso_split(ssde_handle* h) {
     // Direction split: a 10^4-track batch is only ~160 waves for 1024 SIMDs; give every
     // covariance-affecting direction its own wave (each recomputes the cheap primal) until
     // the grid holds a few waves per SIMD.  SSDE_ISO_SPLIT=fused|split overrides.
-    const char* env = getenv("SSDE_ISO_SPLIT");
-    bool split = false;  // time windows (below) fill the chip without recomputing the primal
-    if (env && !strcmp(env, "fused")) split = false;
-    if (env && !strcmp(env, "split")) split = true;
+    const char* env = h->knobs.iso_split ? h->knobs.iso_split->c_str() : nullptr;
+    const bool split = h->knobs.iso_split == "split";  // (unset or "fused": time windows (below) fill the chip without recomputing the primal)
     int np = 0;
     if (split) {
         // mu rides with the cheapest covariance direction (sigma_obs), else alone
@@ -93,8 +91,7 @@ int lattice_pad(const ssde_desc* d, ssde_handle* h, const std::vector<int64_t>& 
     // by at most this relative amount, and the nllk by no more (each row's term has an O(1) log-derivative in dt): the
     // default leaves two orders of magnitude to the 1e-10 parity bar.  Long series with inexact steps (stamp / step > ~5000)
     // are beyond it and keep the per-row transition; SSDE_GRID_RTOL loosens it at the caller's own risk.
-    double rtol = 1e-12;
-    if (const char* e = getenv("SSDE_GRID_RTOL")) rtol = std::max(0.0, atof(e));
+    const double rtol = h->knobs.grid_rtol;
     if (!std::isfinite(delta) || !std::isfinite(dmax) || !(delta > 0.0)) { cleanup(); return SSDE_OK; }   // no used interval, or not a grid
     if (dmax == delta) { h->snap_dt = delta; cleanup(); return SSDE_OK; }           // regular (whatever the unused first intervals are)
     if (dmax <= delta * (1.0 + rtol)) { h->snap_dt = 0.5 * (delta + dmax); cleanup(); return SSDE_OK; }   // regular to the last bits
@@ -138,13 +135,13 @@ constexpr int SSDE_RETRY_WITHOUT_PP = -78;        // internal: the drift's block
 // 0.072 against 0.067 ms, 1.24e7: 0.072 / 0.077, 1.74e7: 0.072 / 0.096).  Built from LAG_MIN_BULK_ROWS, above every crossover seen.
 constexpr double LAG_MIN_BULK_ROWS = 1.6e7;
 static int build_lagstats(ssde_handle* h, int G, const std::vector<int32_t>& lane_ns, const std::vector<int32_t>& glen) {
-    if (const char* e = getenv("SSDE_LAGSTATS")) if (atoi(e) == 0) return SSDE_OK;
+    if (h->knobs.lagstats == 0) return SSDE_OK;
     if (!(h->model == SSDE_MODEL_CTCRW && h->use_shared && !h->drift && h->n_clean_groups == G && h->uniform_dt && h->iso_parts == 1 &&
           (h->d == 1 || h->d == 2) && h->glen_max > LAG_A))
         return SSDE_OK;
     int64_t bulk = 0;
     for (int32_t ns : lane_ns) bulk += ns > LAG_A ? ns - LAG_A : 0;
-    const bool forced = getenv("SSDE_LAGSTATS") && atoi(getenv("SSDE_LAGSTATS")) == 2;     // (testing: whatever the rule says)
+    const bool forced = h->knobs.lagstats == 2;     // (testing: whatever the rule says)
     if (!forced && (double)bulk < LAG_MIN_BULK_ROWS) return SSDE_OK;
     const auto t0 = std::chrono::steady_clock::now();
     TileView tv;
@@ -210,10 +207,10 @@ static int plan_register_path(ssde_handle* h, int G, const std::vector<int32_t>&
             //  has no such lanes -- found by fuzz seed 552, round 5: launch_iso_few refused the launch)
             for (auto& sl : h->slots) mu_streamed = mu_streamed || (sl.par_j < h->d && sl.col >= 0);
             h->cv_few = !h->cv_full && !h->has_h && !mu_streamed && h->n_stream_cols >= 1 && h->n_stream_cols <= 2 * CV_FEW_K &&
-                        (int)cols.size() <= 2 * CV_KC && !getenv("SSDE_CV_NO_FEW");
+                        (int)cols.size() <= 2 * CV_KC && !h->knobs.cv_no_few;
             // (the wide instantiation -- more than four columns or tangents -- of CTCRW with two response columns spills: the pipeline)
             const bool wide = h->n_stream_cols > CV_FEW_K || (int)cols.size() > CV_KC;
-            if (wide && h->model == SSDE_MODEL_CTCRW && h->d == 2 && !getenv("SSDE_CV_FEW_WIDE")) h->cv_few = false;
+            if (wide && h->model == SSDE_MODEL_CTCRW && h->d == 2) h->cv_few = false;
         }
         {
             // the gradient by a reverse sweep (k_iso_adj.hip): its cost does not depend on the number of columns, so it takes every batch
@@ -222,8 +219,7 @@ static int plan_register_path(ssde_handle* h, int G, const std::vector<int32_t>&
             bool mu_streamed = false;
             for (auto& c : cols) mu_streamed = mu_streamed || (c.type >= 3 && c.chan >= 0);
             for (auto& sl : h->slots) mu_streamed = mu_streamed || (sl.par_j < h->d && sl.col >= 0);       // (free or fixed: the lanes are the MU ones either way)
-            const char* e = getenv("SSDE_CV_ADJ");
-            const int mode = e ? atoi(e) : 1;
+            const int mode = h->knobs.cv_adj.value_or(1);
             h->cv_adj = mode > 0 && !h->cv_single && (!h->has_h || h->d == 1 || h->cv_full) && (!h->cv_full || h->d == 2) && h->n_stream_cols >= 1 &&
                         adj_ks(h->n_stream_cols) >= 0 && (!mu_streamed || adj_ks(h->n_stream_cols) <= 9) && (!h->cv_few || mode > 1);
             if (h->cv_adj) h->cv_few = false;
@@ -238,14 +234,6 @@ static int plan_register_path(ssde_handle* h, int G, const std::vector<int32_t>&
         const int N = (int)cols.size();
         int n_w[CV_WAVES];
         for (int p = 0; p < CV_WAVES; p++) n_w[p] = 0;
-        bool dealt_by_env = false;
-        if (const char* e = getenv("SSDE_CV_DEAL")) {              // testing: "n0,n1,...,n7"
-            int v[8], tot = 0;
-            if (sscanf(e, "%d,%d,%d,%d,%d,%d,%d,%d", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &v[7]) == 8) {
-                for (int p = 0; p < 8; p++) { v[p] = std::min(std::max(v[p], 0), CV_KC); tot += v[p]; }
-                if (tot == N) { for (int p = 0; p < 8; p++) n_w[p] = v[p]; dealt_by_env = true; }
-            }
-        }
         if (h->cv_few) { n_w[0] = std::min(N, CV_KC); n_w[1] = N - n_w[0]; }     // (iso_few_kernel: every column on the one wave; slots 0-3 / 4-7 = parts 0 / 1)
         else
         if (h->cv_single) {
@@ -260,8 +248,7 @@ static int plan_register_path(ssde_handle* h, int G, const std::vector<int32_t>&
                 h->cv_pidx[k] = c.pidx;
             }
             cols.clear();                                          // (dealt)
-        } else
-        if (!dealt_by_env) {
+        } else {
             int left = N;
             for (int k = 0; k < CV_KC && left > 0; k++)
                 for (int p = 1; p < CV_WAVES - 1 && left > 0; p++) { n_w[p]++; left--; }
@@ -335,9 +322,9 @@ static int plan_register_path(ssde_handle* h, int G, const std::vector<int32_t>&
         bool all_clean = h->uniform_dt;
         for (int g = 0; g < G; g++) all_clean = all_clean && gflags[g] != 0;
         // (the lanes that carry their own covariance are issue-bound already: the table form costs them a third more -- tile the columns)
-        if (!all_clean && h->pp_drift.nb > 0 && !getenv("SSDE_DRIFT_PP_ALL")) return SSDE_RETRY_WITHOUT_PP;
-        if (!all_clean && getenv("SSDE_NO_DRIFT_GENERAL")) return SSDE_RETRY_WITHOUT_DRIFT;
-        if (getenv("SSDE_NO_SHARED")) all_clean = false;                  // (testing: the general lanes on a batch the shared ones would take)
+        if (!all_clean && h->pp_drift.nb > 0 && !h->knobs.drift_pp_all) return SSDE_RETRY_WITHOUT_PP;
+        if (!all_clean && h->knobs.no_drift_general) return SSDE_RETRY_WITHOUT_DRIFT;
+        if (h->knobs.no_shared) all_clean = false;                  // (testing: the general lanes on a batch the shared ones would take)
         h->drift = all_clean ? 1 : 2;
         h->drift_nstate = all_clean ? drift_nstate(h->model, h->d, h->n_stream_cols) : drift_general_nstate(h->model, h->d, h->n_stream_cols);
     }
@@ -365,11 +352,11 @@ static int plan_register_path(ssde_handle* h, int G, const std::vector<int32_t>&
     }
     for (size_t ns = 1; ns < cnt.size(); ns++)
         if (cnt[ns]) h->clean_ns_hist.push_back({(int)ns, cnt[ns]});
-    h->use_shared = h->uniform_dt && h->n_clean_groups > 0 && h->iso_parts == 1 && !getenv("SSDE_NO_SHARED");
+    h->use_shared = h->uniform_dt && h->n_clean_groups > 0 && h->iso_parts == 1 && !h->knobs.no_shared;
     if (h->drift) h->use_shared = h->drift == 1;
     // (two concurrent launches, a fork / join and a longer finalize cost ~40 us: with fewer than a quarter of the groups on
     //  the shared kernel that is more than it wins -- measured 0.82 against 0.78 ms at one tenth -- and everything stays general)
-    if (h->use_shared && h->n_clean_groups < G && 4 * h->n_clean_groups < G && !getenv("SSDE_SHARED_ALWAYS")) h->use_shared = false;
+    if (h->use_shared && h->n_clean_groups < G && 4 * h->n_clean_groups < G) h->use_shared = false;
     // time windows: enough (group, window, part) workgroups for ~2 waves on each of the 1024 SIMDs
     int glmax = 0;
     for (int g = 0; g < G; g++) glmax = std::max(glmax, glen[g]);
@@ -384,8 +371,8 @@ static int plan_register_path(ssde_handle* h, int G, const std::vector<int32_t>&
     // (k_iso.hip: every general kernel but CTCRW's irregular-grid one is built for two waves per SIMD)
     // (a mixed batch whose general launch gets a plan of its own, below, keeps the shared kernel's plan here whatever the
     //  share of its groups)
-    const bool own_plans = h->use_shared && h->n_clean_groups < G && !getenv("SSDE_CHUNKS") && !getenv("SSDE_ONE_PLAN");
-    if (!h->drift && !(h->model == SSDE_MODEL_CTCRW && !h->uniform_dt) && (!h->uniform_dt || (2 * h->n_clean_groups < G && !own_plans)) && !getenv("SSDE_NO_LIGHT2"))
+    const bool own_plans = h->use_shared && h->n_clean_groups < G && !h->knobs.chunks;
+    if (!h->drift && !(h->model == SSDE_MODEL_CTCRW && !h->uniform_dt) && (!h->uniform_dt || (2 * h->n_clean_groups < G && !own_plans)))
         // measured (tools/bench_na.py, SSDE_CHUNKS sweep 12 .. 32): the scalar-covariance models run best with
         // 1.5 work items per wave slot (shorter items even out the tail; their hand-over dumps are small), CTCRW
         // with one (its 32-component dumps make every further boundary cost what the shorter tail gains)
@@ -398,8 +385,7 @@ static int plan_register_path(ssde_handle* h, int G, const std::vector<int32_t>&
     // are ordinary ones; a batch far beyond it is streamed past the caches (measured, profiles/r04_a_nt_vs_plain.txt: 205 MB
     // 0.053 -> 0.044 ms with ordinary loads, 260 / 330 / 410 MB no difference, 1.6 GB 0.259 -> 0.274 ms)
     h->stream_nt = (double)h->tile_doubles * 8.0 > 300e6;
-    if (const char* e = getenv("SSDE_NT")) h->stream_nt = atoi(e) != 0;
-    if (const char* e = getenv("SSDE_CHUNKS")) { want = atoi(e); h->chunks_forced = true; }   // testing
+    if (h->knobs.chunks) { want = *h->knobs.chunks; h->chunks_forced = true; }   // testing
     h->max_chunks = std::max(1, std::min(want + 1, std::max(1, glmax / (4 * WIN_ALIGN))));
     // (row-varying tau / nu with few groups: windows down to two alignment units, shorter than their warm-up -- with CUs idle
     //  the redundant warm-up rows run in parallel, only a workgroup's own chain of rows matters; ssde_engine_iso.hip picks)
@@ -413,7 +399,7 @@ static int plan_register_path(ssde_handle* h, int G, const std::vector<int32_t>&
     // sets the evaluation's time (0.75-0.9 ms with 1-30 % of the tracks affected).  The general launch gets a plan of
     // its own: enough windows to fill its two waves per SIMD (plan_windows keeps them at least two warm-ups long).
     int buf_chunks = h->max_chunks;
-    if (h->use_shared && !h->drift && h->n_clean_groups < G && !h->chunks_forced && !getenv("SSDE_ONE_PLAN")) {
+    if (h->use_shared && !h->drift && h->n_clean_groups < G && !h->chunks_forced) {
         const int gd8 = ((G - h->n_clean_groups) + 7) / 8 * 8;
         const int want_d = std::max(1, (h->model == SSDE_MODEL_CTCRW ? 2048 : 3072) / gd8);
         // (the hand-over dumps are sized for every group x the longer plan: keep them under ~0.5 GB)
@@ -424,7 +410,7 @@ static int plan_register_path(ssde_handle* h, int G, const std::vector<int32_t>&
     // Quiet rows: a regular-grid batch whose groups hold missing rows here and there (no complete group to keep on the shared
     // kernel, or some) -- the general lanes drop their covariance wherever it is stationary on all 64 lanes (k_iso.hip).  Worth it
     // when a fair share of the blocks qualifies (with missing rows in every block of every group the flags cost a little and win nothing).
-    if (h->uniform_dt && !h->drift && h->iso_parts == 1 && h->n_clean_groups < G && glmax >= 8 * WIN_ALIGN && !getenv("SSDE_NO_QUIET")) {
+    if (h->uniform_dt && !h->drift && h->iso_parts == 1 && h->n_clean_groups < G && glmax >= 8 * WIN_ALIGN && !h->knobs.no_quiet) {
         const int U = iso_block_rows(h->model);
         h->nan_words = (glmax / U + 63) / 64 + 1;
         HIPCHK(h, h->nan_bits.alloc((size_t)G * h->nan_words));
@@ -451,16 +437,15 @@ static int plan_register_path(ssde_handle* h, int G, const std::vector<int32_t>&
         h->quiet_share = n_blocks > 0 ? (double)n_quiet / (double)n_blocks : 0.0;
         // (measured, 10^4 x 10^4 CTCRW with 1 / 2 / 3 / 5 missing rows per track = shares 0.98 / 0.53 / 0.33 / 0.18: 0.40 / 0.70 / 0.78 /
         //  0.86 ms against 0.84-0.87 without quiet rows)
-        const double need = getenv("SSDE_QUIET_ALWAYS") ? 0.0 : h->model == SSDE_MODEL_CTCRW ? 0.25 : 0.2;
+        const double need = h->knobs.quiet_always ? 0.0 : h->model == SSDE_MODEL_CTCRW ? 0.25 : 0.2;
         h->quiet_ok = n_blocks > 0 && (double)n_quiet >= need * (double)n_blocks;
         if (!h->quiet_ok) { h->nan_bits.release(); h->nan_words = 0; }
         else { HIPCHK(h, h->quiet_flag.alloc(1)); HIPCHK(h, hipMemset(h->quiet_flag.p, 0, 8)); }
-        if (const char* e = getenv("SSDE_QUIET_WINDOW")) h->env_quiet_window = std::max(0, atoi(e));
         if (h->quiet_ok && !h->chunks_forced) {
             // nearly every row a quiet row: the rows cost what the shared-covariance kernels' cost, and windows cost warm-up rows and
             // hand-over checks -- one work item per SIMD (10^4 tracks: 6 windows 0.40 ms, 12 windows 0.435); otherwise one per wave
             // slot (two waves per SIMD), which evens out the stretches of general rows (2 missing rows per track: 0.70 against 0.84)
-            const int slots = getenv("SSDE_QUIET_SLOTS") ? atoi(getenv("SSDE_QUIET_SLOTS")) : h->quiet_share >= 0.9 ? 1024 : 2048;
+            const int slots = h->quiet_share >= 0.9 ? 1024 : 2048;
             if (h->use_shared && h->want_chunks_d > 0) {
                 const int gd8 = ((G - h->n_clean_groups) + 7) / 8 * 8;
                 h->want_chunks_d = std::max(1, std::min(h->want_chunks_d, slots / gd8));
@@ -483,8 +468,6 @@ static int plan_register_path(ssde_handle* h, int G, const std::vector<int32_t>&
         // (measured, profiles/r05_fused_finalize_ab.txt: SLOWER than the dependent launch it replaces -- a wave's way from "my rows are
         //  done" to "the result is out" is six device-scope round trips of ~2 us across the XCDs -- so the two-launch form stays the
         //  default and SSDE_FUSED_FINALIZE=1 selects this one, bitwise the same numbers)
-        h->env_no_fused = true;
-        if (const char* e = getenv("SSDE_FUSED_FINALIZE")) h->env_no_fused = atoi(e) == 0;
     }
     if (h->drift == 3) HIPCHK(h, hipMemset(h->bnd.p, 0, h->bnd.n * 8));      // (a part dumps its own block of a hand-over record; the check reads all of it)
     h->partial_doubles = (size_t)std::max(MAX_PARTS, CV_WAVES) * buf_chunks * std::max(NACC_MAX, 2 + CV_KC + 2) * G;
@@ -498,10 +481,11 @@ int build(const ssde_desc* d, ssde_handle* h, const ParLayout* part_layout) {
     // (what the caller set on the handle before build() survives a retry: the reset below wipes everything else -- ADVICE r04)
     const bool force_tv = h->force_tv, wide_ok = h->wide_ok;
     bool no_drift_pp = h->no_drift_pp;
+    const Knobs knobs = h->knobs = knobs_from_env(WIN_ALIGN);     // the one place the library reads its environment
     auto reset = [&]() {
         release_device(h);
         *h = ssde_handle();
-        h->force_tv = force_tv; h->wide_ok = wide_ok; h->no_drift_pp = no_drift_pp;
+        h->force_tv = force_tv; h->wide_ok = wide_ok; h->no_drift_pp = no_drift_pp; h->knobs = knobs;
     };
     int st = build_impl(d, h, part_layout, true);
     if (st == SSDE_RETRY_WITHOUT_PP) {
@@ -548,18 +532,6 @@ static int check_descriptor(const ssde_desc* d, ssde_handle* h, const ParLayout*
     if (d->n < 2) return fail(h, SSDE_ERR_ARG, "need at least two rows");
     if (!d->id || !d->times || !d->obs || !d->ncol_fe) return fail(h, SSDE_ERR_ARG, "id/times/obs/ncol_fe must be non-NULL");
     h->model = d->model; h->d = d->n_dim; h->q = d->n_par; h->n = d->n;
-    if (const char* e = getenv("SSDE_WINDOW")) h->env_window = std::max(1, atoi(e));     // testing: deliberately short overlaps
-    if (const char* e = getenv("SSDE_ADJ_TAIL")) h->env_adj_tail = std::max(1, atoi(e));  // testing: ... of the backward recursion only (k_iso_adj.hip)
-    if (const char* e = getenv("SSDE_TV_WAVES")) h->env_tv_waves = std::max(1, atoi(e));
-    if (const char* e = getenv("SSDE_TV_MINLEN")) h->env_tv_minlen = std::max(WIN_ALIGN, atoi(e) / WIN_ALIGN * WIN_ALIGN);
-    if (const char* e = getenv("SSDE_T0_COST")) h->env_t0_cost = atof(e);
-    if (const char* e = getenv("SSDE_W0_RATIO")) h->env_w0_ratio = atof(e);     // 0 = equal windows on the general kernel
-    h->env_no_derive = getenv("SSDE_NO_DERIVE") != nullptr;
-    h->env_no_graph = getenv("SSDE_NO_GRAPH") != nullptr;
-    h->env_no_exact_hess = getenv("SSDE_NO_EXACT_HESS") != nullptr;
-    h->env_own_stream = getenv("SSDE_SYNC_OWN_STREAM") != nullptr;
-    h->trace = getenv("SSDE_TRACE") != nullptr;
-    if (const char* e = getenv("SSDE_WAVE_CLOCK")) h->wave_clock_file = e;
     h->sdim = state_dim(d->model, d->n_dim);
     h->na_any = d->na_mode == SSDE_NA_ANY_NAN;
     h->has_h = is_kalman(d->model) && d->h_array != nullptr;
@@ -639,7 +611,7 @@ static int stage_basis_tables(const ssde_desc* d, ssde_handle* h, bool on_dev, i
         bool kcap_ok = true;
         for (int j = 0; j < MAX_Q; j++) kcap_ok = kcap_ok && cols_of[j] <= DIRECT_KCAP;
         const bool fast_family = !is_kalman(d->model) && !is_eseal(d->model) && h->L.n_decay == 0 && with_cols.size() <= 2 &&
-                                 kcap_ok && !getenv("SSDE_NO_DIRECT_FAST") && !getenv("SSDE_NO_PP_FAST");
+                                 kcap_ok && !h->knobs.no_direct_fast;
         for (int j = 0; j < d->n_par; j++) {
             const ssde_ppbasis* pb = d->basis_re[j];
             if (!pb) continue;
@@ -720,7 +692,6 @@ static int find_segments(const ssde_desc* d, ssde_handle* h, bool on_dev, int64_
     }
 
     HIPCHK(h, h->out.alloc(2 + h->L.n_full));
-    HIPCHK(h, hipHostMalloc((void**)&h->out_pinned, (size_t)(2 + h->L.n_full) * 8, hipHostMallocDefault));
     {
         const size_t words = ((size_t)(2 + h->L.n_full) + 15) / 16 * 16;           // the sequence word gets a 128-byte line of its own
         HIPCHK(h, hipHostMalloc((void**)&h->pub_pinned, (words + 16) * 8, hipHostMallocDefault));
@@ -729,13 +700,16 @@ static int find_segments(const ssde_desc* d, ssde_handle* h, bool on_dev, int64_
         HIPCHK(h, h->pub_count.alloc(1));
         HIPCHK(h, hipMemset(h->pub_count.p, 0, sizeof(unsigned int)));
         // measured in the engine (tools/bench_strong.py, same session): 27-30 us outside the kernel either way -- the read-back
-        // copy it saves is paid back in the counting and the system-scope store; opt-in, for the record
-        h->pub_ok = getenv("SSDE_PUBLISH") != nullptr;
+        // copy it saves is paid back in the counting and the system-scope store; opt-in (SSDE_PUBLISH), for the record
     }
     for (auto& pr : h->ev_ring) { HIPCHK(h, hipEventCreate(&pr[0])); HIPCHK(h, hipEventCreate(&pr[1])); }
     h->ev_k0 = h->ev_ring[0][0]; h->ev_k1 = h->ev_ring[0][1];
 
     return SSDE_OK;
+}
+
+static bool one_step(const ssde_handle* h, double lo, double hi) {     // is [lo, hi] one step to within SSDE_GRID_RTOL?  (the tolerance and its argument: lattice_pad)
+    return std::isfinite(lo) && lo > 0.0 && hi <= lo * (1.0 + h->knobs.grid_rtol);
 }
 
 // ---- step 4a: the direct families keep the long format (lane = row is already coalesced) ----
@@ -746,7 +720,6 @@ static int build_direct(const ssde_desc* d, ssde_handle* h, bool on_dev, int64_t
     // column stride: padded so that the same row of different columns does not fall on addresses that are
     // equal modulo a large power of two (all columns of a row are fetched together)
     h->col_stride = ((n + 63) / 64) * 64 + 160;
-    if (const char* e = getenv("SSDE_COL_PAD")) h->col_stride = ((n + 63) / 64) * 64 + atoi(e);
     // columns evaluated on the fly from a basis table need no copy: col = -2
     int ncb = 0;
     for (auto& s : h->slots)
@@ -772,7 +745,6 @@ static int build_direct(const ssde_desc* d, ssde_handle* h, bool on_dev, int64_t
         idb.release();
     }
     h->direct_blocks = (int)std::min<int64_t>((n + 255) / 256, 2048);
-    if (const char* e = getenv("SSDE_DIRECT_BLOCKS")) h->direct_blocks = std::max(1, std::min(atoi(e), 65536));
     h->partial_doubles = (size_t)(1 + MAX_Q + h->slots.size() + MAX_DECAY) * h->direct_blocks;
     {
         // regular grid?  (min / max over the scored intervals)
@@ -784,10 +756,7 @@ static int build_direct(const ssde_desc* d, ssde_handle* h, bool on_dev, int64_t
         HIPCHK(h, hipMemcpy(mmh.data(), mm.p, mmh.size() * 8, hipMemcpyDeviceToHost));
         double dmin = INFINITY, dmax = -INFINITY;
         for (int b = 0; b < nb; b++) { dmin = std::min(dmin, mmh[2 * b]); dmax = std::max(dmax, mmh[2 * b + 1]); }
-        // regular to the last bits counts as regular (the tolerance and its argument: lattice_pad)
-        double rtol = 1e-12;
-        if (const char* e = getenv("SSDE_GRID_RTOL")) rtol = std::max(0.0, atof(e));
-        h->direct_uniform_dt = (dmax <= dmin * (1.0 + rtol)) && dmin > 0.0 && std::isfinite(dmin) && !(d->flags & SSDE_FLAG_NO_UNIFORM_DT);
+        h->direct_uniform_dt = one_step(h, dmin, dmax) && !(d->flags & SSDE_FLAG_NO_UNIFORM_DT);
         h->direct_dt = h->direct_uniform_dt ? 0.5 * (dmin + dmax) : 0.0;
         h->uniform_dt = h->direct_uniform_dt;
         mm.release();
@@ -797,7 +766,7 @@ static int build_direct(const ssde_desc* d, ssde_handle* h, bool on_dev, int64_t
             if (sl.col == -1) { h->df_icpt[sl.par_j] = sl.pidx; continue; }
             if (streamed_par.empty() || streamed_par.back() != sl.par_j) streamed_par.push_back(sl.par_j);
         }
-        bool ok = streamed_par.size() <= 2 && !getenv("SSDE_NO_DIRECT_FAST") && h->L.n_decay == 0;   // decaying columns: generic kernel
+        bool ok = streamed_par.size() <= 2 && !h->knobs.no_direct_fast && h->L.n_decay == 0;   // decaying columns: generic kernel
         if (ok) {
             for (auto& sl : h->slots) {
                 if (sl.col == -1) continue;
@@ -917,12 +886,12 @@ static int build_impl(const ssde_desc* d, ssde_handle* h, const ParLayout* part_
         // one animal) stay on the lane = direction path, whose windows cut ONE track into a hundred concurrent pieces.
         // (a per-row H_array couples the dimensions: CTCRW with d = 2 has 4 x 4 covariance lanes in k_iso_colvar.hip, any P0)
         const bool iso_cfg = !h->has_h && p0_is_isotropic(d, h->p0_iso);
-        const bool full_cfg = h->has_h && h->d == 2 && !getenv("SSDE_NO_COLVAR_FULL");
+        const bool full_cfg = h->has_h && h->d == 2 && !h->knobs.no_colvar_full;
         // (one response column: H_array[,,i] is the row's measurement variance -- the isotropic lanes of k_iso_colvar.hip with h = H_i)
-        const bool h1_cfg = h->has_h && h->d == 1 && p0_is_isotropic(d, h->p0_iso) && !getenv("SSDE_NO_COLVAR_FULL");
+        const bool h1_cfg = h->has_h && h->d == 1 && p0_is_isotropic(d, h->p0_iso) && !h->knobs.no_colvar_full;
         // (... also with CONSTANT coefficients: tracks with error ellipses and one tau, one nu -- the intercepts are columns of ones)
         if (!iso_ok && h->d <= 2 && allow_drift && (iso_cfg || full_cfg || h1_cfg) && (!h->const_coeff || full_cfg || h1_cfg) && !(d->flags & SSDE_FLAG_FORCE_DENSE) &&
-            !getenv("SSDE_NO_DRIFT") && !h->force_tv) {
+            !h->knobs.no_drift && !h->force_tv) {
             bool mu_only = true;
             for (auto& sl : h->slots)
                 if (sl.col >= 0 && sl.par_j >= h->d) mu_only = false;
@@ -930,9 +899,8 @@ static int build_impl(const ssde_desc* d, ssde_handle* h, const ParLayout* part_
             // the lane = direction path costs ~0.07 ms + 0.2 us per 1000 rows, the register lanes ~0.09 ms (0.18 for CTCRW: its transient
             // window) + 0.012 us per 1000 rows -- round 3's rule, >= 32 tracks, was wrong by 17-117 % at 32-64 tracks x 10^3 rows).
             // SSDE_DRIFT_MIN_TRACKS keeps its meaning for the tests: a track count decides.
-            int min_tracks = 32;
-            const bool by_tracks = getenv("SSDE_DRIFT_MIN_TRACKS") != nullptr;
-            if (by_tracks) min_tracks = atoi(getenv("SSDE_DRIFT_MIN_TRACKS"));
+            const bool by_tracks = h->knobs.drift_min_tracks.has_value();
+            const int min_tracks = h->knobs.drift_min_tracks.value_or(32);
             const double n_rows = (double)n;
             const bool drift_pays = by_tracks ? h->n_seg >= min_tracks : n_rows >= (h->model == SSDE_MODEL_CTCRW ? 5e5 : 1.5e5);
             if (iso_cfg && mu_only && drift_pays && h->n_stream_cols <= DRIFT_KMAX) {
@@ -944,8 +912,7 @@ static int build_impl(const ssde_desc* d, ssde_handle* h, const ParLayout* part_
                 // d = 2 1.54 / 1.49; CTCRW (AGPR spills on top) 2.3 / 1.44 and the general lanes 1.99 / 1.48 are slower and keep the
                 // streamed form (SSDE_DRIFT_PP_ALL=1: everything that qualifies, for the tests).  What the table form always wins is
                 // HBM: tiles of 8 (d + blocks) bytes per row instead of 8 (d + K).
-                const bool pp_all = getenv("SSDE_DRIFT_PP_ALL") != nullptr;
-                bool pp = !getenv("SSDE_NO_DRIFT_PP") && !h->no_drift_pp && (h->model != SSDE_MODEL_CTCRW || pp_all);
+                bool pp = !h->knobs.no_drift_pp && !h->no_drift_pp && (h->model != SSDE_MODEL_CTCRW || h->knobs.drift_pp_all);
                 int nb = 0, blk_j[2] = {-1, -1};
                 for (auto& sl : h->slots) {
                     if (sl.col < 0) continue;
@@ -977,11 +944,11 @@ static int build_impl(const ssde_desc* d, ssde_handle* h, const ParLayout* part_
             // whatever the batch.
             // (a smooth drift alone, H = sigma_obs^2 I, took the drift kernels above; with H_array, or next to columns of tau / nu, the
             //  drift's design columns are columns of kinds of their own here)
-            bool par_only = (!(mu_only && iso_cfg) || h->const_coeff) && !getenv("SSDE_NO_COLVAR");
+            bool par_only = (!(mu_only && iso_cfg) || h->const_coeff) && !h->knobs.no_colvar;
             if (h->const_coeff && !(full_cfg || h1_cfg)) par_only = false;
             for (auto& sl : h->slots)
                 if (sl.col >= 0 && sl.basis_c >= 0 && !sl.src) par_only = false;      // (a basis block materialised at create is a block of columns)
-            if (getenv("SSDE_CV_NO_MU_COLS"))
+            if (h->knobs.cv_no_mu_cols)
                 for (auto& sl : h->slots)
                     if (sl.col >= 0 && sl.par_j < h->d) par_only = false;
             // (measured, tools/bench_colvar.py --tracks M --rows 1000, 18 columns: 0.18 / 0.19 / 0.20 / 0.22 / 0.24 ms at M = 32 / 128 /
@@ -993,7 +960,7 @@ static int build_impl(const ssde_desc* d, ssde_handle* h, const ParLayout* part_
             for (auto& sl : h->slots)
                 if (!h->fixed[sl.pidx]) { n_dirs++; if (sl.par_j >= h->d) n_tan++; else if (sl.col >= 0) n_mu_cols++; }
             const bool few_shape = iso_cfg && n_mu_cols == 0 && n_tan <= CV_KC * ((h->model == SSDE_MODEL_CTCRW && h->d == 2) ? 1 : 2) && h->n_stream_cols >= 1 && h->n_stream_cols <= 2 * CV_FEW_K &&
-                                   !getenv("SSDE_CV_NO_FEW");                   // (columns may still be shared below: checked again at the plan)
+                                   !h->knobs.cv_no_few;                   // (columns may still be shared below: checked again at the plan)
             //  (With H_array the lane = direction lanes carry a full covariance and cost three times as much: 64 / 640 / 1280 tracks x 10^3 rows,
             //   constant tau / nu: 0.245 / 0.30 / 0.53 ms there against 0.23-0.24 on iso_full_kernel; row-varying, 160 tracks: 0.60 against 0.36.)
             // (round 4, the same sweep: rows decide here too.  The lane = direction path costs ~0.1 ms + 0.35 us per 1000 rows and 32 lanes per
@@ -1009,15 +976,15 @@ static int build_impl(const ssde_desc* d, ssde_handle* h, const ParLayout* part_
                                : n_rows * lpt_dirs >= 4.5e6;
             if (par_only && cv_pays && h->d <= 2 && h->n_stream_cols <= 2 * DRIFT_KMAX) {
                 int nd = h->n_stream_cols;
-                if (!getenv("SSDE_CV_NO_SHARE")) { int st = share_equal_columns(d, h, on_dev, n, &nd); if (st) return st; }
-                if (nd <= DRIFT_KMAX) { h->n_stream_cols = nd; h->drift = 3; h->path = PATH_ISO; h->cv_full = full_cfg; h->cv_single = h->cv_full && nd == 0 && !getenv("SSDE_CV_NO_SINGLE"); }
+                if (!h->knobs.cv_no_share) { int st = share_equal_columns(d, h, on_dev, n, &nd); if (st) return st; }
+                if (nd <= DRIFT_KMAX) { h->n_stream_cols = nd; h->drift = 3; h->path = PATH_ISO; h->cv_full = full_cfg; h->cv_single = h->cv_full && nd == 0; }
                 else return SSDE_RETRY_WITHOUT_DRIFT;              // (the slots were renumbered: start over)
             }
         }
         // row-varying coefficients with H = sigma_obs^2 I and a block-identical P0: the tv path
         // everything the constant-coefficient register path does not take: row-varying coefficients (isotropic
         // lanes), per-row H_array or a P0 that is not block-identical (full-covariance lanes)
-        const bool tv_ok = !iso_ok && h->d <= 2 && !h->drift && !(d->flags & SSDE_FLAG_FORCE_DENSE) && !getenv("SSDE_NO_TV") &&
+        const bool tv_ok = !iso_ok && h->d <= 2 && !h->drift && !(d->flags & SSDE_FLAG_FORCE_DENSE) && !h->knobs.no_tv &&
                            (double)n * (TV_RS + 64) * 8.0 < 150e9;
         if (tv_ok) {
             h->tv_dense = h->has_h || !p0_is_isotropic(d, h->p0_iso);
@@ -1039,7 +1006,7 @@ static int build_impl(const ssde_desc* d, ssde_handle* h, const ParLayout* part_
         DevBuf<double> pad_times, pad_obs;
         const double *t_times = d->times, *t_obs = d->obs;
         bool t_on_dev = on_dev;
-        if (h->path == PATH_ISO && !h->drift && !(d->flags & SSDE_FLAG_NO_UNIFORM_DT) && !getenv("SSDE_NO_LATTICE")) {
+        if (h->path == PATH_ISO && !h->drift && !(d->flags & SSDE_FLAG_NO_UNIFORM_DT) && !h->knobs.no_lattice) {
             int st = lattice_pad(d, h, starts, on_dev, tstarts_pad, pad_times, pad_obs);
             if (st) return st;
             if (h->n_pad > 0) { tn = h->n_pad; t_times = pad_times.p; t_obs = pad_obs.p; t_on_dev = true; }
@@ -1057,7 +1024,7 @@ static int build_impl(const ssde_desc* d, ssde_handle* h, const ParLayout* part_
         if (!t_on_dev) { HIPCHK(h, stage(t_obs, (size_t)tn * d->n_dim, false, s_obs)); p_obs = s_obs.p; }
         std::vector<uint8_t> seg_dirty((size_t)M, 0);
         std::vector<int> seg_napos;
-        if (h->path == PATH_ISO && !h->drift && !getenv("SSDE_NO_REGROUP")) {
+        if (h->path == PATH_ISO && !h->drift && !h->knobs.no_regroup) {
             DevBuf<int64_t> sd;
             DevBuf<int> fl;
             HIPCHK(h, sd.upload(tstarts));
@@ -1068,7 +1035,7 @@ static int build_impl(const ssde_desc* d, ssde_handle* h, const ParLayout* part_
             HIPCHK(h, hipMemcpy(flh.data(), fl.p, (size_t)M * sizeof(int), hipMemcpyDeviceToHost));
             for (int64_t k = 0; k < M; k++) seg_dirty[k] = flh[k] != 0;
             sd.release(); fl.release();
-            if (!getenv("SSDE_NO_NA_SORT")) seg_napos = flh;    // 1 + the track's last row with a missing observation
+            if (!h->knobs.no_na_sort) seg_napos = flh;    // 1 + the track's last row with a missing observation
         }
         std::vector<int64_t> order(M);
         std::iota(order.begin(), order.end(), 0);
@@ -1090,7 +1057,7 @@ static int build_impl(const ssde_desc* d, ssde_handle* h, const ParLayout* part_
         const double* p_times = t_times;
         if (!t_on_dev) { HIPCHK(h, stage(t_times, (size_t)tn, false, s_times)); p_times = s_times.p; }
         h->c_obs = 1;
-        if (!(d->flags & SSDE_FLAG_NO_UNIFORM_DT) && !getenv("SSDE_KEEP_DT_CHANNEL")) {
+        if (!(d->flags & SSDE_FLAG_NO_UNIFORM_DT)) {
             const int nb = 1024;
             DevBuf<double> mm;
             HIPCHK(h, mm.alloc((size_t)nb * 2));
@@ -1100,9 +1067,7 @@ static int build_impl(const ssde_desc* d, ssde_handle* h, const ParLayout* part_
             double lo = INFINITY, hi = -INFINITY;
             for (int b = 0; b < nb; b++) { lo = std::min(lo, mmh[2 * b]); hi = std::max(hi, mmh[2 * b + 1]); }
             mm.release();
-            double rtol = 1e-12;                                    // (regular to the last bits counts as regular: lattice_pad)
-            if (const char* e = getenv("SSDE_GRID_RTOL")) rtol = std::max(0.0, atof(e));
-            if (std::isfinite(lo) && lo > 0.0 && hi <= lo * (1.0 + rtol)) { h->c_obs = 0; h->dt_all = 0.5 * (lo + hi); }
+            if (one_step(h, lo, hi)) { h->c_obs = 0; h->dt_all = 0.5 * (lo + hi); }
         }
         // (a smooth drift evaluated from tables: one channel per block -- its covariate -- instead of one per column)
         const int n_tile_cols = h->pp_drift.nb > 0 ? h->pp_drift.nb : h->n_stream_cols;

@@ -8,6 +8,10 @@
 
 using namespace ssde_engine;
 
+// Measured.  T0_COST: a row of the transient window, in stationary rows.  W0_RATIO: cost of a row of window 0 (every direction) over a
+// row of a later window (one derived) on the general kernel -- 0 .. 1.45 swept, 3 % on CTCRW at 1.2, nothing on the scalar models.
+constexpr double T0_COST = 3.0, W0_RATIO = 1.2;
+
 namespace {
 
 // Warm-up length of a time window: iterate the (data-independent) covariance recursion on the
@@ -81,7 +85,7 @@ void plan_windows(ssde_handle* h, const IsoArgs& a, int* n_chunks, int* window) 
     //  columns: W 48 -> 32, kernel 0.617 -> 0.572 ms, hand-over check 9e-15 -> 6e-14 against the 1e-11 it has to meet)
     W = (int)std::ceil(std::log(1e-18) / std::log(std::max(rho, 1e-300))) + (h->cv_adj ? 0 : 16);
     W = std::max(W, 16);
-    if (h->env_window > 0) W = h->env_window;                             // testing: deliberately short overlaps
+    if (h->knobs.window) W = *h->knobs.window;                             // testing: deliberately short overlaps
     if ((int64_t)W * h->window_boost > (int64_t)h->glen_max) return;     // longer than a track: sequential filter
     W *= h->window_boost;
     W = (W + WIN_ALIGN - 1) / WIN_ALIGN * WIN_ALIGN;
@@ -320,7 +324,7 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
         // ... which is loose (a partition-of-unity basis reaches max |coef|, the bound says sum |coef|): once a launch has run,
         // the range it actually saw, widened by a quarter of its width (+ 0.05), bounds the plan; a parameter jump that leaves
         // it fails the hand-over check and the retry plans from that evaluation's own range
-        if (h->cv_ranges_pinned && !getenv("SSDE_CV_DESIGN_BOUND"))
+        if (h->cv_ranges_pinned)
             for (int j = 0; j < 2; j++) {
                 const double lo = h->cv_ranges_pinned[2 * j], hi = h->cv_ranges_pinned[2 * j + 1];
                 if (!(lo <= hi) || !std::isfinite(lo) || !std::isfinite(hi)) continue;
@@ -359,13 +363,13 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
         if (h->uniform_dt) bm_trans(h->dt_uniform, a.sigma, a.str);
     }
     auto tick = [&]() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double tk0 = h->trace ? tick() : 0.0;
+    double tk0 = h->knobs.trace ? tick() : 0.0;
     plan_windows(h, a, &a.n_chunks, &a.window);
-    if (h->trace) { const double t = tick(); h->trace_us[0] += t - tk0; tk0 = t; }
+    if (h->knobs.trace) { const double t = tick(); h->trace_us[0] += t - tk0; tk0 = t; }
     a.bnd = h->bnd.p; a.chk = h->chk.p;
     a.bnd_stride = h->drift ? std::max(NSTATE_MAX, h->drift_nstate) : NSTATE_MAX;
     a.chk_out = out_dev + (1 + L.n_full);
-    a.derive = (h->env_no_derive || h->drift) ? 0 : 1;
+    a.derive = (h->knobs.no_derive || h->drift) ? 0 : 1;
     a.stream_nt = h->stream_nt ? 1 : 0;
     a.all_clean = ((h->use_shared && h->n_clean_groups == h->n_groups) || h->drift) ? 1 : 0;      // (drift: one dump layout for every group)
     a.nstate_clean = h->drift ? h->drift_nstate
@@ -385,7 +389,7 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
         int st = (h->d == 1) ? build_gain_table<1>(h, a, h->iso_free_mask, s, add)
                              : build_gain_table<2>(h, a, h->iso_free_mask, s, add);
         if (st) return st;
-        if (h->trace) { const double t = tick(); h->trace_us[1] += t - tk0; tk0 = t; }
+        if (h->knobs.trace) { const double t = tick(); h->trace_us[1] += t - tk0; tk0 = t; }
         a.group_mode = 3;
         // Rows past LAG_A from the lag statistics, decided here for this evaluation: the cut K the window plan asks
         // for must fit the statistics (K <= LAG_KMAX) and the head (the stationary gains from row s_stat, K rows before LAG_A);
@@ -431,12 +435,9 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
         h->last_chunks = a.n_chunks;
     }
     // the transient window (gain table, direction form) runs on the wave that owns window 1: that window is
-    // shortened by what the transient rows cost, in stationary rows (SSDE_T0_COST x t0)
-    {
-        const double cost = h->env_t0_cost;
-        a.t0_delta = (int)(cost * a.t0 + WIN_ALIGN - 1) / WIN_ALIGN * WIN_ALIGN;
-    }
-    if (!h->use_shared && !h->drift && a.n_chunks > 1 && h->env_w0_ratio > 0.0) {
+    // shortened by what the transient rows cost, in stationary rows (T0_COST x t0)
+    a.t0_delta = (int)(T0_COST * a.t0 + WIN_ALIGN - 1) / WIN_ALIGN * WIN_ALIGN;
+    if (!h->use_shared && !h->drift && a.n_chunks > 1) {
         // General kernel, every window on its own wave: window 0 carries EVERY direction (windows >= 1 derive one,
         // k_iso.hip) but has no warm-up rows.  With equal windows its waves are the last to finish and the whole
         // launch waits for them (CTCRW: 212 against 163 instructions per row).  Balance: window 0 = [0, L0) with
@@ -444,7 +445,7 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
         // window (t0 = L0), with nothing to subtract from window 1 (t0_delta = 0: it has a wave of its own).
         const bool can_derive = order >= 1 && a.derive && (a.part_mask[0] & DIR_SIG) &&
                                 (a.part_mask[0] & (h->model == SSDE_MODEL_BM_SSM ? DIR_P1 : DIR_P2));
-        const double r = can_derive ? h->env_w0_ratio : 1.0;
+        const double r = can_derive ? W0_RATIO : 1.0;
         const int nc = a.n_chunks;
         const double L0 = ((double)h->glen_max / (nc - 1) + a.window) / (r + 1.0 / (nc - 1));
         const int t0 = (int)(L0 / WIN_ALIGN) * WIN_ALIGN;
@@ -461,7 +462,7 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
         a.nan_bits = h->nan_bits.p; a.nan_words = h->nan_words; a.quiet_flag = h->quiet_flag.p;
         a.quiet_w = (h->plan_warmup + U - 1) / U;
         // (testing: a memory of its own, deliberately short -- the check at the switch has to notice; a retry doubles it like a warm-up)
-        if (h->env_quiet_window > 0) { a.quiet_w = (h->env_quiet_window * h->window_boost + U - 1) / U; h->last_quiet_window = h->env_quiet_window * h->window_boost; }
+        if (h->knobs.quiet_window > 0) { a.quiet_w = (h->knobs.quiet_window * h->window_boost + U - 1) / U; h->last_quiet_window = h->knobs.quiet_window * h->window_boost; }
         a.quiet_b0 = (a.gain_last + SHARED_U - 1) / SHARED_U * SHARED_U / U + 1;
         for (int i = 0; i < 12; i++) a.quiet_p[i] = h->stat_p[i];
         a.quiet_ld = h->stat_ld;
@@ -469,7 +470,7 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
     }
     // The finalising work inside the main launch (fused_finalize_wave, ssde_device.hpp): the shared-covariance kernel alone on the
     // batch (no group on the general kernel, no drift columns); SSDE_FUSED_FINALIZE=0: the two-launch form (A/B -- bitwise the same)
-    const bool fused = h->use_shared && !h->drift && h->n_clean_groups == h->n_groups && !h->hess_req && h->fuse_words.p && !h->env_no_fused;
+    const bool fused = h->use_shared && !h->drift && h->n_clean_groups == h->n_groups && !h->hess_req && h->fuse_words.p && h->knobs.fused_finalize.value_or(false);
     // the reduction's arguments: which accumulator of which part feeds which output slot (needed BEFORE the main launch when the
     // finalising work is fused into it)
     auto fill_ra = [&]() {
@@ -547,7 +548,7 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
                 // window 0 carries every direction and has no warm-up: the balance of the all-general case (below)
                 const bool can_derive = order >= 1 && a.derive && (a.part_mask[0] & DIR_SIG) &&
                                         (a.part_mask[0] & (h->model == SSDE_MODEL_BM_SSM ? DIR_P1 : DIR_P2));
-                const double r = (can_derive && h->env_w0_ratio > 0.0) ? h->env_w0_ratio : 1.0;
+                const double r = can_derive ? W0_RATIO : 1.0;
                 const double L0 = ((double)h->glen_max / (nc - 1) + a.window) / (r + 1.0 / (nc - 1));
                 const int t0 = (int)(L0 / WIN_ALIGN) * WIN_ALIGN;
                 if (t0 >= 2 * WIN_ALIGN && t0 + 2 * a.window < h->glen_max) ad.t0 = t0;
@@ -561,7 +562,7 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
         if (lag_K > 0 && !fused) a.quiet_flag = h->lag_flag.p;     // (the finalize launch folds the bulk's check into out[n_out])
         IsoArgs b = a;
         b.group_mode = 2;
-        if (!h->wave_clock_file.empty()) {
+        if (h->knobs.wave_clock) {
             const int items = ((h->n_groups + 7) / 8 * 8) * a.n_chunks + 8;
             if ((int)h->wave_clock.n < 4 * items) { h->wave_clock.release(); HIPCHK(h, h->wave_clock.alloc((size_t)4 * items)); }
             HIPCHK(h, hipMemsetAsync(h->wave_clock.p, 0, (size_t)4 * items * 8, s));
@@ -608,7 +609,7 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
         if (h->stamps) HIPCHK(h, hipEventRecord(h->ev_k0, s));
         if (h->drift == 3) {
             a.t0 = 0; a.t0_delta = 0;
-            if (!h->wave_clock_file.empty()) {                  // (a build with -DSSDE_CV_CLOCK fills it: cycles per row and phase of every wave)
+            if (h->knobs.wave_clock) {                  // (a build with -DSSDE_CV_CLOCK fills it: cycles per row and phase of every wave)
                 const int items = h->n_groups * a.n_chunks * CV_WAVES;
                 if ((int)h->wave_clock.n < 4 * items) { h->wave_clock.release(); HIPCHK(h, h->wave_clock.alloc((size_t)4 * items)); }
                 HIPCHK(h, hipMemsetAsync(h->wave_clock.p, 0, (size_t)4 * items * 8, s));
@@ -620,8 +621,8 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
                 const int items = adj_items(h->n_groups, a.n_chunks), cb = adj_ckpt_rows(h->model, h->d, h->cv_full), nst = adj_nstate(h->model, h->d, h->cv_full) / 2;
                 const int units = (h->glen_max + WIN_ALIGN - 1) / WIN_ALIGN;
                 a.adj_tail = a.window;
-                if (const char* e = getenv("SSDE_ADJ_DIAG")) a.adj_diag = atoi(e);
-                if (h->env_adj_tail > 0) a.adj_tail = (int)std::min<int64_t>((int64_t)h->env_adj_tail * h->window_boost, h->glen_max);      // (testing)
+                a.adj_diag = h->knobs.adj_diag;
+                if (h->knobs.adj_tail) a.adj_tail = (int)std::min<int64_t>((int64_t)*h->knobs.adj_tail * h->window_boost, h->glen_max);      // (testing)
                 const int len = (units / a.n_chunks + 1) * WIN_ALIGN + (a.n_chunks > 1 ? a.adj_tail : 0);
                 a.adj_ckpt_stride = (int64_t)((len + cb - 1) / cb + 1) * nst * WAVE;
                 const size_t need = order >= 1 ? (size_t)items * (size_t)a.adj_ckpt_stride : (size_t)WAVE;
@@ -652,12 +653,12 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
         h->ev_k_valid = h->stamps;
         h->last_s_stat = -1;
     }
-    if (h->trace) { const double t = tick(); h->trace_us[2] += t - tk0; tk0 = t; }
+    if (h->knobs.trace) { const double t = tick(); h->trace_us[2] += t - tk0; tk0 = t; }
     if (!fused) fill_ra();
     // the hand-over checks and the final sums in one launch (unless the main launch has done them)
     if (!fused) HIPCHK(h, launch_iso_finalize(h->model, h->d, a, ra, s));
     h->last_fused = fused;
-    if (h->trace) {
+    if (h->knobs.trace) {
         const double t = tick(); h->trace_us[3] += t - tk0; h->trace_n++;
         if (h->trace_skip < 8) {                        // the first calls load code objects: not what is being measured
             h->trace_skip++;

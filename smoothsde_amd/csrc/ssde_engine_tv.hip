@@ -125,7 +125,6 @@ int build_tv(const ssde_desc* d, ssde_handle* h, const std::vector<int64_t>& sta
     HIPCHK(h, hipHostMalloc((void**)&h->tv_out_pinned, (MAX_PAR + 2) * 8, hipHostMallocDefault));
     HIPCHK(h, hipHostMalloc((void**)&h->tv_chk_pinned, (size_t)TV_LEAN_ITEMS * 8, hipHostMallocDefault));
     memset(h->tv_chk_pinned, 0, (size_t)TV_LEAN_ITEMS * 8);
-    h->env_tv_no_lean = getenv("SSDE_TV_NO_LEAN") != nullptr;
     TvArgs a;
     tv_base_args(h, a);
     HIPCHK(h, launch_tv_weights(a, 0));
@@ -217,7 +216,7 @@ int tv_plan(ssde_handle* h, double hobs, hipStream_t s) {   // hobs: sigma_obs^2
             //  1e-12 .. 7e-12 against the 1e-11 tolerance, two failures in 400 evaluations and 32 evaluations on a four-fold plan after each)
             if (h->tv_dense) w += WIN_ALIGN;
             w = std::max<int64_t>(w, 16);
-            if (h->env_window > 0) w = h->env_window;
+            if (h->knobs.window) w = *h->knobs.window;
             w *= h->window_boost;
             w = (w + WIN_ALIGN - 1) / WIN_ALIGN * WIN_ALIGN;
             if (2 * w <= h->glen_max) W = (int)w;
@@ -230,7 +229,7 @@ int tv_plan(ssde_handle* h, double hobs, hipStream_t s) {   // hobs: sigma_obs^2
     const int tpw = WAVE >> h->tv_lpt_shift;
     const int64_t n_packs = (h->n_seg + tpw - 1) / tpw;
     int target = 2048;
-    if (h->env_tv_waves > 0) target = h->env_tv_waves;
+    if (h->knobs.tv_waves) target = *h->knobs.tv_waves;
     const int nc_cap = (int)std::max<int64_t>(1, (target + n_packs * h->tv_nb - 1) / (n_packs * h->tv_nb));
     std::vector<TvItem> ig, iv;
     int max_nc = 1;
@@ -242,7 +241,7 @@ int tv_plan(ssde_handle* h, double hobs, hipStream_t s) {   // hobs: sigma_obs^2
         // is what the evaluation waits for.  SSDE_TV_MINLEN: shortest scored stretch of a window (rows).
         int minlen = h->tv_dense ? 2 * WIN_ALIGN : WIN_ALIGN;   // (round 4: 16 rows, not 32, on the isotropic lanes -- C1's filter launch 41.5 -> 33 us; the
                                                                   //  full-covariance lanes cost three times as much per warm-up row: 32)
-        if (h->env_tv_minlen > 0) minlen = h->env_tv_minlen;
+        if (h->knobs.tv_minlen) minlen = *h->knobs.tv_minlen;
         if (W > 0 && L >= 2 * W) nc = std::max(1, std::min(nc_cap, (L + minlen - 1) / minlen));
         max_nc = std::max(max_nc, nc);
         for (int b = 0; b < h->tv_nb; b++)
@@ -331,7 +330,7 @@ int eval_tv_graph(ssde_handle* h, const double* par, int order, double* o_host) 
     // few rows (C1: one animal): every node of the graph costs ~4 us, the three copies as much as the kernels between them -- the
     // kernels read the parameters from, and write the statistics / sums / checks to, pinned host memory themselves (TvArgs.par0_w)
     const int n_items_now = ord ? h->tv_n_items_g : h->tv_n_items_v;
-    const bool lean = !h->env_tv_no_lean && h->tv_chk_pinned && h->tv_stats_blocks <= TV_LEAN_BLOCKS && n_items_now <= TV_LEAN_ITEMS;
+    const bool lean = !h->knobs.tv_no_lean && h->tv_chk_pinned && h->tv_stats_blocks <= TV_LEAN_BLOCKS && n_items_now <= TV_LEAN_ITEMS;
     if (!h->tv_gexec[ord] || h->tv_graph_plan[ord] != h->tv_plan_gen || h->tv_graph_lean[ord] != lean) {
         if (h->tv_gexec[ord]) { (void)hipGraphExecDestroy(h->tv_gexec[ord]); h->tv_gexec[ord] = nullptr; }
         TvArgs a;

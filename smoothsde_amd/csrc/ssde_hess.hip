@@ -21,7 +21,7 @@ namespace ssde_engine {
 // one engine by itself: 3 = every free entry (hyper-dual lanes, k_tv_hess.hip -- its own rows or those of its companion),
 // 2 = the coefficients of a direct family (k_direct_hess.hip), 1 = the drift coefficients of a shared-covariance batch, 0 = none
 static int scope_one(const ssde_handle* e) {
-    if (e->env_no_exact_hess) return 0;
+    if (e->knobs.no_exact_hess) return 0;
     // SSDE_FLAG_EXACT_HESS: the same rows on the lane = direction path next to a handle whose own kernels are first-order only
     if (e->hess_companion) return scope_one(e->hess_companion);
     if (e->path == PATH_TV) {
@@ -183,7 +183,7 @@ static int hess_tv_device(ssde_handle* h, const double* par, const std::vector<i
     for (int attempt = 0;; attempt++) {
         // windows per track: as many as keep ~2048 waves busy, each at least two alignment units of scored rows
         std::vector<TvItem> items;
-        const int target = h->env_tv_waves > 0 ? h->env_tv_waves : 2048;
+        const int target = h->knobs.tv_waves.value_or(2048);
         const int nc_cap = (int)std::max<int64_t>(1, (target + M * n_pb - 1) / (M * n_pb));
         for (int64_t t = 0; t < M; t++) {
             const int L = h->tv_ns_host[(size_t)t];

@@ -12,6 +12,8 @@
 #include "../../smoothsde_amd/csrc/ssde_math.hpp"
 #include "../../smoothsde_amd/csrc/ssde_tv.hpp"
 #include "../../smoothsde_amd/csrc/ssde_adj.hpp"
+#include "../../smoothsde_amd/csrc/ssde_knobs.hpp"
+#include <sstream>
 #include <vector>
 
 using namespace ssde;
@@ -297,6 +299,31 @@ double hostsim_cir(double z0, double z1, double dt, double lmu, double lb, doubl
 double hostsim_direct(int model, double z0, double z1, double dt, double mu, double p1, double p2, double* g) {
     if (model == M_BM) return bm_direct(z0, z1, dt, mu, p1, g[0], g[1]);
     return ou_direct(z0, z1, dt, mu, p1, p2, g[0], g[1], g[2]);
+}
+
+// The engine's knobs as the current environment sets them (csrc/ssde_knobs.hpp), one NAME=value line each ("unset" where an
+// absent variable is a state of its own).  Returns the text's length; nothing is written when it does not fit into cap bytes.
+int hostsim_knobs(int win_align, char* buf, int cap) {
+    const ssde_engine::Knobs k = ssde_engine::knobs_from_env(win_align);
+    std::ostringstream o;
+    o.precision(17);
+    auto put = [&](const char* name, const auto& v) { o << "SSDE_" << name << '=' << v << '\n'; };
+    auto opt = [&](const char* name, const auto& v) { if (v) put(name, *v); else put(name, "unset"); };
+    put("NO_QUIET", k.no_quiet); put("QUIET_ALWAYS", k.quiet_always); put("NO_NA_SORT", k.no_na_sort);
+    put("NO_SHARED", k.no_shared); put("NO_TV", k.no_tv); put("NO_DIRECT_FAST", k.no_direct_fast); put("NO_GRAPH", k.no_graph);
+    put("NO_DERIVE", k.no_derive); put("NO_LATTICE", k.no_lattice); put("NO_REGROUP", k.no_regroup);
+    put("NO_DRIFT", k.no_drift); put("NO_DRIFT_GENERAL", k.no_drift_general); put("NO_DRIFT_PP", k.no_drift_pp);
+    put("DRIFT_PP_ALL", k.drift_pp_all); put("NO_COLVAR", k.no_colvar); put("NO_COLVAR_FULL", k.no_colvar_full);
+    put("CV_NO_SHARE", k.cv_no_share); put("CV_NO_MU_COLS", k.cv_no_mu_cols); put("CV_NO_FEW", k.cv_no_few);
+    put("TV_NO_LEAN", k.tv_no_lean); put("NO_EXACT_HESS", k.no_exact_hess); put("PUBLISH", k.publish); put("TRACE", k.trace);
+    opt("CHUNKS", k.chunks); opt("WINDOW", k.window); opt("ADJ_TAIL", k.adj_tail); opt("TV_WAVES", k.tv_waves);
+    opt("TV_MINLEN", k.tv_minlen); put("QUIET_WINDOW", k.quiet_window); opt("ISO_SPLIT", k.iso_split);
+    opt("DRIFT_MIN_TRACKS", k.drift_min_tracks); opt("CV_ADJ", k.cv_adj); opt("LAGSTATS", k.lagstats);
+    opt("FUSED_FINALIZE", k.fused_finalize); put("GRID_RTOL", k.grid_rtol); put("ADJ_DIAG", k.adj_diag);
+    opt("WAVE_CLOCK", k.wave_clock);
+    const std::string t = o.str();
+    if ((int)t.size() < cap) memcpy(buf, t.c_str(), t.size() + 1);
+    return (int)t.size();
 }
 
 }  // extern "C"

@@ -33,8 +33,18 @@ def load():
         lib.hostsim_kalman_adj_full.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int64, _lp, _lp, _dp, _dp, _dp,
                                                 C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp]
         lib.hostsim_kalman_adj_full.restype = C.c_int
+        lib.hostsim_knobs.argtypes = [C.c_int, C.c_char_p, C.c_int]
+        lib.hostsim_knobs.restype = C.c_int
         _LIB = lib
     return _LIB
+
+
+def knobs(win_align):
+    """The engine's knobs as the current environment sets them (csrc/ssde_knobs.hpp: knobs_from_env): {"SSDE_X": text}."""
+    buf = C.create_string_buffer(1 << 14)
+    n = load().hostsim_knobs(win_align, buf, len(buf))
+    assert 0 < n < len(buf)
+    return dict(line.split("=", 1) for line in buf.value.decode().splitlines())
 
 
 def kalman_adj_full(pb, par):

@@ -16,5 +16,5 @@ ASAN_LIB="$(g++ -print-file-name=libasan.so)"
 cd "$ROOT"
 # (python itself is not instrumented: leak reports about the interpreter are noise)
 LD_PRELOAD="$ASAN_LIB" ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 \
-  SSDE_ORACLE_LIBDIR="$OUT" python -m pytest tests/test_oracle_golden.py tests/test_oracle_quad.py tests/test_kernel_math_host.py tests/test_laplace.py \
+  SSDE_ORACLE_LIBDIR="$OUT" python -m pytest tests/test_oracle_golden.py tests/test_oracle_quad.py tests/test_kernel_math_host.py tests/test_knobs_host.py tests/test_laplace.py \
   -q -m "not gpu" -p no:cacheprovider "$@"
