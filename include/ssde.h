@@ -486,6 +486,18 @@ int ssde_lagstats_host(const double *y, const int64_t *rows, int64_t n_tracks, i
    sizes of ssde_lagstats_host).  SSDE_ERR_ARG when the handle holds none (the dispatch rule did not build them, or a multi-device
    parent: ask its shards). */
 int ssde_lagstats_read(const ssde_handle *h, double *M, double *s, double *n_bulk);
+/* The bulk's forms of ONE evaluation, on the host: what an evaluation on the lag-statistics path computes from M, s and n_bulk
+   (ssde_lagstats_host / ssde_lagstats_read) before its reducing launch, without a device.  CTCRW on a regular
+   grid of step dt; theta = (log sigma_obs, mu_1 .. mu_d, log tau, log nu); p0 = (p11, p12, p22) the covariance recursion starts
+   from, or NULL; K = the cut (16 .. n_taps - 1; the check's cut is K - 16); mask = the gradient directions wanted (1: sigma_obs,
+   2: mu, 4: tau, 8: nu; < 0: all).  taps: 2 x n_taps doubles, the impulse responses of u and of r -- written (zero beyond K) when
+   taps_given == 0, read as they are when taps_given != 0 (entries beyond K are never read).
+   raw: 2 x 6 doubles, S, C_1, C_2, C_3, su_1, su_2 of the cut K and then of the cut K - 16; acc: the 4 + d accumulators
+   [value | sigma_obs | mu_1 .. mu_d | tau | nu] of the cut K; chk: the largest difference between the raw sums of the two cuts,
+   relative to max(|sum|, sqrt(|S| n_bulk)).  SSDE_ERR_ARG: a NULL pointer, d outside 1..2, K out of range, or a theta without
+   a stationary regime. */
+int ssde_lagforms_host(const double *M, const double *s, double n_bulk, int32_t d, const double *theta, double dt, const double *p0,
+                       int32_t K, int32_t mask, int32_t taps_given, double *taps, double *raw, double *acc, double *chk);
 
 #ifdef __cplusplus
 }

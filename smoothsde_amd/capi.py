@@ -504,6 +504,9 @@ def load_library():
     lib.ssde_lagstats_host.restype = C.c_int
     lib.ssde_lagstats_read.argtypes = [C.c_void_p, _dp, _dp, _dp]
     lib.ssde_lagstats_read.restype = C.c_int
+    lib.ssde_lagforms_host.argtypes = [_dp, _dp, C.c_double, C.c_int32, _dp, C.c_double, _dp, C.c_int32, C.c_int32, C.c_int32,
+                                       _dp, _dp, _dp, _dp]
+    lib.ssde_lagforms_host.restype = C.c_int
     lib.ssde_abi_version.argtypes = []
     lib.ssde_abi_version.restype = C.c_int
     lib.ssde_laplace_eval.argtypes = [C.c_void_p, _dp, C.c_int32, C.c_int32, _dp, _dp, _dp, C.POINTER(SsdeLaplaceOpts)]
@@ -543,7 +546,7 @@ WINDOW_TOL = 1e-11  # largest tolerated relative hand-over disagreement between 
 
 EXPORTED_SYMBOLS = ("ssde_create", "ssde_eval", "ssde_eval_device", "ssde_penalty", "ssde_report", "ssde_widen_windows", "ssde_relax_windows",
                     "ssde_info", "ssde_destroy", "ssde_last_error", "ssde_abi_version", "ssde_comm_unique_id", "ssde_comm_init_rank", "ssde_forget", "ssde_laplace_eval", "ssde_last_kernel_ms", "ssde_kernel_ms_history",
-                    "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_smooth")
+                    "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth")
 
 def lagstats_host(tracks):
     """The lag statistics ssde_create builds for a stationary batch, computed on the host: `tracks` is a list of
@@ -560,6 +563,30 @@ def lagstats_host(tracks):
     if st != 0:
         raise ValueError(f"ssde_lagstats_host: status {st}")
     return M, s, float(n[0]), int(a0.value)
+
+
+def lagforms_host(M, s, n_bulk, theta, dt, K, d=None, p0=None, mask=-1, taps=None):
+    """The bulk's forms of one evaluation on the lag-statistics path, on the host: CTCRW on a regular grid of
+    step `dt` at theta = (log sigma_obs, mu_1 .. mu_d, log tau, log nu), cut at `K` taps (the check's cut: K - 16), from the
+    statistics M, s, n_bulk.  `taps` (2 x taps: the impulse responses of u and r): used as they are when given, computed otherwise.
+    Returns a dict: raw (2 x 6: S, C_1..3, su_1, su_2 of the cut K, then of K - 16), acc (the 4 + d accumulators), chk, taps."""
+    lib = load_library()
+    M = np.ascontiguousarray(M, dtype=np.float64); s = np.ascontiguousarray(s, dtype=np.float64)
+    theta = np.ascontiguousarray(theta, dtype=np.float64)
+    if d is None:
+        d = theta.size - 3
+    given = taps is not None
+    tp = np.ascontiguousarray(taps, dtype=np.float64).copy() if given else np.zeros((2, M.shape[0]))
+    if tp.shape != (2, M.shape[0]) or s.shape != (2, M.shape[0]) or theta.size != d + 3:
+        raise ValueError("lagforms_host: shapes")
+    p0a = None if p0 is None else np.ascontiguousarray(p0, dtype=np.float64)
+    raw = np.zeros((2, 6)); acc = np.zeros(4 + d); chk = np.zeros(1)
+    st = lib.ssde_lagforms_host(M.ctypes.data_as(_dp), s.ctypes.data_as(_dp), float(n_bulk), d, theta.ctypes.data_as(_dp), float(dt),
+                                None if p0a is None else p0a.ctypes.data_as(_dp), int(K), int(mask), 1 if given else 0,
+                                tp.ctypes.data_as(_dp), raw.ctypes.data_as(_dp), acc.ctypes.data_as(_dp), chk.ctypes.data_as(_dp))
+    if st != 0:
+        raise ValueError(f"ssde_lagforms_host: status {st}")
+    return {"raw": raw, "acc": acc, "chk": float(chk[0]), "taps": tp}
 
 
 COMM_ID_BYTES = 128

@@ -819,6 +819,10 @@ __global__ __launch_bounds__(256) void iso_finalize_kernel(const IsoArgs A, cons
             const unsigned long long v = atomicExch((unsigned long long*)A.quiet_flag, 0ull);
             if (v) dep = atomicMax((unsigned long long*)A.chk_out, v);
         }
+        if ((int)blockIdx.x == n_check && threadIdx.x == 0 && R.lag_part > 0 && lag_chk_bits(R.lag_chk)) {
+            // the difference between the two cuts of the bulk's forms (ssde_lagforms.hpp, by value)
+            dep ^= atomicMax((unsigned long long*)A.chk_out, lag_chk_bits(R.lag_chk));
+        }
         publish_if_last(R, reduce_slot(R, blockIdx.x - n_check, sh) ^ dep);      // (the count depends on BOTH atomics' return values)
     }
 }

@@ -1,9 +1,8 @@
-// k_lagstats.hip -- the lag statistics of a stationary batch (ssde_create, once) and the bulk forms built from them (every
-// evaluation that takes that path).  Derivation and layout: ssde_lagstats.hpp, DESIGN.md §3.3d.  Every sum runs in a fixed
-// order: two creates of the same data give bitwise-equal statistics, two evaluations at the same theta bitwise-equal forms.
+// k_lagstats.hip -- the lag statistics of a stationary batch (ssde_create, once).  The bulk forms built from them at every
+// evaluation that takes that path run on the host (ssde_lagforms.hpp).  Derivation and layout: ssde_lagstats.hpp, DESIGN.md
+// §3.3d.  Every sum runs in a fixed order: two creates of the same data give bitwise-equal statistics.
 #include "ssde_device.hpp"
 #include "ssde_lagstats.hpp"
-#include "ssde_tf.hpp"
 
 namespace ssde {
 
@@ -133,92 +132,6 @@ __global__ __launch_bounds__(256) void lag_group_sum_kernel(const double* src, i
     dst[e] = s;
 }
 
-// The bulk's forms at one theta: v = M lam (and the same for the check's shorter cut), then per tap row i its share of S, C_1..3
-// and su_a (the mu dt terms through s and n), summed over the rows by a fixed tree and turned into the accumulators
-// tf_finish forms (ssde_tf.hpp, as TfCtcrw::finish) -- written as window `chunk` of group 0 of the partial sums (every other group of that window: zero).
-constexpr int LF_THREADS = 4 * LAG_N;
-__global__ __launch_bounds__(LF_THREADS) void lag_forms_kernel(const LagFormArgs A) {
-    __shared__ double sv[2][4][LAG_N];
-    __shared__ double red[12][256];
-    const int tid = threadIdx.x;
-    {
-        const int r = tid % LAG_N, qq = tid / LAG_N, k0 = qq * (LAG_N / 4);
-        double v = 0.0, vc = 0.0;
-        // (fully unrolled this loop measured 32 against 14 us per launch on the headline batch)
-        for (int k = k0; k < k0 + LAG_N / 4; k++) {
-            const double m = A.M[(int64_t)k * LAG_N + r];       // (symmetric: column r, coalesced)
-            const double lk = k <= A.K ? A.lam[k] : 0.0;
-            v = fma(m, lk, v);
-            vc = fma(m, k <= A.Kc ? lk : 0.0, vc);
-        }
-        sv[0][qq][r] = v; sv[1][qq][r] = vc;
-    }
-    __syncthreads();
-    if (tid < 256) {
-        double x[2][6];
-        for (int c = 0; c < 2; c++)
-            for (int j = 0; j < 6; j++) x[c][j] = 0.0;
-        const int i = tid;
-        if (i < LAG_N) {
-            for (int c = 0; c < 2; c++) {
-                const int K = c ? A.Kc : A.K;
-                const double V = (sv[c][0][i] + sv[c][1][i]) + (sv[c][2][i] + sv[c][3][i]);
-                const double li = i <= K ? A.lam[i] : 0.0, Lam = A.sum_lam[c];
-                double rho[3];
-                for (int k = 0; k < 3; k++) rho[k] = (i >= k + 1 && i <= K) ? A.rr[i - k - 1] : 0.0;
-                double S = li * V, Ck[3] = {rho[0] * V, rho[1] * V, rho[2] * V};
-                for (int a = 0; a < A.d; a++) {
-                    const double sa = A.s[a * LAG_N + i], cm = A.cm[a];
-                    S -= 2.0 * Lam * cm * li * sa;
-                    for (int k = 0; k < 3; k++) Ck[k] -= cm * (Lam * rho[k] * sa + A.sum_rho[c][k] * li * sa);
-                    double su = li * sa;
-                    if (i == 0) {
-                        S += A.n * cm * cm * Lam * Lam;
-                        for (int k = 0; k < 3; k++) Ck[k] += A.n * cm * cm * Lam * A.sum_rho[c][k];
-                        su -= A.n * cm * Lam;
-                    }
-                    x[c][4 + a] = su;
-                }
-                x[c][0] = S; x[c][1] = Ck[0]; x[c][2] = Ck[1]; x[c][3] = Ck[2];
-            }
-        }
-        for (int c = 0; c < 2; c++)
-            for (int j = 0; j < 6; j++) red[c * 6 + j][tid] = x[c][j];
-    }
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o)
-            for (int j = 0; j < 12; j++) red[j][tid] += red[j][tid + o];
-        __syncthreads();
-    }
-    const int NACC = 4 + A.d, G = A.n_groups;
-    auto at = [&](int g, int k) -> int64_t {
-        return A.kfast ? ((int64_t)A.chunk * G + g) * NACC + k : ((int64_t)A.chunk * NACC + k) * G + g;
-    };
-    for (int e = tid; e < G * NACC; e += LF_THREADS) {
-        const int g = e / NACC, k = e % NACC;
-        if (g != 0) A.partials[at(g, k)] = 0.0;
-    }
-    if (tid == 0) {
-        double out[NACC_MAX];
-        const double su[2] = {red[4][0], red[5][0]};
-        tf_finish(A.statc, A.d, A.mask, red[0][0], red[1][0], red[2][0], red[3][0], su, out);     // (what the streaming lanes finish with)
-        for (int k = 0; k < NACC; k++) A.partials[at(0, k)] = out[k];
-        // the check: every raw sum of the two cuts, relative to itself or to sqrt(S n) (the size of a sum of n products of u with a
-        // unit-scale signal), whichever is larger
-        const double floor_ = sqrt(fabs(red[0][0]) * A.n);
-        double w = 0.0;
-        for (int j = 0; j < 4 + A.d; j++) {
-            const double a = red[j][0], b = red[6 + j][0];
-            const double sc = fmax(fmax(fabs(a), fabs(b)), floor_);
-            const double r = fabs(a - b) / sc;
-            w = (r == r) ? fmax(w, r) : INFINITY;
-        }
-        if (!(w == w)) w = INFINITY;
-        if (w > 0.0) atomicMax((unsigned long long*)A.chk, (unsigned long long)__double_as_longlong(w));
-    }
-}
-
 }  // namespace
 
 hipError_t launch_lagstats(const TileView& tv, int d, double* Qg, double* Dg, double* sg, double* Q, double* D, double* s, hipStream_t st) {
@@ -232,11 +145,6 @@ hipError_t launch_lagstats(const TileView& tv, int d, double* Qg, double* Dg, do
     sum(Qg, LAG_N, Q);
     sum(Dg, (int64_t)LAG_N * LAG_N, D);
     sum(sg, 2 * LAG_N, s);
-    return hipGetLastError();
-}
-
-hipError_t launch_lag_forms(const LagFormArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(lag_forms_kernel, dim3(1), dim3(LF_THREADS), 0, s, a);
     return hipGetLastError();
 }
 

@@ -292,8 +292,6 @@ hipError_t launch_iso_finalize(int model, int d, const IsoArgs& a, const ReduceA
 // lag statistics of a stationary batch (k_lagstats.hip, ssde_lagstats.hpp): per-group Toeplitz sums Qg [G][LAG_N], end corrections
 // Dg [G][LAG_N][LAG_N] and s [G][2][LAG_N], and their fixed-order sums over the groups into Q, D, s
 hipError_t launch_lagstats(const TileView& tv, int d, double* Qg, double* Dg, double* sg, double* Q, double* D, double* s, hipStream_t st);
-struct LagFormArgs;
-hipError_t launch_lag_forms(const LagFormArgs& a, hipStream_t s);
 void fill_stat_consts(int model, int d, IsoArgs& a);
 int iso_nstate(int model, int d);
 
@@ -325,7 +323,15 @@ struct ReduceArgs {
     unsigned long long pub_seq;
     unsigned int* pub_count;      // device, zero between launches: workgroups of this launch that have finished
     int pub_blocks;               // workgroups of this launch
+    // The bulk of a stationary batch from the lag statistics (ssde_lagforms.hpp, computed on the host): one more window of direction
+    // part 0, of which only group 0 is not zero, passed BY VALUE.  lag_part = that window's index (the windows that live in
+    // `partials` come before it), 0 = none.  The sums take lag_acc as entry lag_part * n_blocks of their fixed order; lag_chk (the
+    // difference between the forms' two cuts) is folded into out[n_out] by max.
+    int lag_part;
+    double lag_acc[NACC_MAX];
+    double lag_chk;
 };
+static_assert(sizeof(IsoArgs) + sizeof(ReduceArgs) <= 4096, "iso_shared_kernel and iso_finalize_kernel take both by value: the 4 KB argument block");
 hipError_t launch_reduce(const ReduceArgs& a, hipStream_t s);
 
 // ---- ingest (k_ingest.hip): long format -> tiles ------------------------------------------------
@@ -768,13 +774,17 @@ __device__ __forceinline__ unsigned long long reduce_slot(const ReduceArgs& A, i
     auto sum_run = [&](int p0, int k, int chunks) {
         const double* base = A.kfast ? A.partials + (int64_t)p0 * stride + k : A.partials + ((int64_t)p0 * A.nacc + k) * A.n_blocks;
         const int total = chunks * A.n_blocks;
-        for (int i0 = tid; i0 < total; i0 += 4 * 256) {
+        // (the bulk's forms: the entry after the run's last one -- group 0 of the window that follows it)
+        const bool lag = A.lag_part > 0 && p0 + chunks == A.lag_part;
+        const double lag_v = lag ? A.lag_acc[k] : 0.0;
+        const int total_x = total + (lag ? 1 : 0);
+        for (int i0 = tid; i0 < total_x; i0 += 4 * 256) {
             double v[4];
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 const int i = i0 + u * 256;
                 const int c = i / A.n_blocks, b = i - c * A.n_blocks;
-                v[u] = i < total ? (A.kfast ? base[(int64_t)i * A.nacc] : base[c * stride + b]) : 0.0;
+                v[u] = i < total ? (A.kfast ? base[(int64_t)i * A.nacc] : base[c * stride + b]) : i == total ? lag_v : 0.0;
             }
             acc += (v[0] + v[1]) + (v[2] + v[3]);
         }
@@ -815,6 +825,11 @@ __device__ __forceinline__ unsigned long long reduce_slot(const ReduceArgs& A, i
 __device__ __forceinline__ void dev_store(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ double dev_load(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void dev_stores_done() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+
+// the forms' check value as the word the checks are raised with (not a number: infinity)
+__device__ __forceinline__ unsigned long long lag_chk_bits(double w) {
+    return (unsigned long long)__double_as_longlong(w == w ? fabs(w) : INFINITY);
+}
 
 __device__ __forceinline__ double window_check_wave(const IsoArgs& A, int nstate, int g, int c) {
     const int lane = threadIdx.x & 63;
@@ -861,17 +876,19 @@ __device__ __forceinline__ void reduce_all_wave(const ReduceArgs& A, double (&r)
 #pragma unroll
     for (int k = 0; k < NACC; k++) acc[k][0] = acc[k][1] = acc[k][2] = acc[k][3] = 0.0;
     const int total = A.n_value_parts * A.n_blocks;
+    const bool lag = A.lag_part > 0 && A.n_value_parts == A.lag_part;      // (the bulk's forms: the entry after the last one, as reduce_slot)
+    const int total_x = total + (lag ? 1 : 0);
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         const int tid = lane + 64 * j;
-        for (int i0 = tid; i0 < total; i0 += 4 * 256) {
+        for (int i0 = tid; i0 < total_x; i0 += 4 * 256) {
             double v[4][NACC];
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 const int i = i0 + u * 256;
                 const double* e = A.partials + (int64_t)(i < total ? i : 0) * NACC;
 #pragma unroll
-                for (int k = 0; k < NACC; k++) v[u][k] = i < total ? e[k] : 0.0;
+                for (int k = 0; k < NACC; k++) v[u][k] = i < total ? e[k] : (lag && i == total) ? A.lag_acc[k] : 0.0;
             }
 #pragma unroll
             for (int k = 0; k < NACC; k++) acc[k][j] += (v[0][k] + v[1][k]) + (v[2][k] + v[3][k]);
@@ -929,7 +946,8 @@ __device__ __forceinline__ void fused_finalize_wave(const IsoArgs& A, const Redu
             dev_store(&R.out[slot], v);
         }
         // the check word has a slot of its own (nobody zeroes out[] between launches): moved, and cleared for the next launch
-        const unsigned long long w = __hip_atomic_exchange((unsigned long long*)A.chk_out, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        unsigned long long w = __hip_atomic_exchange((unsigned long long*)A.chk_out, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (R.lag_part > 0) w = max(w, lag_chk_bits(R.lag_chk));    // (non-negative doubles order like their bit patterns)
         dev_store(&R.out[R.n_out], __longlong_as_double((long long)w));
         __hip_atomic_store(A.fuse_done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }

@@ -296,7 +296,7 @@ struct ssde_handle {
     bool lag_ready = false;
     DevBuf<double> lag_M, lag_s;           // [LAG_N][LAG_N], [2][LAG_N]
     DevBuf<int32_t> lag_glen, lag_ns;      // group_len / lane_nsteps capped at LAG_A: what the streamed head launch walks
-    DevBuf<double> lag_flag;               // the bulk's check value (one word, zero between launches; the finalize launch folds it in)
+    std::vector<double> lag_M_host, lag_s_host;   // the same on the host: what an evaluation's forms read (ssde_lagforms.hpp)
     double lag_n = 0.0;                    // bulk rows (past LAG_A) of the batch
     int64_t lag_rows = 0, last_lag_rows = 0;   // ... and those the last evaluation took from the statistics (0: streamed)
     double lag_create_ms = 0.0;            // what building them cost at create

@@ -129,11 +129,13 @@ namespace ssde_engine {
 constexpr int SSDE_RETRY_WITHOUT_DRIFT = -77;     // internal: the drift layout was tried and the data do not qualify
 constexpr int SSDE_RETRY_WITHOUT_PP = -78;        // internal: the drift's blocks were tiled as covariates and the lanes that would read them are the general ones
 // The lag statistics of a stationary batch (ssde_lagstats.hpp): CTCRW on the shared-covariance path, every group
-// complete, regular grid, no drift.  The rule is the measured crossover (profiles/r06_c_lagstats_crossover.txt: bench.py both ways
-// at 7e6 - 2e7 bulk rows): an evaluation on the path costs ~0.07 ms whatever the batch (the head launch's ~256-row critical path,
-// the forms' launch, the fixed costs), the streamed one grows with the rows; the two meet at 1.2 - 1.4e7 rows past LAG_A (7.4e6:
-// 0.072 against 0.067 ms, 1.24e7: 0.072 / 0.077, 1.74e7: 0.072 / 0.096).  Built from LAG_MIN_BULK_ROWS, above every crossover seen.
-constexpr double LAG_MIN_BULK_ROWS = 1.6e7;
+// complete, regular grid, no drift.  An evaluation on the path costs ~0.055 ms whatever the batch (the head launch's ~256-row critical
+// path, the finalize launch, the fixed costs; the forms run on the host while the head runs); the streamed one grows with the rows.
+// profiles/r07_c_lagstats_crossover.txt (bench.py both ways, SSDE_LAGSTATS=0 against =2, 1.4e6 - 2.7e7 bulk rows, two repetitions):
+// streaming wins or ties at NONE of the sizes -- 1.43e6: 0.058 against 0.055-0.056 ms, 4.43e6: 0.063 / 0.057-0.058, 7.4e6: 0.067-0.069 /
+// 0.056, 1.24e7: 0.076-0.078 / 0.056-0.059.  The crossover lies below what was measured, so the rule sits at its floor: above the 4.3e6
+// below which the tests expect nothing built, 3 x the smallest size at which the path already won.
+constexpr double LAG_MIN_BULK_ROWS = 4.4e6;
 static int build_lagstats(ssde_handle* h, int G, const std::vector<int32_t>& lane_ns, const std::vector<int32_t>& glen) {
     if (h->knobs.lagstats == 0) return SSDE_OK;
     if (!(h->model == SSDE_MODEL_CTCRW && h->use_shared && !h->drift && h->n_clean_groups == G && h->uniform_dt && h->iso_parts == 1 &&
@@ -162,15 +164,15 @@ static int build_lagstats(ssde_handle* h, int G, const std::vector<int32_t>& lan
     HIPCHK(h, hipMemcpy(host.data(), sums.p, host.size() * 8, hipMemcpyDeviceToHost));
     Qg.release(); Dg.release(); sg.release(); sums.release();
     lag_assemble(host.data(), host.data() + LAG_N, M.data());
-    HIPCHK(h, h->lag_M.upload(M));
-    HIPCHK(h, h->lag_s.upload(std::vector<double>(host.begin() + LAG_N + NN, host.end())));
+    h->lag_s_host.assign(host.begin() + LAG_N + NN, host.end());
+    HIPCHK(h, h->lag_M.upload(M));                     // (the device copies: ssde_lagstats_read)
+    HIPCHK(h, h->lag_s.upload(h->lag_s_host));
+    h->lag_M_host = std::move(M);
     std::vector<int32_t> cg(glen.begin(), glen.end()), cn(lane_ns.begin(), lane_ns.end());
     for (auto& v : cg) v = std::min(v, (int32_t)LAG_A);
     for (auto& v : cn) v = std::min(v, (int32_t)LAG_A);
     HIPCHK(h, h->lag_glen.upload(cg));
     HIPCHK(h, h->lag_ns.upload(cn));
-    HIPCHK(h, h->lag_flag.alloc(1));
-    HIPCHK(h, hipMemset(h->lag_flag.p, 0, 8));
     HIPCHK(h, hipDeviceSynchronize());
     h->lag_rows = bulk;
     h->lag_n = (double)bulk;

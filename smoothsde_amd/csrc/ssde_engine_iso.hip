@@ -2,6 +2,7 @@
 // window plan, the gain table of the shared-covariance kernels, the launches (shared / general / drift / mixed batch) and
 // the finalising launch (hand-over checks + fixed-order sums).  Called from eval_device (ssde_engine.hip).
 #include "ssde_engine.hpp"
+#include "ssde_lagforms.hpp"
 #include "ssde_tf.hpp"
 
 #include <chrono>
@@ -133,6 +134,18 @@ void plan_windows(ssde_handle* h, const IsoArgs& a, int* n_chunks, int* window) 
 // for the regular grid -- it does not depend on the observations -- until it is bitwise
 // stationary, upload the gains, and return the data-independent likelihood terms
 // (D/2 sum log F and its derivatives, weighted by how many tracks reach each row).
+// Stationarity test of the covariance recursion, shared by the gain table and ssde_lagforms_host.  In floating point the recursion
+// ends in a last-bit limit cycle rather than a bitwise fixed point, so "settled" = every component moved by less than 2e-15
+// relative; GAIN_SETTLED_ROWS such rows in a row end the recursion.
+constexpr int GAIN_SETTLED_ROWS = 4;
+inline bool gain_close(double a, double b) { return std::fabs(a - b) <= 2e-15 * (std::fabs(a) + std::fabs(b)) + 1e-300; }
+inline bool ctcrw_cov_settled(const CtcrwCov<15>& C, const CtcrwCov<15>& prev) {
+    bool same = gain_close(C.p11, prev.p11) && gain_close(C.p12, prev.p12) && gain_close(C.p22, prev.p22);
+    for (int j = 0; j < NDIRP && same; j++)
+        same = gain_close(C.d11[j], prev.d11[j]) && gain_close(C.d12[j], prev.d12[j]) && gain_close(C.d22[j], prev.d22[j]);
+    return same;
+}
+
 template <int D>
 int build_gain_table(ssde_handle* h, IsoArgs& a, int mask, hipStream_t s, double add[4]) {
     const int slot = h->par_next;
@@ -153,7 +166,7 @@ int build_gain_table(ssde_handle* h, IsoArgs& a, int mask, hipStream_t s, double
     // bitwise fixed point, so "stationary" = every component moved by less than 2e-15 relative for 4 rows
     // in a row; the row reached then is used for all later rows (a 1e-15 relative perturbation of gains
     // that themselves carry rounding errors of that size).
-    auto close = [](double a, double b) { return std::fabs(a - b) <= 2e-15 * (std::fabs(a) + std::fabs(b)) + 1e-300; };
+    auto close = gain_close;
     if (h->model == SSDE_MODEL_CTCRW) {
         CtcrwCov<15> C;
         C.init(a.p0[0], a.p0[1], a.p0[2]);
@@ -171,11 +184,8 @@ int build_gain_table(ssde_handle* h, IsoArgs& a, int mask, hipStream_t s, double
             cum_ld.push_back(ld);
             for (int j = 0; j < NDIRP; j++) cum_g[j].push_back(C.gld[j]);
             last = t;
-            bool same = close(C.p11, prev.p11) && close(C.p12, prev.p12) && close(C.p22, prev.p22);
-            for (int j = 0; j < NDIRP && same; j++)
-                same = close(C.d11[j], prev.d11[j]) && close(C.d12[j], prev.d12[j]) && close(C.d22[j], prev.d22[j]);
-            stable = same ? stable + 1 : 0;
-            if (stable >= 4) break;
+            stable = ctcrw_cov_settled(C, prev) ? stable + 1 : 0;
+            if (stable >= GAIN_SETTLED_ROWS) break;
         }
         h->stat_p[0] = C.p11; h->stat_p[1] = C.p12; h->stat_p[2] = C.p22;
         for (int j = 0; j < NDIRP; j++) { h->stat_p[3 + 3 * j] = C.d11[j]; h->stat_p[4 + 3 * j] = C.d12[j]; h->stat_p[5 + 3 * j] = C.d22[j]; }
@@ -200,7 +210,7 @@ int build_gain_table(ssde_handle* h, IsoArgs& a, int mask, hipStream_t s, double
             bool same = close(C.p, prev.p);
             for (int j = 0; j < NDIRP && same; j++) same = close(C.dp[j], prev.dp[j]);
             stable = same ? stable + 1 : 0;
-            if (stable >= 4) break;
+            if (stable >= GAIN_SETTLED_ROWS) break;
         }
         for (int i = 0; i < 12; i++) h->stat_p[i] = 0.0;
         h->stat_p[0] = C.p;
@@ -209,7 +219,7 @@ int build_gain_table(ssde_handle* h, IsoArgs& a, int mask, hipStream_t s, double
     const int rows = last + 1;
     h->last_gain_rows = rows;
     // (quiet rows of the general kernel: the covariance after the last row, and what a further row adds to sum log F / sum dF / F)
-    h->gain_stationary = stable >= 4 && last >= 1;
+    h->gain_stationary = stable >= GAIN_SETTLED_ROWS && last >= 1;
     if (last >= 1) {
         h->stat_ld = cum_ld[last] - cum_ld[last - 1];
         for (int j = 0; j < NDIRP; j++) h->stat_gld[j] = cum_g[j][last] - cum_g[j][last - 1];
@@ -239,36 +249,46 @@ int build_gain_table(ssde_handle* h, IsoArgs& a, int mask, hipStream_t s, double
     return SSDE_OK;
 }
 
-// The bulk's forms at this evaluation (ssde_lagstats.hpp): the taps are the impulse responses of the lanes' own stationary step
+// The bulk's forms at this evaluation (ssde_lagforms.hpp): the taps are the impulse responses of the lanes' own stationary step
 // (TfCtcrw::step_stat, ssde_tf.hpp, here on the host) to a unit increment -- u for lam, r for rr -- and the constants those lanes
-// finish with.  K taps for the forms, K - LAG_CHECK for the check.
-void lag_form_args(ssde_handle* h, const IsoArgs& a, int order, int K, LagFormArgs& f) {
+// finish with.  K taps for the forms, K - LAG_CHECK for the check.  (M, s, n: the caller's)
+void lag_form_taps(const IsoArgs& a, int d, int mask, int K, LagFormArgs& f) {
     TfCtcrw<1, DIR_SIG | DIR_MU> T;
     T.setup(a);
     T.cm[0] = 0.0;                              // (the mu dt terms enter through s and n)
     double y = 0.0;
     T.init(&y);
     y = 1.0;                                    // dy_0 = 1, then 0
-    for (int t = 0; t < LAG_N; t++) {
+    for (int t = 0; t < LAG_N; t++) f.lam[t] = f.rr[t] = 0.0;
+    for (int t = 0; t <= K && t < LAG_N; t++) {         // (taps beyond the cut are zero: nothing reads them)
         T.reset_acc();
         T.step_stat(&y);
-        f.lam[t] = t <= K ? T.su[0] : 0.0;
-        f.rr[t] = t <= K ? T.r1[0] : 0.0;
+        f.lam[t] = T.su[0];
+        f.rr[t] = T.r1[0];
     }
-    f.M = h->lag_M.p; f.s = h->lag_s.p; f.n = h->lag_n;
-    f.K = K; f.Kc = K - LAG_CHECK; f.d = h->d; f.mask = order >= 1 ? a.part_mask[0] : 0;
-    for (int c = 0; c < 2; c++) {
-        const int k = c ? f.Kc : f.K;
-        double sl = 0.0, sr[3] = {0.0, 0.0, 0.0};
-        for (int i = 0; i <= k; i++) sl += f.lam[i];
-        for (int j = 0; j < 3; j++)
-            for (int i = j + 1; i <= k; i++) sr[j] += f.rr[i - j - 1];
-        f.sum_lam[c] = sl;
-        for (int j = 0; j < 3; j++) f.sum_rho[c][j] = sr[j];
-    }
-    for (int i = 0; i < 2; i++) f.cm[i] = i < h->d ? a.statc[29 + i] : 0.0;
+    f.K = K; f.Kc = K - LAG_CHECK; f.d = d; f.mask = mask;
+    lag_tap_sums(f);
+    for (int i = 0; i < 2; i++) f.cm[i] = i < d ? a.statc[29 + i] : 0.0;
     for (int i = 0; i < 48; i++) f.statc[i] = a.statc[i];
-    f.n_groups = h->n_groups;
+}
+
+// ... and their result into the reducing launch's arguments, as the window after the `n_windows` that live in the partial sums
+int lag_forms_into(ssde_handle* h, const IsoArgs& a, int order, int K, int n_windows, ReduceArgs& ra) {
+    // the reductions recognise the by-value window as the one after the windows of direction part 0 (reduce_slot, reduce_all_wave):
+    // one part, one plan, and the sums run over exactly the windows that live in the partial sums
+    if (a.n_parts != 1 || a.dual || ra.n_value_parts != n_windows || ra.chunks_per_part != n_windows || ra.n_parts != n_windows) {
+        h->err = "lag statistics: the reduction's windows do not match the head's plan";
+        return SSDE_ERR_ARG;
+    }
+    LagFormArgs f;
+    LagFormOut o;
+    lag_form_taps(a, h->d, order >= 1 ? a.part_mask[0] : 0, K, f);
+    f.M = h->lag_M_host.data(); f.s = h->lag_s_host.data(); f.n = h->lag_n;
+    lag_forms_host(f, o);
+    ra.lag_part = n_windows;
+    for (int k = 0; k < NACC_MAX; k++) ra.lag_acc[k] = o.acc[k];
+    ra.lag_chk = o.chk;
+    return SSDE_OK;
 }
 
 }  // namespace
@@ -489,8 +509,7 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
         ra.n_parts = a.n_parts * ncr; ra.nacc = nacc; ra.n_blocks = h->n_groups;
         ra.n_value_parts = ncr; ra.chunks_per_part = ncr;
         ra.chk = h->chk.p; ra.n_chk = a.n_chunks > 1 ? a.n_parts * (a.n_chunks - 1) * h->n_groups : 0;
-        // the bulk's forms: one more window of the partial sums (group 0; lag_forms_kernel), summed with the others in the same order
-        if (lag_K > 0) { ra.n_parts += 1; ra.n_value_parts += 1; ra.chunks_per_part += 1; }
+        // (the bulk's forms are one more window, by value: lag_forms_into)
         if (order >= 1 && h->cv_adj) {
             // accumulators of k_iso_adj.hip: [value | log sigma_obs | mu_a | par[d] | par[d + 1] | per streamed column: par[d], par[d + 1] (, mu_a)]
             const int nkp = h->model == SSDE_MODEL_BM_SSM ? 1 : 2, nk = adj_nk(h->model, h->d, a.cv_mu_cols != 0);
@@ -559,7 +578,6 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
                 HIPCHK(h, hipMemsetAsync(h->partials.p, 0, (size_t)std::max(a.n_chunks, ad.n_chunks) * (4 + h->d) * h->n_groups * 8, s));
             }
         }
-        if (lag_K > 0 && !fused) a.quiet_flag = h->lag_flag.p;     // (the finalize launch folds the bulk's check into out[n_out])
         IsoArgs b = a;
         b.group_mode = 2;
         if (h->knobs.wave_clock) {
@@ -590,15 +608,9 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
                 b.fuse_arrive = h->fuse_words.p + 4; b.fuse_done = h->fuse_words.p;
                 b.chk_out = (double*)(h->fuse_words.p + 2);         // (its own word, zero between launches: the last wave moves it to out[n_out])
             }
-            if (lag_K > 0) {
-                // the forms first: their partial sums and check are in place before the head's reduction runs (either form)
-                LagFormArgs f;
-                memset(&f, 0, sizeof(f));
-                lag_form_args(h, a, order, lag_K, f);
-                f.partials = h->partials.p; f.chunk = a.n_chunks; f.kfast = fused ? 1 : 0;
-                f.chk = fused ? b.chk_out : h->lag_flag.p;
-                HIPCHK(h, launch_lag_forms(f, s));
-            }
+            // the bulk's forms, on the host: the single launch of the fused form needs them; the two-launch form computes them
+            // while the head runs (below), for its finalize launch
+            if (lag_K > 0 && fused) { const int st = lag_forms_into(h, a, order, lag_K, a.n_chunks, ra); if (st) return st; }
             HIPCHK(h, launch_iso_shared(h->model, h->d, b, ra, s, h->stamps ? h->ev_k0 : nullptr, h->stamps ? h->ev_k1 : nullptr));
         }
         h->last_kernel_id = h->drift ? SSDE_KERNEL_ISO_DRIFT : any_dirty ? SSDE_KERNEL_ISO_MIXED : SSDE_KERNEL_ISO_SHARED;
@@ -655,6 +667,7 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
     }
     if (h->knobs.trace) { const double t = tick(); h->trace_us[2] += t - tk0; tk0 = t; }
     if (!fused) fill_ra();
+    if (!fused && lag_K > 0) { const int st = lag_forms_into(h, a, order, lag_K, a.n_chunks, ra); if (st) return st; }     // (the head is running: this overlaps it)
     // the hand-over checks and the final sums in one launch (unless the main launch has done them)
     if (!fused) HIPCHK(h, launch_iso_finalize(h->model, h->d, a, ra, s));
     h->last_fused = fused;
@@ -670,3 +683,50 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
 }
 
 }  // namespace ssde_engine
+
+extern "C" int ssde_lagforms_host(const double* M, const double* s, double n_bulk, int32_t d, const double* theta, double dt,
+                                  const double* p0, int32_t K, int32_t mask, int32_t taps_given, double* taps, double* raw,
+                                  double* acc, double* chk) {
+    if (!M || !s || !theta || !taps || !raw || !acc || !chk || d < 1 || d > 2) return SSDE_ERR_ARG;
+    if (K < LAG_CHECK || K > LAG_KMAX || !(dt > 0.0) || !std::isfinite(dt)) return SSDE_ERR_ARG;
+    IsoArgs a;
+    memset(&a, 0, sizeof(a));
+    const double sig = exp(theta[0]);
+    a.h = sig * sig;
+    for (int i = 0; i < d; i++) a.mu[i] = theta[1 + i];
+    a.tau = exp(theta[1 + d]);
+    const double nu = exp(theta[2 + d]);
+    a.beta = 1.0 / a.tau;
+    a.sigma = 2.0 * nu / sqrt(M_PI * a.tau);
+    ctcrw_trans(dt, a.tau, a.beta, a.sigma, a.ctr);
+    // the stationary gains: the covariance half of the filter until it has stopped moving (as build_gain_table)
+    CtcrwCov<15> C;
+    if (p0) C.init(p0[0], p0[1], p0[2]); else C.init(1.0, 0.0, 1.0);
+    CtcrwGain G;
+    int stable = 0;
+    for (int t = 0; t < 100000 && stable < GAIN_SETTLED_ROWS; t++) {
+        const CtcrwCov<15> prev = C;
+        if (d == 1) ctcrw_cov_step<1, 15>(C, a.ctr, a.h, false, G); else ctcrw_cov_step<2, 15>(C, a.ctr, a.h, false, G);
+        stable = ctcrw_cov_settled(C, prev) ? stable + 1 : 0;
+    }
+    if (stable < GAIN_SETTLED_ROWS || G.iF == 0.0) return SSDE_ERR_ARG;      // (no stationary regime: such an evaluation streams every row)
+    a.gain_stat[0] = G.iF; a.gain_stat[1] = G.k1; a.gain_stat[2] = G.k2; a.gain_stat[3] = G.bm;
+    for (int j = 0; j < NDIRP; j++) { a.gain_stat[4 + j] = G.diF[j]; a.gain_stat[7 + j] = G.dk1[j]; a.gain_stat[10 + j] = G.dk2[j]; }
+    fill_stat_consts(SSDE_MODEL_CTCRW, d, a);
+    LagFormArgs f;
+    LagFormOut o;
+    lag_form_taps(a, d, mask < 0 ? (DIR_SIG | DIR_MU | DIR_P1 | DIR_P2) : mask, K, f);
+    if (taps_given) {                                       // the caller's taps, as they are (nothing beyond the cut is read)
+        for (int i = 0; i < LAG_N; i++) { f.lam[i] = taps[i]; f.rr[i] = taps[LAG_N + i]; }
+        lag_tap_sums(f);
+    } else {
+        for (int i = 0; i < LAG_N; i++) { taps[i] = f.lam[i]; taps[LAG_N + i] = f.rr[i]; }
+    }
+    f.M = M; f.s = s; f.n = n_bulk;
+    lag_forms_host(f, o);
+    for (int c = 0; c < 2; c++)
+        for (int j = 0; j < LAG_NRAW; j++) raw[c * LAG_NRAW + j] = o.raw[c][j];
+    for (int k = 0; k < 4 + d; k++) acc[k] = o.acc[k];
+    *chk = o.chk;
+    return SSDE_OK;
+}

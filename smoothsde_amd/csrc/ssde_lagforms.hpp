@@ -1,0 +1,120 @@
+// ssde_lagforms.hpp -- the bulk's forms at one theta, on the host (the statistics: ssde_lagstats.hpp).
+//
+// v = M lam (and the same for the check's shorter cut), then per tap row i its share of S, C_1..3 and su_a (the mu dt terms
+// through s and n), summed over the rows by a fixed tree and turned into the accumulators tf_finish forms (ssde_tf.hpp, as
+// TfCtcrw::finish).  The result goes BY VALUE into the reducing launch (ReduceArgs.lag_acc, ssde_device.hpp): nothing of it lives
+// in device memory.  Taps beyond the cut are exact zeros, so the loops stop at K (Kc): ~(K + 1)^2 products per cut.
+#pragma once
+#include "ssde_lagstats.hpp"
+#include "ssde_tf.hpp"
+
+#include <cmath>
+
+namespace ssde {
+
+constexpr int LAG_NRAW = 6;           // raw sums of a cut: S, C_1, C_2, C_3, su_1, su_2
+
+struct LagFormArgs {
+    const double* M;                  // [LAG_N][LAG_N] (host)
+    const double* s;                  // [2][LAG_N] (host)
+    double n;                         // bulk rows
+    int K, Kc;                        // taps 0..K of the forms, 0..Kc of the check
+    int d, mask;                      // response coordinates, DIR_* bits of the evaluation
+    double lam[LAG_N];                // impulse response of u
+    double rr[LAG_N];                 // impulse response of r (r_{t-k}: rr shifted by k)
+    double sum_lam[2], sum_rho[2][3]; // sums of the taps 0..K (index 0) and 0..Kc (index 1)
+    double cm[2];                     // mu_a dt
+    double statc[48];                 // the stationary constants (IsoArgs.statc): tf_finish forms the accumulators from them
+};
+
+struct LagFormOut {
+    double raw[2][LAG_NRAW];          // the raw sums of the cut K (index 0) and of the check's cut Kc (index 1)
+    double acc[NACC_MAX];             // the 4 + d accumulators of the cut K
+    double chk;                       // the largest relative difference between the two cuts
+};
+
+// sums of the taps of both cuts, as the forms use them (f.lam, f.rr, f.K, f.Kc set)
+inline void lag_tap_sums(LagFormArgs& f) {
+    for (int c = 0; c < 2; c++) {
+        const int k = c ? f.Kc : f.K;
+        double sl = 0.0, sr[3] = {0.0, 0.0, 0.0};
+        for (int i = 0; i <= k; i++) sl += f.lam[i];
+        for (int j = 0; j < 3; j++)
+            for (int i = j + 1; i <= k; i++) sr[j] += f.rr[i - j - 1];
+        f.sum_lam[c] = sl;
+        for (int j = 0; j < 3; j++) f.sum_rho[c][j] = sr[j];
+    }
+}
+
+#if defined(__clang__)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wpass-failed"     // (tf_finish asks for loops unrolled that have a run-time bound here)
+#endif
+// Fixed order: per row four partial sums over the blocks of LAG_N / 4 taps, combined as (q0 + q1) + (q2 + q3); the per-row
+// terms; a 256-wide halving tree over the rows.  Two calls at the same theta give bitwise-equal forms.
+inline void lag_forms_host(const LagFormArgs& A, LagFormOut& o) {
+    static_assert(LAG_N <= 256, "the tree over the rows is 256 wide");
+    constexpr int QB = LAG_N / 4;
+    double red[2 * LAG_NRAW][256];
+    for (int j = 0; j < 2 * LAG_NRAW; j++)
+        for (int i = 0; i < 256; i++) red[j][i] = 0.0;
+    for (int c = 0; c < 2; c++) {
+        const int K = c ? A.Kc : A.K;
+        const double Lam = A.sum_lam[c];
+        // (a row past the cut has li = rho = 0: every term of it is an exact zero)
+        for (int i = 0; i <= K && i < LAG_N; i++) {
+            double q[4] = {0.0, 0.0, 0.0, 0.0};
+            const double* m = A.M + (int64_t)i * LAG_N;     // (symmetric: row i for column i)
+            for (int b = 0; b < 4; b++) {
+                const int k1 = K < (b + 1) * QB - 1 ? K : (b + 1) * QB - 1;
+                double v = 0.0;
+                for (int k = b * QB; k <= k1; k++) v += m[k] * A.lam[k];
+                q[b] = v;
+            }
+            const double V = (q[0] + q[1]) + (q[2] + q[3]);
+            const double li = A.lam[i];
+            double rho[3];
+            for (int k = 0; k < 3; k++) rho[k] = i >= k + 1 ? A.rr[i - k - 1] : 0.0;
+            double S = li * V, Ck[3] = {rho[0] * V, rho[1] * V, rho[2] * V};
+            for (int a = 0; a < A.d; a++) {
+                const double sa = A.s[a * LAG_N + i], cm = A.cm[a];
+                S -= 2.0 * Lam * cm * li * sa;
+                for (int k = 0; k < 3; k++) Ck[k] -= cm * (Lam * rho[k] * sa + A.sum_rho[c][k] * li * sa);
+                double su = li * sa;
+                if (i == 0) {
+                    S += A.n * cm * cm * Lam * Lam;
+                    for (int k = 0; k < 3; k++) Ck[k] += A.n * cm * cm * Lam * A.sum_rho[c][k];
+                    su -= A.n * cm * Lam;
+                }
+                red[c * LAG_NRAW + 4 + a][i] = su;
+            }
+            red[c * LAG_NRAW + 0][i] = S;
+            for (int k = 0; k < 3; k++) red[c * LAG_NRAW + 1 + k][i] = Ck[k];
+        }
+    }
+    for (int w = 128; w > 0; w >>= 1)
+        for (int j = 0; j < 2 * LAG_NRAW; j++)
+            for (int i = 0; i < w; i++) red[j][i] += red[j][i + w];
+    for (int c = 0; c < 2; c++)
+        for (int j = 0; j < LAG_NRAW; j++) o.raw[c][j] = red[c * LAG_NRAW + j][0];
+    for (int k = 0; k < NACC_MAX; k++) o.acc[k] = 0.0;
+    const double su[2] = {o.raw[0][4], o.raw[0][5]};
+    tf_finish(A.statc, A.d, A.mask, o.raw[0][0], o.raw[0][1], o.raw[0][2], o.raw[0][3], su, o.acc);     // (what the streaming lanes finish with)
+    // the check: every raw sum of the two cuts, relative to itself or to sqrt(S n) (the size of a sum of n products of u with a
+    // unit-scale signal), whichever is larger
+    const double floor_ = std::sqrt(std::fabs(o.raw[0][0]) * A.n);
+    double w = 0.0;
+    for (int j = 0; j < 4 + A.d; j++) {
+        const double a = o.raw[0][j], b = o.raw[1][j];
+        const double sc = std::fmax(std::fmax(std::fabs(a), std::fabs(b)), floor_);
+        const double r = std::fabs(a - b) / sc;
+        w = (r == r) ? std::fmax(w, r) : INFINITY;
+    }
+    if (!(w == w)) w = INFINITY;
+    o.chk = w;
+}
+#if defined(__clang__)
+#pragma clang diagnostic pop
+#endif
+
+}  // namespace ssde

@@ -56,22 +56,6 @@ inline void lag_track_stats(const double* y, int rows, int d, double* Q, double*
     }
 }
 
-// the per-evaluation forms (k_lagstats.hip: lag_forms_kernel)
-struct LagFormArgs {
-    const double* M;                  // [LAG_N][LAG_N]
-    const double* s;                  // [2][LAG_N]
-    double n;                         // bulk rows
-    int K, Kc;                        // taps 0..K of the forms, 0..Kc of the check
-    int d, mask;                      // response coordinates, DIR_* bits of the evaluation
-    double lam[LAG_N];                // impulse response of u
-    double rr[LAG_N];                 // impulse response of r (r_{t-k}: rr shifted by k)
-    double sum_lam[2], sum_rho[2][3]; // sums of the taps 0..K (index 0) and 0..Kc (index 1)
-    double cm[2];                     // mu_a dt
-    double statc[48];                 // the stationary constants (IsoArgs.statc): tf_finish forms the accumulators from them
-    double* partials;                 // the evaluation's partial sums: this writes window `chunk` of every group
-    int chunk, n_groups, kfast;
-    double* chk;                      // raised to the relative difference between the two cuts (a non-negative double as its bit pattern)
-};
-static_assert(sizeof(LagFormArgs) <= 4096, "lag_forms_kernel takes its arguments by value");
+// (the per-evaluation forms built from M, s and n: ssde_lagforms.hpp, on the host)
 
 }  // namespace ssde

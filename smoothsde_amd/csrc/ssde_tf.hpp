@@ -25,7 +25,7 @@ namespace ssde {
 // sensitivities are short linear combinations of y_{t-1}, w and r), so the window check is unchanged.
 // The accumulators [value | sigma_obs | mu_1 .. mu_d | par d | par d + 1] from the sums of the stationary rows: S = sum u^2,
 // C_k = sum u r_{t-k}, su_a = sum u_a, with the stationary constants c = IsoArgs.statc.  TfCtcrw::finish and the bulk's forms
-// (k_lagstats.hip: lag_forms_kernel) both end here.
+// (ssde_lagforms.hpp: lag_forms_host) both end here.
 SSDE_HD void tf_finish(const double* c, int d, int mask, double S, double C1, double C2, double C3, const double* su, double* out) {
     const double iF = c[0];
     out[0] = 0.5 * iF * S;
