@@ -54,6 +54,8 @@ template <int N> inline Dual<N>& operator-=(Dual<N>& a, const Dual<N>& b) { a = 
 template <int N> inline bool operator<=(const Dual<N>& a, double b) { return a.v <= b; }
 template <int N> inline bool operator>(const Dual<N>& a, double b) { return a.v > b; }
 template <int N> inline bool operator<(const Dual<N>& a, double b) { return a.v < b; }
+template <int N> inline bool operator==(const Dual<N>& a, const Dual<N>& b) { return a.v == b.v; }
+template <int N> inline bool operator!=(const Dual<N>& a, const Dual<N>& b) { return a.v != b.v; }
 
 template <int N> inline Dual<N> exp(const Dual<N>& a) {
     Dual<N> r; r.v = std::exp(a.v); for (int k = 0; k < N; k++) r.d[k] = r.v * a.d[k]; return r; }

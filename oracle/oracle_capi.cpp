@@ -2,7 +2,7 @@
 //
 // TEST INFRASTRUCTURE ONLY: loaded by tests/, __graft_entry__.smoke() and the
 // cpu_baseline leg of bench.py.  The product library (smoothsde_amd/lib/libssde_hip.so)
-// never links or calls it.  PARITY UNPINNED (see ssde_oracle.hpp / README.md).
+// never links or calls it.  Its reading of the reference is pinned by ref_capi.cpp (see README.md).
 //
 //   oracle_eval(desc, par, order, &value, grad, aest_all, n_threads)
 //     value = nllk_data + penalty, exactly what objective_function<Type>::operator()

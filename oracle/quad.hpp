@@ -39,6 +39,8 @@ inline Quad& operator-=(Quad& a, const Quad& b) { a.v -= b.v; return a; }
 inline bool operator<=(const Quad& a, double b) { return a.v <= b; }
 inline bool operator>(const Quad& a, double b) { return a.v > b; }
 inline bool operator<(const Quad& a, double b) { return a.v < b; }
+inline bool operator==(const Quad& a, const Quad& b) { return a.v == b.v; }
+inline bool operator!=(const Quad& a, const Quad& b) { return a.v != b.v; }
 
 inline Quad exp(const Quad& a) { return q128(expq(a.v)); }
 inline Quad log(const Quad& a) { return q128(logq(a.v)); }

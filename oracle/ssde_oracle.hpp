@@ -2,10 +2,10 @@
 //
 // TEST INFRASTRUCTURE ONLY.  Nothing under smoothsde_amd/ may include, link or call this
 // file; it is the checker for the HIP path (tests/, __graft_entry__.smoke(), and the
-// cpu_baseline leg of bench.py).  PARITY UNPINNED: the reference's own tests hold no
-// numeric result for this path (/root/reference/tests/testthat/test_sde.R:4-72) and the
-// reference cannot be built here (it needs TMB.hpp / Eigen / R headers, none installed),
-// so this restatement is pinned only by independent cross-checks (oracle/README.md).
+// cpu_baseline leg of bench.py).  The reference's own tests hold no numeric result for this
+// path (/root/reference/tests/testthat/test_sde.R:4-72); this restatement is pinned by
+// independent cross-checks and, for its READING of the reference, by the reference's own
+// sources compiled behind a stand-in <TMB.hpp> (ref_capi.cpp, tmb_shim/; oracle/README.md).
 //
 // Every function names the reference lines it follows.  Like the reference, the code is
 // templated on the scalar `Type`; the reference instantiates it with CppAD's AD<double>,

@@ -4,9 +4,11 @@
 What this pins: the oracle's double arithmetic (rounding, summation order, the LU of F) and its forward-mode gradient
 (oracle/dual.hpp) on every golden case -- at ordinary parameters the double-precision value sits within 1e-12 of the exact
 value of the reference's formulas and the dual-number gradient within 1e-9 of the derivative of that exact function.
-What it cannot pin: a misreading of the reference shared by both instantiations (PARITY UNPINNED stays: the reference holds
-no numeric fixture and cannot be built here).  The binary128 build is also the arbiter of tools/extreme_probe.py, where
-the literal double formulas are ill-conditioned and oracle and engine disagree."""
+What it cannot pin: a misreading of the reference shared by both instantiations.  That is pinned elsewhere: the reference's
+own likelihood sources, compiled unmodified behind a stand-in <TMB.hpp>, against this oracle in double and in binary128
+(tests/test_reference_parity.py; oracle/README.md says what of TMB and of the R side stays a restatement).  The binary128
+build is also the arbiter of tools/extreme_probe.py, where the literal double formulas are ill-conditioned and oracle and
+engine disagree."""
 import numpy as np
 import pytest
 
