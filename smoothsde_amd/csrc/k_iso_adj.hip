@@ -15,7 +15,7 @@
 //            slab, then the CB rows BACKWARDS: the transposed step, the row's g_j, and the FMAs of X' g.  The next block's rows
 //            and checkpoint are requested before the backward half, which reads its columns from the registers the forward
 //            half filled.
-// Windows (ssde_engine_iso.hip: plan_windows) as everywhere, in BOTH directions: the adjoint forgets through the same closed-loop
+// Windows (ssde_windows.hpp: plan_windows) as everywhere, in BOTH directions: the adjoint forgets through the same closed-loop
 // matrix transposed, so a window that is not the last runs `adj_tail` = `window` rows past its end (s_hi = s_end + adj_tail: rows it walks but
 // whose gradient terms belong to the next window) and starts the backward recursion there from zero.  The hand-over record of a
 // boundary holds the forward state AND the adjoint at that row from both sides; iso_finalize_kernel compares them like any other

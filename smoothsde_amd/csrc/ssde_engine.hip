@@ -484,101 +484,25 @@ int run_once(ssde_handle* h, const double* par, int order, double* o) {
     return SSDE_OK;
 }
 
-// An evaluation with the window policy around it: re-evaluate with a wider warm-up until the time
-// windows agree, narrow again on probation after `cooldown` calm evaluations.  Every decision is taken on the
-// REDUCED check value (a sum of non-negative per-shard / per-rank maxima, compared with the single-engine
-// tolerance: conservative), so the shards of a parent and the ranks of a communicator move in lockstep and the
-// collective inside run_once is entered by everyone the same number of times.
+// An evaluation with the window policy around it (WindowPolicy, ssde_windows.hpp): run once, ask the policy, apply
+// what it asks of the engines -- until it accepts.
 int run_checked(ssde_handle* h, const double* par, int order, std::vector<double>& o) {
+    WindowPolicy& policy = h->policy();
+    const ssde_handle* e0 = h->shards.empty() ? h : h->shards[0];
     const bool dist = !h->shards.empty() || !h->comms.empty();
-    int attempt = 0;
-    double seen[2] = {-1.0, -1.0};                    // the check values of the last two attempts that each made this call quadruple the warm-up
-    for (;; attempt++) {
+    WindowPolicy::Call call;
+    for (;;) {
         int st = run_once(h, par, order, o.data());
         if (st) return st;
-        h->last_check = o[1 + h->L.n_full];
-        each_engine(h, [&](ssde_handle* e) { e->last_check = h->last_check; });
-        // hand-over check of the time windows (k_iso.hip): widen the warm-up and re-evaluate
-        // until the windows agree with each other; 64x the estimate ends in one sequential window
-        if (h->last_check <= std::max(SSDE_WINDOW_TOL, h->check_floor)) break;
-        // ROUNDING FLOOR.  What a short warm-up leaves behind decays with its length; a SMALL disagreement that stays where it is
-        // while the warm-up is quadrupled TWICE (16 x the rows) is not the warm-up's: it is rounding in the states themselves (fixes
-        // that are very precise against the movement between them: P11 ~ sigma_obs^2 next to P22 ~ 1, the gains 1 - O(sigma_obs^2)),
-        // the same in one sequential window, where nothing would notice it.  Such a floor is accepted from here on (up to 4 x what was
-        // seen, never beyond 1e-8) and the plan goes back to the warm-up it had -- instead of ending in ONE window per track, two orders
-        // of magnitude slower on long tracks, for the same digits.  (A slowly forgetting mode of small amplitude is NOT flat over 16 x
-        // the rows: tests/test_gpu_drift.py::test_forced_short_warm_up_is_caught_and_repaired.  The value is the reduced one: shards
-        // and ranks decide alike.)
-        if (seen[0] > 0.0 && seen[1] > 0.0 && seen[0] <= 1e-8 && seen[1] <= 1e-8 && h->last_check <= 1e-8 &&
-            seen[1] >= 0.5 * seen[0] && h->last_check >= 0.5 * seen[1] && std::isfinite(o[0])) {
-            h->check_floor = std::min(1e-8, 4.0 * std::max(h->last_check, std::max(seen[0], seen[1])));
-            each_engine(h, [](ssde_handle* e) { e->window_boost = std::max(1, e->window_boost / 16); });
-            if (!h->shards.empty()) h->window_boost = std::max(1, h->window_boost / 16);
-            break;
-        }
-        // (one window has no hand-over to disagree -- unless quiet rows ran: their switch check is folded into the same
-        //  value, and a longer memory, finally none at all, is the repair)
-        if (!dist && h->last_chunks <= 1 && h->last_quiet_window == 0 && h->last_lag_rows == 0) break;
-        // a non-finite nllk is rejected by the caller whatever the windows did: no retry, and no lasting
-        // widening of the plan because an optimiser probed an absurd parameter once
-        if (!std::isfinite(o[0])) break;
-        // (a plan that has given up runs one window WITHOUT quiet rows -- eval_iso -- so nothing is left to disagree; the cap is
-        //  for whatever that reasoning missed: the failure is then reported through window_check_max instead of spinning -- ADVICE r04)
-        if (attempt > 6) break;
-        h->n_retries++;
-        h->calm = 0;
-        if (h->probing && attempt == 0) {
-            // the narrower plan tried on probation does not hold here: back to the one that worked, and wait twice
-            // as long before the next try
-            h->probing = false;
-            h->cooldown = std::min(h->cooldown * 2, 1 << 14);
-            if (h->probe_from == 0) each_engine(h, [](ssde_handle* e) { e->max_chunks = 1; e->want_chunks = 1; e->gave_up = true; });
-            else each_engine(h, [&](ssde_handle* e) { e->window_boost = h->probe_from; });
-            if (h->probe_from == 0) h->gave_up = true;
-            else h->window_boost = h->probe_from;
-            continue;
-        }
-        // the row-varying path plans from the parameter ranges its pre-pass saw in the PREVIOUS evaluation: after a
-        // jump in the parameters the first retry needs no boost, just this evaluation's own ranges
-        const int path0 = h->shards.empty() ? h->path : h->shards[0]->path;
-        const int drift0 = h->shards.empty() ? h->drift : h->shards[0]->drift;
-        if ((path0 == PATH_TV || drift0 == 3) && attempt == 0) continue;       // (k_iso_colvar.hip plans the same way)
-        if (attempt >= 3) {                                            // give up on windows: sequential filter
-            each_engine(h, [](ssde_handle* e) {
-                if (!e->gave_up) { e->saved_max_chunks = e->max_chunks; e->saved_want_chunks = e->want_chunks; e->gave_up = true; }
-                e->max_chunks = 1; e->want_chunks = 1;
-            });
-            h->gave_up = true;
-        } else {
-            seen[0] = seen[1]; seen[1] = h->last_check;
-            each_engine(h, [](ssde_handle* e) { e->window_boost *= 4; });
-            if (!h->shards.empty()) h->window_boost *= 4;
-        }
+        // (one window has no hand-over to disagree -- unless quiet rows or the lag statistics ran: their checks are folded into the same value)
+        const bool one_window = h->last_chunks <= 1 && h->last_quiet_window == 0 && h->last_lag_rows == 0;
+        const WindowPolicy::Verdict v = policy.after_attempt(call, {o[1 + h->L.n_full], std::isfinite(o[0]), one_window, dist,
+                                                                    e0->path == PATH_TV || e0->drift == 3});
+        each_engine(h, [&](ssde_handle* e) { apply_chunks(*e, v.engines); });
+        if (!v.retry) break;
     }
-    if (std::isfinite(o[0]) && !(h->last_check <= h->check_max)) h->check_max = h->last_check;
-    // (the floor belongs to the regime that showed it: an evaluation whose windows agree outright ends it, so that a later, genuinely
-    //  short warm-up is not waved through under an old allowance)
-    if (h->last_check <= SSDE_WINDOW_TOL) h->check_floor = 0.0;
-    // A widened plan is not for life: one slow-forgetting parameter vector in a line search would otherwise tax every
-    // later evaluation.  Every evaluation is checked, so narrowing on probation is safe -- a failure costs one retry.
-    const bool forced = h->shards.empty() ? h->chunks_forced : h->shards[0]->chunks_forced;
-    if (attempt == 0 && !forced) {
-        h->calm++;
-        if (h->probing && h->calm >= 4) h->probing = false;           // the narrower plan holds
-        if (h->calm >= h->cooldown && (h->gave_up || h->window_boost > 1)) {
-            h->calm = 0;
-            h->probing = true;
-            if (h->gave_up) {
-                h->probe_from = 0;
-                each_engine(h, [](ssde_handle* e) { e->max_chunks = e->saved_max_chunks; e->want_chunks = e->saved_want_chunks; e->gave_up = false; });
-                h->gave_up = false;
-            } else {
-                h->probe_from = h->window_boost;
-                each_engine(h, [](ssde_handle* e) { e->window_boost = std::max(1, e->window_boost / 2); });
-                if (!h->shards.empty()) h->window_boost = std::max(1, h->window_boost / 2);
-            }
-        }
-    }
+    const ChunkAction act = policy.end_call(call, std::isfinite(o[0]), e0->chunks_forced);
+    each_engine(h, [&](ssde_handle* e) { apply_chunks(*e, act); });
     return SSDE_OK;
 }
 
@@ -725,9 +649,8 @@ int ssde_report(ssde_handle* h, const double* par, int32_t n_par_full, double* a
 
 int ssde_widen_windows(ssde_handle* h, int32_t factor) {
     if (!h) return SSDE_ERR_ARG;
-    for (ssde_handle* s : h->shards) ssde_widen_windows(s, factor);
-    if (factor <= 0) { h->max_chunks = 1; h->want_chunks = 1; }
-    else if (h->window_boost < (1 << 20)) h->window_boost *= factor;
+    if (factor <= 0) each_engine(h, [](ssde_handle* e) { e->max_chunks = 1; e->want_chunks = 1; });
+    else h->policy().widen(factor);
     h->memo_order = -1;
     return SSDE_OK;
 }
@@ -826,8 +749,7 @@ int ssde_forget(ssde_handle* h) {
 
 int ssde_relax_windows(ssde_handle* h) {
     if (!h) return SSDE_ERR_ARG;
-    for (ssde_handle* s : h->shards) ssde_relax_windows(s);
-    h->window_boost = std::max(1, h->window_boost / 2);
+    h->policy().relax();
     return SSDE_OK;
 }
 
@@ -866,7 +788,7 @@ int ssde_info(const ssde_handle* h, ssde_info_t* info) {
             info->required_bytes_per_row = required;
             info->sdim = h->sdim;
         }
-        info->window_check = h->last_check; info->window_retries = h->n_retries; info->window_check_max = h->check_max;
+        info->window_check = h->policy().last_check; info->window_retries = h->policy().n_retries; info->window_check_max = h->policy().check_max;
         info->n_memo_hits = h->n_memo_hits;
         info->n_devices = h->n_track_shards; info->comm_ranks = h->comm_ranks; info->comm_ranks_reported = h->comm_ranks_reported;
         info->exact_hess_scope = hess_exact_scope(h);
@@ -906,7 +828,7 @@ int ssde_info(const ssde_handle* h, ssde_info_t* info) {
         info->quiet_window = h->last_quiet_window; info->quiet_share = h->quiet_share;
     }
     info->n_evals = h->n_evals; info->n_memo_hits = h->n_memo_hits;
-    info->n_devices = 1; info->comm_ranks = h->comm_ranks; info->window_check_max = h->check_max;
+    info->n_devices = 1; info->comm_ranks = h->comm_ranks; info->window_check_max = h->policy().check_max;
     info->comm_ranks_reported = h->comm_ranks_reported; info->kernel_id = h->last_kernel_id;
     info->exact_hess_scope = hess_exact_scope(h);
     if (h->path == PATH_ISO)   // 4-wave workgroups; with a transient window the grid enumerates windows 1.. only
@@ -918,8 +840,8 @@ int ssde_info(const ssde_handle* h, ssde_info_t* info) {
                           : h->path == PATH_DENSE ? h->n_dirblocks
                           : h->path == PATH_TV ? h->tv_ndp * h->tv_max_nc : 1;
     info->window = h->last_window;
-    info->window_check = h->last_check;
-    info->window_retries = h->n_retries;
+    info->window_check = h->policy().last_check;
+    info->window_retries = h->policy().n_retries;
     info->main_kernel_ms = 0.0;
     if (h->ev_k_valid && hipEventQuery(h->ev_k1) == hipSuccess) {
         float ms = 0.f;

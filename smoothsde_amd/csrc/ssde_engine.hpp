@@ -20,6 +20,7 @@
 #include "ssde_knobs.hpp"
 #include "ssde_lagstats.hpp"
 #include "ssde_tv.hpp"
+#include "ssde_windows.hpp"
 
 namespace ssde_engine {
 
@@ -27,7 +28,7 @@ extern thread_local std::string g_create_error;   // message of the last failed 
 
 enum { PATH_DIRECT = 0, PATH_ISO = 1, PATH_DENSE = 2, PATH_TV = 3 };
 constexpr int PAR_RING = 8;
-constexpr double SSDE_WINDOW_TOL = 1e-11;  // largest tolerated relative hand-over disagreement
+constexpr WindowConsts WINDOW_CONSTS = {ssde::WIN_ALIGN, ssde::SHARED_U, ssde::LAG_A, ssde::LAG_KMAX};   // (ssde_windows.hpp)
 
 template <class T>
 struct DevBuf {
@@ -140,18 +141,17 @@ struct ssde_handle {
     int last_quiet_window = 0;     // rows of memory the last launch used (0: no quiet rows)
     bool gain_stationary = false;  // the last gain recursion reached its stationary row
     double stat_p[12] = {0}, stat_ld = 0.0, stat_gld[3] = {0, 0, 0};   // ... the covariance, log F and dF / F there
-    double plan_rho = 1.0;         // spectral radius of the closed-loop matrix the last plan_windows call found
-    int plan_warmup = 0;           // warm-up rows the last plan_windows call found sufficient (0: no usable forgetting)
-    int window_boost = 1;          // multiplies the estimated warm-up after a failed hand-over check
+    double plan_rho = 1.0;         // spectral radius of the closed-loop matrix the last plan found
+    int plan_warmup = 0;           // warm-up rows the last plan found sufficient (0: no usable forgetting)
     int last_chunks = 1, last_window = 0;
-    double last_check = 0.0;
-    int n_retries = 0;
     ssde_engine::Knobs knobs;      // testing / tuning knobs, read once, by build(): nothing reads the environment per evaluation
-    // recovery from a widened plan (ssde_eval): after `cooldown` evaluations accepted at the first try the boost is
-    // halved (or a given-up window plan restored) on probation; a failure on probation restores the level that worked
-    // and doubles the cooldown
-    int calm = 0, cooldown = 32, probe_from = 0, saved_max_chunks = 0, saved_want_chunks = 0;
-    bool probing = false, gave_up = false;
+    // The retry / probation policy around ssde_eval (ssde_windows.hpp).  A top-level handle decides with its own; the shards of a
+    // multi-device parent plan with the parent's (create_sharded sets the pointer), so every engine of a handle sees one boost.
+    ssde_engine::WindowPolicy own_policy;
+    ssde_engine::WindowPolicy* parent_policy = nullptr;
+    ssde_engine::WindowPolicy& policy() { return parent_policy ? *parent_policy : own_policy; }
+    const ssde_engine::WindowPolicy& policy() const { return parent_policy ? *parent_policy : own_policy; }
+    int saved_max_chunks = 0, saved_want_chunks = 0;   // this engine's limits from before the policy gave up on windows (apply_chunks)
 
     // shared-covariance path
     DevBuf<int32_t> group_flags;
@@ -316,8 +316,6 @@ struct ssde_handle {
     double memo_value = 0.0;
     int memo_order = -1;                      // -1 = nothing memoised
     int64_t n_evals = 0, n_memo_hits = 0;
-    double check_max = 0.0;                   // largest accepted hand-over disagreement since create
-    double check_floor = 0.0;                 // > 0: a disagreement that a 4x longer warm-up did NOT reduce -- rounding in the states, not a short warm-up; accepted up to here
     // host-side phase clock of the isotropic path (SSDE_TRACE=1 at create; printed at destroy): plan, gain table,
     // main launch(es), finalize launch, read-back
     double trace_us[6] = {0, 0, 0, 0, 0, 0};
@@ -346,8 +344,6 @@ void destroy(ssde_handle* h);
 void attach_hess_companion(const ssde_desc* desc, ssde_handle* h);     // SSDE_FLAG_EXACT_HESS (ssde_engine.hip)
 void release_device(ssde_handle* h);          // everything the handle holds on the device / in pinned memory (the handle stays)
 int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipStream_t s, ReduceArgs& ra);   // ssde_engine_iso.hip
-// spectral radius of the stationary closed-loop matrix T - K Z at constant parameters p1, p2 (ssde_engine_tv.hip); p0 = {p11, p12, p22} or {p}
-double closed_loop_rho(int model, double dt, double p1, double p2, double hobs, const double* p0);
 int eval_device(ssde_handle* h, const double* par, int order, double* out_dev, hipStream_t s);
 
 // ---- distributed evaluation (ssde_engine_dist.hip) --------------------------------------------------------------------

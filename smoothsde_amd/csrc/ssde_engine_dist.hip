@@ -385,6 +385,7 @@ coupled_done:
             if (st != SSDE_OK)
                 return fail(parent, st, (S > 1 ? "shard " + std::to_string(k) + " " : std::string()) + (P > 1 ? "dimension part " + std::to_string(p) + " " : std::string()) +
                                         "(device " + std::to_string(sd.device) + "): " + sh->err);
+            sh->parent_policy = &parent->own_policy;        // one window policy per handle: every engine plans with the parent's
             parent->shard_leader.push_back(leader);
             if (leader != e) sh->own_stream = parent->shards[leader]->own_stream;       // one stream per device orders its engines and their sum
             else HIPCHK(parent, hipStreamCreateWithFlags(&sh->own_stream, hipStreamNonBlocking));

@@ -1,5 +1,5 @@
-// ssde_engine_iso.hip -- one evaluation on the register Kalman path (constant coefficients, or a row-varying drift): the
-// window plan, the gain table of the shared-covariance kernels, the launches (shared / general / drift / mixed batch) and
+// ssde_engine_iso.hip -- one evaluation on the register Kalman path (constant coefficients, or a row-varying drift): decode the
+// parameters, plan the windows and their geometry (ssde_windows.hpp), the gain table of the shared-covariance kernels, the launches (shared / general / drift / mixed batch) and
 // the finalising launch (hand-over checks + fixed-order sums).  Called from eval_device (ssde_engine.hip).
 #include "ssde_engine.hpp"
 #include "ssde_lagforms.hpp"
@@ -9,125 +9,19 @@
 
 using namespace ssde_engine;
 
-// Measured.  T0_COST: a row of the transient window, in stationary rows.  W0_RATIO: cost of a row of window 0 (every direction) over a
-// row of a later window (one derived) on the general kernel -- 0 .. 1.45 swept, 3 % on CTCRW at 1.2, nothing on the scalar models.
-constexpr double T0_COST = 3.0, W0_RATIO = 1.2;
-
 namespace {
 
-// Warm-up length of a time window: iterate the (data-independent) covariance recursion on the
-// host at the smallest interval of the batch until it is stationary, take the spectral radius
-// rho of the closed-loop matrix T - K Z there, and ask for rho^W <= 1e-18 (plus slack for the
-// t * rho^t growth of the sensitivity recursions).  The device-side hand-over check decides
-// whether the estimate was good enough; it never has to be trusted.
-void plan_windows(ssde_handle* h, const IsoArgs& a, int* n_chunks, int* window) {
-    *n_chunks = 1;
-    *window = 0;
-    h->plan_warmup = 0;
-    if (h->max_chunks <= 1) return;
-    const double dt = h->uniform_dt ? h->dt_uniform : h->dt_min;
-    double rho = 1.0;
-    if (dt > 0.0 && std::isfinite(dt)) {
-        if (h->model == SSDE_MODEL_CTCRW) {
-            CtcrwTrans tr;
-            ctcrw_trans(dt, a.tau, a.beta, a.sigma, tr);
-            double p11 = a.p0[0], p12 = a.p0[1], p22 = a.p0[2], k1 = 0, k2 = 0;
-            for (int it = 0; it < 20000; it++) {
-                const double F = p11 + a.h, iF = 1.0 / F;
-                const double tp11 = p11 + tr.t12 * p12, tp12 = p12 + tr.t12 * p22, tp21 = tr.e * p12, tp22 = tr.e * p22;
-                k1 = tp11 * iF; k2 = tp21 * iF;
-                const double n11 = tp11 * (1.0 - k1) + tp12 * tr.t12 + tr.q11, n12 = -tp11 * k2 + tp12 * tr.e + tr.q12,
-                             n22 = -tp21 * k2 + tp22 * tr.e + tr.q22;
-                const double ch = std::fabs(n11 - p11) + std::fabs(n12 - p12) + std::fabs(n22 - p22);
-                p11 = n11; p12 = n12; p22 = n22;
-                if (ch <= 1e-15 * (std::fabs(p11) + std::fabs(p22))) break;
-            }
-            // L = [[1 - k1, t12], [-k2, e]]
-            const double trc = (1.0 - k1) + tr.e, det = (1.0 - k1) * tr.e + k2 * tr.t12;
-            const double disc = trc * trc - 4.0 * det;
-            rho = disc >= 0.0 ? std::max(std::fabs(0.5 * (trc + std::sqrt(disc))), std::fabs(0.5 * (trc - std::sqrt(disc))))
-                              : std::sqrt(std::fabs(det));
-        } else {
-            ScalTrans tr;
-            if (h->model == SSDE_MODEL_OU_SSM) ou_trans(dt, a.tau, a.sigma, tr);
-            else bm_trans(dt, a.sigma, tr);
-            double p = a.p0[0], k = 0;
-            for (int it = 0; it < 20000; it++) {
-                const double F = p + a.h, tp = tr.t * p;
-                k = tp / F;
-                const double np_ = tp * (tr.t - k) + tr.q;
-                const double ch = std::fabs(np_ - p);
-                p = np_;
-                if (ch <= 1e-15 * std::fabs(p)) break;
-            }
-            rho = std::fabs(tr.t - k);
-        }
-    }
-    if (h->drift == 3 && dt > 0.0 && std::isfinite(dt)) {
-        // row-varying tau / nu: the slowest-forgetting corner of the ranges the linear predictors can reach on this design
-        // (the hand-over check decides whether that was enough, as everywhere)
-        rho = 0.0;
-        const double dts[2] = {dt, h->uniform_dt ? dt : h->dt_max};
-        for (int c = 0; c < 8; c++) {
-            const double r = closed_loop_rho(h->model, dts[c & 1], (c & 2) ? h->cv_eta_hi[0] : h->cv_eta_lo[0],
-                                             (c & 4) ? h->cv_eta_hi[1] : h->cv_eta_lo[1], a.h, a.p0);
-            rho = std::max(rho, std::isfinite(r) ? r : 1.0);
-        }
-    }
-    int W = 0;
-    h->plan_rho = rho;
-    if (!(rho < 0.9995) || !std::isfinite(rho)) return;  // no usable forgetting: sequential filter
-    // The stationary CTCRW lanes run the filter as 1/D(q)^2 recursions (k_iso_shared.hip): with closed-loop poles
-    // close to 1 their intermediate signals grow like 1/(1-rho)^2 and cancel in the innovation -- below rho = 0.97
-    // that costs < 1e-12 relative; above, the evaluation stays on the sequential direction-form filter
-    if (h->use_shared && !h->drift && h->model == SSDE_MODEL_CTCRW && rho > 0.97) return;
-    // (+ 16 rows of slack for the t rho^t growth of the forward sensitivity recursions; the reverse sweep carries none -- state and
-    //  adjoint forget like rho^t -- and every warm-up row costs it a forward AND a backward row: none there.  10^4 x 10^3 rows, 18
-    //  columns: W 48 -> 32, kernel 0.617 -> 0.572 ms, hand-over check 9e-15 -> 6e-14 against the 1e-11 it has to meet)
-    W = (int)std::ceil(std::log(1e-18) / std::log(std::max(rho, 1e-300))) + (h->cv_adj ? 0 : 16);
-    W = std::max(W, 16);
-    if (h->knobs.window) W = *h->knobs.window;                             // testing: deliberately short overlaps
-    if ((int64_t)W * h->window_boost > (int64_t)h->glen_max) return;     // longer than a track: sequential filter
-    W *= h->window_boost;
-    W = (W + WIN_ALIGN - 1) / WIN_ALIGN * WIN_ALIGN;
-    // a window must be long enough to amortise its warm-up
-    int glmax = 0;
-    {
-        // group lengths are sorted descending: the first group is the longest
-        glmax = h->glen_max;
-    }
-    int nc = h->want_chunks;
-    if (h->drift == 3 && !h->cv_one_wave() && !h->chunks_forced) { while (nc > 1 && (glmax / nc) < 2 * WIN_ALIGN) nc--; }     // (the cost below decides, not a rule)
-    else if (h->cv_adj && !h->chunks_forced) {
-        // one wave per (group, window) and per SIMD; a window walks its warm-up, its rows and -- for the backward recursion -- W rows
-        // past its end forwards (~0.8 us a row), then its rows and that tail backwards (~1.2 us a row): rounds x that is what the
-        // launch takes.  With SIMDs idle (few groups) windows shorter than their warm-up pay: the redundant rows run in parallel.
-        nc = std::max(1, std::min(h->max_chunks, glmax / (2 * WIN_ALIGN)));
-        const int ng = h->n_groups;                           // (the grid pads the groups to eight: those waves leave at once)
-        int best = 1;
-        double best_cost = (double)((ng + 1023) / 1024) * 2.0 * glmax;
-        for (int c = 2; c <= nc; c++) {
-            const double len = (double)glmax / c;
-            const double cost = (double)(((int64_t)ng * c + 1023) / 1024) * (0.8 * (len + 2.0 * W) + 1.2 * (len + W));
-            if (cost < best_cost) { best_cost = cost; best = c; }
-        }
-        nc = best;
-    }
-    else
-    while (nc > 1 && (glmax / nc) < 2 * W) nc--;
-    if (h->drift == 3 && !h->cv_one_wave() && !h->chunks_forced) {
-        // one workgroup per (group, window) and per CU: rounds x (rows of a window + its warm-up) is what the launch takes
-        int best = 1;
-        double best_cost = (double)((h->n_groups + 255) / 256) * glmax;
-        for (int c = 2; c <= nc; c++) {
-            const double cost = (double)(((int64_t)h->n_groups * c + 255) / 256) * ((double)glmax / c + W);
-            if (cost < best_cost) { best_cost = cost; best = c; }
-        }
-        nc = best;
-    }
-    *n_chunks = nc;
-    *window = nc > 1 ? W : 0;
-    h->plan_warmup = W;                                  // usable warm-up length even when one window is planned
+// what the window plan and its geometry read of the handle (ssde_windows.hpp)
+WindowFacts window_facts(const ssde_handle* h) {
+    WindowFacts f;
+    f.model = h->model; f.uniform_dt = h->uniform_dt; f.dt_uniform = h->dt_uniform; f.dt_min = h->dt_min; f.dt_max = h->dt_max;
+    f.max_chunks = h->max_chunks; f.want_chunks = h->want_chunks; f.want_chunks_d = h->want_chunks_d;
+    f.glen_max = h->glen_max; f.n_groups = h->n_groups; f.use_shared = h->use_shared; f.drift = h->drift;
+    f.cv_adj = h->cv_adj; f.cv_one_wave = h->cv_one_wave(); f.chunks_forced = h->chunks_forced; f.window = h->knobs.window;
+    for (int j = 0; j < 2; j++) { f.cv_eta_lo[j] = h->cv_eta_lo[j]; f.cv_eta_hi[j] = h->cv_eta_hi[j]; }
+    f.any_dirty = h->n_clean_groups < h->n_groups; f.quiet_ok = h->quiet_ok; f.lag_ready = h->lag_ready;
+    f.quiet_window = h->knobs.quiet_window; f.block_rows = iso_block_rows(h->model);
+    return f;
 }
 
 // Shared-covariance path: run the covariance half of the filter (ssde_math.hpp) ONCE on the host
@@ -291,6 +185,71 @@ int lag_forms_into(ssde_handle* h, const IsoArgs& a, int order, int K, int n_win
     return SSDE_OK;
 }
 
+// The reduction's arguments: which accumulator of which part feeds which output slot (needed BEFORE the main launch when the
+// finalising work is fused into it).  Reads the handle's layout and the launch's arguments, writes ra.
+void fill_reduce_args(const ssde_handle* h, const IsoArgs& a, int order, const double add[4], ReduceArgs& ra) {
+    const ParLayout& L = h->L;
+    for (int i = 0; i < 4; i++) { ra.add[i] = add[i]; ra.add_slot[i] = -1; }
+    if (h->use_shared) {
+        ra.add_slot[0] = 0;
+        if (order >= 1) {
+            const int pj[NDIRP] = {0, L.off_fe + L.fe_off[h->d], h->q > h->d + 1 ? L.off_fe + L.fe_off[h->d + 1] : 0};
+            for (int j = 0; j < NDIRP; j++)
+                if (pj[j] < L.n_full && !h->fixed[pj[j]] && (j < 2 || h->q > h->d + 1)) ra.add_slot[1 + j] = (int16_t)(1 + pj[j]);
+        }
+    }
+    const int nacc = h->cv_adj ? adj_nacc(h->model, h->d, h->n_stream_cols, a.cv_mu_cols != 0)
+                   : h->drift == 3 ? 2 + CV_KC + h->d : 4 + h->d + (h->drift ? h->n_stream_cols : 0);
+    const int ncr = (a.dual && a.n_chunks_d > a.n_chunks) ? a.n_chunks_d : a.n_chunks;     // windows the final sums run over
+    ra.n_parts = a.n_parts * ncr; ra.nacc = nacc; ra.n_blocks = h->n_groups;
+    ra.n_value_parts = ncr; ra.chunks_per_part = ncr;
+    ra.chk = h->chk.p; ra.n_chk = a.n_chunks > 1 ? a.n_parts * (a.n_chunks - 1) * h->n_groups : 0;
+    // (the bulk's forms are one more window, by value: lag_forms_into)
+    if (order >= 1 && h->cv_adj) {
+        // accumulators of k_iso_adj.hip: [value | log sigma_obs | mu_a | par[d] | par[d + 1] | per streamed column: par[d], par[d + 1] (, mu_a)]
+        const int nkp = h->model == SSDE_MODEL_BM_SSM ? 1 : 2, nk = adj_nk(h->model, h->d, a.cv_mu_cols != 0);
+        if (!h->fixed[0] && !h->has_h) ra.map[0] = 1;
+        for (auto& sl : h->slots) {
+            if (h->fixed[sl.pidx]) continue;
+            const int kind = sl.par_j < h->d ? nkp + sl.par_j : sl.par_j - h->d;
+            const int k = sl.col >= 0 ? 4 + h->d + sl.col * nk + kind : (sl.par_j < h->d ? 2 + sl.par_j : 2 + h->d + (sl.par_j - h->d));
+            ra.map[k - 1] = (int16_t)(1 + sl.pidx);
+        }
+    } else
+    if (order >= 1 && h->drift == 3) {
+        // accumulators of k_iso_colvar.hip, per part: [value | the part's columns | mu_1 .. mu_d | log sigma_obs]
+        for (int p = 0; p < CV_WAVES; p++) {
+            for (int k = 0; k < CV_KC; k++) {
+                const int pidx = h->cv_pidx[(size_t)p * CV_KC + k];
+                if (pidx >= 0) ra.map[p * (nacc - 1) + k] = (int16_t)(1 + pidx);
+            }
+            if (p == h->cv_mu_part)
+                for (auto& sl : h->slots)
+                    if (sl.par_j < h->d && sl.col < 0 && !h->fixed[sl.pidx]) ra.map[p * (nacc - 1) + CV_KC + sl.par_j] = (int16_t)(1 + sl.pidx);
+            if (p == h->cv_sig_part) ra.map[p * (nacc - 1) + CV_KC + h->d] = 1;
+        }
+    } else
+    if (order >= 1 && h->drift) {
+        // accumulators of k_iso_drift.hip: [value | sigma_obs | mu intercepts | par d | par d+1 | streamed columns]
+        if (!h->fixed[0]) ra.map[0] = 1;
+        for (auto& sl : h->slots) {
+            if (h->fixed[sl.pidx]) continue;
+            const int k = sl.col >= 0 ? 4 + h->d + sl.col : (sl.par_j < h->d ? 2 + sl.par_j : sl.par_j == h->d ? 2 + h->d : 3 + h->d);
+            ra.map[k - 1] = (int16_t)(1 + sl.pidx);
+        }
+    } else
+    if (order >= 1) {
+        for (int p = 0; p < a.n_parts; p++)
+            for (int k = 1; k < nacc; k++) {
+                // accumulators are ordered like the constant-coefficient parameter vector: sigma_obs, one per SDE parameter
+                const int j = k - 2;     // SDE parameter of accumulator k (k == 1: log_sigma_obs)
+                if (j >= h->q) continue;
+                const int pidx = j < 0 ? 0 : L.off_fe + L.fe_off[j];
+                if (pidx < L.n_full && !h->fixed[pidx]) ra.map[p * (nacc - 1) + (k - 1)] = (int16_t)(1 + pidx);
+            }
+    }
+}
+
 }  // namespace
 
 namespace ssde_engine {
@@ -384,7 +343,11 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
     }
     auto tick = [&]() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double tk0 = h->knobs.trace ? tick() : 0.0;
-    plan_windows(h, a, &a.n_chunks, &a.window);
+    // ---- the plan (ssde_windows.hpp): from what create found, this evaluation's parameters and the policy's boost
+    const WindowPolicy& policy = h->policy();
+    const WindowFacts wf = window_facts(h);
+    const WindowParams wp = {a.tau, a.beta, a.sigma, a.h, {a.p0[0], a.p0[1], a.p0[2]}};
+    const WindowPlan plan = plan_windows(wf, WINDOW_CONSTS, wp, policy.boost());
     if (h->knobs.trace) { const double t = tick(); h->trace_us[0] += t - tk0; tk0 = t; }
     a.bnd = h->bnd.p; a.chk = h->chk.p;
     a.bnd_stride = h->drift ? std::max(NSTATE_MAX, h->drift_nstate) : NSTATE_MAX;
@@ -394,11 +357,9 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
     a.all_clean = ((h->use_shared && h->n_clean_groups == h->n_groups) || h->drift) ? 1 : 0;      // (drift: one dump layout for every group)
     a.nstate_clean = h->drift ? h->drift_nstate
                    : h->use_shared ? shared_nstate(h->sdim, order >= 1 ? a.part_mask[0] : 0, h->model != SSDE_MODEL_BM_SSM) : 0;
-    h->last_chunks = a.n_chunks; h->last_window = a.window;
     a.group_flags = h->group_flags.p;
     a.group_mode = 0;
     double add[4] = {0, 0, 0, 0};
-    int lag_K = 0;                           // > 0: rows past LAG_A from the lag statistics, with this many taps
     if (!h->use_shared && h->quiet_ok) {
         int st = (h->d == 1) ? build_gain_table<1>(h, a, h->iso_free_mask, s, add) : build_gain_table<2>(h, a, h->iso_free_mask, s, add);
         if (st) return st;
@@ -411,79 +372,26 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
         if (st) return st;
         if (h->knobs.trace) { const double t = tick(); h->trace_us[1] += t - tk0; tk0 = t; }
         a.group_mode = 3;
-        // Rows past LAG_A from the lag statistics, decided here for this evaluation: the cut K the window plan asks
-        // for must fit the statistics (K <= LAG_KMAX) and the head (the stationary gains from row s_stat, K rows before LAG_A);
-        // a plan that has given up, or gains that never became stationary, stream every row
-        if (h->lag_ready && !h->drift && !h->hess_req && a.n_parts == 1 && !h->gave_up && h->gain_stationary && a.gain_stat[0] != 0.0 &&
-            h->plan_warmup > 0) {
-            const int s_stat = (a.gain_last + SHARED_U - 1) / SHARED_U * SHARED_U;
-            if (h->plan_warmup <= LAG_KMAX && s_stat + h->plan_warmup <= LAG_A) lag_K = h->plan_warmup;
-        }
-        if (lag_K > 0) {
-            // the head: every track capped at LAG_A rows, planned as a batch of that length
-            a.tv.group_len = h->lag_glen.p; a.tv.lane_nsteps = h->lag_ns.p;
-            const int gl = h->glen_max;
-            h->glen_max = LAG_A;
-            plan_windows(h, a, &a.n_chunks, &a.window);
-            h->glen_max = gl;
-            h->last_chunks = a.n_chunks; h->last_window = a.window;
-            h->last_lag_rows = h->lag_rows;
-        }
-        const int glen = lag_K > 0 ? LAG_A : h->glen_max;
-        // the covariance transient gets its own short window [0, t0): every other window (warm-up
-        // included) then lies in the stationary regime and runs the lean kernel
-        // A batch with more track groups than SIMDs needs no time windows to fill the chip, but the lean
-        // stationary kernel only exists for windows past the covariance transient: split every track into
-        // the transient window and ONE stationary window (same wave, so no extra work items)
-        if (h->drift) {
-            // every row costs the same here (HBM-bound; the table rows and the stationary rows run the same step): plain equal windows
-            a.t0 = 0;
-        } else
-        if (a.n_chunks == 1 && h->plan_warmup > 0 && h->max_chunks >= 2 && !h->chunks_forced) {
-            a.n_chunks = 1; a.window = h->plan_warmup;
-            const int s_stat0 = (a.gain_last + SHARED_U - 1) / SHARED_U * SHARED_U;
-            const int t0c = (s_stat0 + a.window + WIN_ALIGN - 1) / WIN_ALIGN * WIN_ALIGN;
-            if (t0c + 2 * a.window < glen) { a.t0 = t0c; a.n_chunks = 2; h->last_window = a.window; }
-            else a.window = 0;
-        } else
-        if (a.n_chunks > 1) {
-            const int s_stat = (a.gain_last + SHARED_U - 1) / SHARED_U * SHARED_U;
-            a.t0 = (s_stat + a.window + WIN_ALIGN - 1) / WIN_ALIGN * WIN_ALIGN;
-            if (a.t0 + 2 * a.window >= glen) { a.t0 = 0; }                   // tracks too short to bother
-            else if (a.n_chunks < h->max_chunks) a.n_chunks += 1;           // window 0 + the planned ones
-        }
-        h->last_chunks = a.n_chunks;
     }
-    // the transient window (gain table, direction form) runs on the wave that owns window 1: that window is
-    // shortened by what the transient rows cost, in stationary rows (T0_COST x t0)
-    a.t0_delta = (int)(T0_COST * a.t0 + WIN_ALIGN - 1) / WIN_ALIGN * WIN_ALIGN;
-    if (!h->use_shared && !h->drift && a.n_chunks > 1) {
-        // General kernel, every window on its own wave: window 0 carries EVERY direction (windows >= 1 derive one,
-        // k_iso.hip) but has no warm-up rows.  With equal windows its waves are the last to finish and the whole
-        // launch waits for them (CTCRW: 212 against 163 instructions per row).  Balance: window 0 = [0, L0) with
-        // r L0 = L1 + W, the others split [L0, L) equally -- the geometry window_bounds already has for a transient
-        // window (t0 = L0), with nothing to subtract from window 1 (t0_delta = 0: it has a wave of its own).
-        const bool can_derive = order >= 1 && a.derive && (a.part_mask[0] & DIR_SIG) &&
-                                (a.part_mask[0] & (h->model == SSDE_MODEL_BM_SSM ? DIR_P1 : DIR_P2));
-        const double r = can_derive ? W0_RATIO : 1.0;
-        const int nc = a.n_chunks;
-        const double L0 = ((double)h->glen_max / (nc - 1) + a.window) / (r + 1.0 / (nc - 1));
-        const int t0 = (int)(L0 / WIN_ALIGN) * WIN_ALIGN;
-        if (t0 >= 2 * WIN_ALIGN && t0 + 2 * a.window < h->glen_max) { a.t0 = t0; a.t0_delta = 0; }
+    // ---- the geometry that follows the plan: the transient window, the balance of window 0, the mixed batch's second plan, the
+    // lag-statistics cut and the quiet rows' memory
+    WindowEval we;
+    we.n_parts = a.n_parts; we.hess_req = h->hess_req;
+    we.can_derive = order >= 1 && a.derive && (a.part_mask[0] & DIR_SIG) && (a.part_mask[0] & (h->model == SSDE_MODEL_BM_SSM ? DIR_P1 : DIR_P2));
+    we.gain_last = a.gain_last; we.gain_usable = h->gain_stationary && a.gain_stat[0] != 0.0;
+    const WindowGeometry g = window_geometry(wf, WINDOW_CONSTS, wp, plan, policy.boost(), policy.gave_up, we);
+    const int lag_K = g.lag_K;
+    h->plan_warmup = g.plan.warmup; h->plan_rho = g.plan.rho;
+    a.n_chunks = g.n_chunks; a.window = g.window; a.t0 = g.t0; a.t0_delta = g.t0_delta;
+    h->last_chunks = a.n_chunks; h->last_window = a.window; h->last_t0 = a.t0; h->last_t0_delta = a.t0_delta;
+    h->last_quiet_window = g.quiet_window;
+    if (lag_K > 0) {                         // the head: every track capped at LAG_A rows
+        a.tv.group_len = h->lag_glen.p; a.tv.lane_nsteps = h->lag_ns.p;
+        h->last_lag_rows = h->lag_rows;
     }
-    h->last_t0 = a.t0; h->last_t0_delta = a.t0_delta;
-    h->last_quiet_window = 0;
-    // (CTCRW: the transfer-function lanes lose digits when the closed-loop poles approach 1 -- the limit plan_windows has for them)
-    // (a plan that has given up on windows gives up on quiet rows too: with them the retry would run the identical plan again)
-    if (h->quiet_ok && !h->gave_up && h->gain_stationary && h->plan_warmup > 0 && a.gain_stat[0] != 0.0 && a.n_parts == 1 &&
-        !(h->model == SSDE_MODEL_CTCRW && h->plan_rho > 0.97)) {
-        const int U = iso_block_rows(h->model);
-        h->last_quiet_window = h->plan_warmup;
+    if (g.quiet_window > 0) {
         a.nan_bits = h->nan_bits.p; a.nan_words = h->nan_words; a.quiet_flag = h->quiet_flag.p;
-        a.quiet_w = (h->plan_warmup + U - 1) / U;
-        // (testing: a memory of its own, deliberately short -- the check at the switch has to notice; a retry doubles it like a warm-up)
-        if (h->knobs.quiet_window > 0) { a.quiet_w = (h->knobs.quiet_window * h->window_boost + U - 1) / U; h->last_quiet_window = h->knobs.quiet_window * h->window_boost; }
-        a.quiet_b0 = (a.gain_last + SHARED_U - 1) / SHARED_U * SHARED_U / U + 1;
+        a.quiet_w = g.quiet_w; a.quiet_b0 = g.quiet_b0;
         for (int i = 0; i < 12; i++) a.quiet_p[i] = h->stat_p[i];
         a.quiet_ld = h->stat_ld;
         for (int j = 0; j < NDIRP; j++) a.quiet_gld[j] = h->stat_gld[j];
@@ -491,92 +399,18 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
     // The finalising work inside the main launch (fused_finalize_wave, ssde_device.hpp): the shared-covariance kernel alone on the
     // batch (no group on the general kernel, no drift columns); SSDE_FUSED_FINALIZE=0: the two-launch form (A/B -- bitwise the same)
     const bool fused = h->use_shared && !h->drift && h->n_clean_groups == h->n_groups && !h->hess_req && h->fuse_words.p && h->knobs.fused_finalize.value_or(false);
-    // the reduction's arguments: which accumulator of which part feeds which output slot (needed BEFORE the main launch when the
-    // finalising work is fused into it)
-    auto fill_ra = [&]() {
-        for (int i = 0; i < 4; i++) { ra.add[i] = add[i]; ra.add_slot[i] = -1; }
-        if (h->use_shared) {
-            ra.add_slot[0] = 0;
-            if (order >= 1) {
-                const int pj[NDIRP] = {0, L.off_fe + L.fe_off[h->d], h->q > h->d + 1 ? L.off_fe + L.fe_off[h->d + 1] : 0};
-                for (int j = 0; j < NDIRP; j++)
-                    if (pj[j] < L.n_full && !h->fixed[pj[j]] && (j < 2 || h->q > h->d + 1)) ra.add_slot[1 + j] = (int16_t)(1 + pj[j]);
-            }
-        }
-        const int nacc = h->cv_adj ? adj_nacc(h->model, h->d, h->n_stream_cols, a.cv_mu_cols != 0)
-                       : h->drift == 3 ? 2 + CV_KC + h->d : 4 + h->d + (h->drift ? h->n_stream_cols : 0);
-        const int ncr = (a.dual && a.n_chunks_d > a.n_chunks) ? a.n_chunks_d : a.n_chunks;     // windows the final sums run over
-        ra.n_parts = a.n_parts * ncr; ra.nacc = nacc; ra.n_blocks = h->n_groups;
-        ra.n_value_parts = ncr; ra.chunks_per_part = ncr;
-        ra.chk = h->chk.p; ra.n_chk = a.n_chunks > 1 ? a.n_parts * (a.n_chunks - 1) * h->n_groups : 0;
-        // (the bulk's forms are one more window, by value: lag_forms_into)
-        if (order >= 1 && h->cv_adj) {
-            // accumulators of k_iso_adj.hip: [value | log sigma_obs | mu_a | par[d] | par[d + 1] | per streamed column: par[d], par[d + 1] (, mu_a)]
-            const int nkp = h->model == SSDE_MODEL_BM_SSM ? 1 : 2, nk = adj_nk(h->model, h->d, a.cv_mu_cols != 0);
-            if (!h->fixed[0] && !h->has_h) ra.map[0] = 1;
-            for (auto& sl : h->slots) {
-                if (h->fixed[sl.pidx]) continue;
-                const int kind = sl.par_j < h->d ? nkp + sl.par_j : sl.par_j - h->d;
-                const int k = sl.col >= 0 ? 4 + h->d + sl.col * nk + kind : (sl.par_j < h->d ? 2 + sl.par_j : 2 + h->d + (sl.par_j - h->d));
-                ra.map[k - 1] = (int16_t)(1 + sl.pidx);
-            }
-        } else
-        if (order >= 1 && h->drift == 3) {
-            // accumulators of k_iso_colvar.hip, per part: [value | the part's columns | mu_1 .. mu_d | log sigma_obs]
-            for (int p = 0; p < CV_WAVES; p++) {
-                for (int k = 0; k < CV_KC; k++) {
-                    const int pidx = h->cv_pidx[(size_t)p * CV_KC + k];
-                    if (pidx >= 0) ra.map[p * (nacc - 1) + k] = (int16_t)(1 + pidx);
-                }
-                if (p == h->cv_mu_part)
-                    for (auto& sl : h->slots)
-                        if (sl.par_j < h->d && sl.col < 0 && !h->fixed[sl.pidx]) ra.map[p * (nacc - 1) + CV_KC + sl.par_j] = (int16_t)(1 + sl.pidx);
-                if (p == h->cv_sig_part) ra.map[p * (nacc - 1) + CV_KC + h->d] = 1;
-            }
-        } else
-        if (order >= 1 && h->drift) {
-            // accumulators of k_iso_drift.hip: [value | sigma_obs | mu intercepts | par d | par d+1 | streamed columns]
-            if (!h->fixed[0]) ra.map[0] = 1;
-            for (auto& sl : h->slots) {
-                if (h->fixed[sl.pidx]) continue;
-                const int k = sl.col >= 0 ? 4 + h->d + sl.col : (sl.par_j < h->d ? 2 + sl.par_j : sl.par_j == h->d ? 2 + h->d : 3 + h->d);
-                ra.map[k - 1] = (int16_t)(1 + sl.pidx);
-            }
-        } else
-        if (order >= 1) {
-            for (int p = 0; p < a.n_parts; p++)
-                for (int k = 1; k < nacc; k++) {
-                    // accumulators are ordered like the constant-coefficient parameter vector: sigma_obs, one per SDE parameter
-                    const int j = k - 2;     // SDE parameter of accumulator k (k == 1: log_sigma_obs)
-                    if (j >= h->q) continue;
-                    const int pidx = j < 0 ? 0 : L.off_fe + L.fe_off[j];
-                    if (pidx < L.n_full && !h->fixed[pidx]) ra.map[p * (nacc - 1) + (k - 1)] = (int16_t)(1 + pidx);
-                }
-        }
-    };
     if (h->use_shared) {
         // two independent launches (NaN-free groups on the shared-covariance kernel, NaN-carrying groups on
         // the general kernel): fork onto a side stream so they share the chip, join before the hand-over check
         const bool any_dirty = h->n_clean_groups < h->n_groups;
         IsoArgs ad = a;                      // the general launch: this plan, or -- mixed batch -- one of its own
-        if (any_dirty && h->want_chunks_d > 0 && a.n_chunks > 1 && h->max_chunks > 1 && !h->gave_up) {
-            int nc = h->want_chunks_d;
-            while (nc > 1 && (h->glen_max / nc) < 2 * a.window) nc--;
-            if (nc > 1) {
-                ad.n_chunks = nc; ad.t0 = 0; ad.t0_delta = 0;
-                // window 0 carries every direction and has no warm-up: the balance of the all-general case (below)
-                const bool can_derive = order >= 1 && a.derive && (a.part_mask[0] & DIR_SIG) &&
-                                        (a.part_mask[0] & (h->model == SSDE_MODEL_BM_SSM ? DIR_P1 : DIR_P2));
-                const double r = can_derive ? W0_RATIO : 1.0;
-                const double L0 = ((double)h->glen_max / (nc - 1) + a.window) / (r + 1.0 / (nc - 1));
-                const int t0 = (int)(L0 / WIN_ALIGN) * WIN_ALIGN;
-                if (t0 >= 2 * WIN_ALIGN && t0 + 2 * a.window < h->glen_max) ad.t0 = t0;
-                a.dual = 1; a.n_chunks_d = ad.n_chunks; a.window_d = ad.window; a.t0_d = ad.t0; a.t0_delta_d = ad.t0_delta;
-                a.dirty_groups = h->dirty_groups.p; a.n_dirty_groups = h->n_dirty_groups;
-                ad.dirty_groups = h->dirty_groups.p; ad.n_dirty_groups = h->n_dirty_groups; ad.use_group_list = 1;
-                // the final sums run over the longer of the two plans: the slots the shorter one does not write must be zero
-                HIPCHK(h, hipMemsetAsync(h->partials.p, 0, (size_t)std::max(a.n_chunks, ad.n_chunks) * (4 + h->d) * h->n_groups * 8, s));
-            }
+        if (g.dual) {
+            ad.n_chunks = g.n_chunks_d; ad.t0 = g.t0_d; ad.t0_delta = 0;
+            a.dual = 1; a.n_chunks_d = ad.n_chunks; a.window_d = ad.window; a.t0_d = ad.t0; a.t0_delta_d = ad.t0_delta;
+            a.dirty_groups = h->dirty_groups.p; a.n_dirty_groups = h->n_dirty_groups;
+            ad.dirty_groups = h->dirty_groups.p; ad.n_dirty_groups = h->n_dirty_groups; ad.use_group_list = 1;
+            // the final sums run over the longer of the two plans: the slots the shorter one does not write must be zero
+            HIPCHK(h, hipMemsetAsync(h->partials.p, 0, (size_t)std::max(a.n_chunks, ad.n_chunks) * (4 + h->d) * h->n_groups * 8, s));
         }
         IsoArgs b = a;
         b.group_mode = 2;
@@ -602,7 +436,7 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
         if (h->drift) HIPCHK(h, launch_iso_drift(h->model, h->d, b, s, h->stamps ? h->ev_k0 : nullptr, h->stamps ? h->ev_k1 : nullptr));
         else {
             if (fused) {
-                fill_ra();
+                fill_reduce_args(h, a, order, add, ra);
                 ra.kfast = 1;
                 b.fused = 1;
                 b.fuse_arrive = h->fuse_words.p + 4; b.fuse_done = h->fuse_words.p;
@@ -615,7 +449,7 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
         }
         h->last_kernel_id = h->drift ? SSDE_KERNEL_ISO_DRIFT : any_dirty ? SSDE_KERNEL_ISO_MIXED : SSDE_KERNEL_ISO_SHARED;
         h->ev_k_valid = h->stamps;
-        h->last_s_stat = h->drift ? -1 : (a.gain_last + SHARED_U - 1) / SHARED_U * SHARED_U;
+        h->last_s_stat = h->drift ? -1 : g.s_stat;
         if (any_dirty) HIPCHK(h, hipStreamWaitEvent(s, h->ev_join[1], 0));
     } else {
         if (h->stamps) HIPCHK(h, hipEventRecord(h->ev_k0, s));
@@ -634,7 +468,7 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
                 const int units = (h->glen_max + WIN_ALIGN - 1) / WIN_ALIGN;
                 a.adj_tail = a.window;
                 a.adj_diag = h->knobs.adj_diag;
-                if (h->knobs.adj_tail) a.adj_tail = (int)std::min<int64_t>((int64_t)*h->knobs.adj_tail * h->window_boost, h->glen_max);      // (testing)
+                if (h->knobs.adj_tail) a.adj_tail = (int)std::min<int64_t>((int64_t)*h->knobs.adj_tail * policy.boost(), h->glen_max);      // (testing)
                 const int len = (units / a.n_chunks + 1) * WIN_ALIGN + (a.n_chunks > 1 ? a.adj_tail : 0);
                 a.adj_ckpt_stride = (int64_t)((len + cb - 1) / cb + 1) * nst * WAVE;
                 const size_t need = order >= 1 ? (size_t)items * (size_t)a.adj_ckpt_stride : (size_t)WAVE;
@@ -666,7 +500,7 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
         h->last_s_stat = -1;
     }
     if (h->knobs.trace) { const double t = tick(); h->trace_us[2] += t - tk0; tk0 = t; }
-    if (!fused) fill_ra();
+    if (!fused) fill_reduce_args(h, a, order, add, ra);
     if (!fused && lag_K > 0) { const int st = lag_forms_into(h, a, order, lag_K, a.n_chunks, ra); if (st) return st; }     // (the head is running: this overlaps it)
     // the hand-over checks and the final sums in one launch (unless the main launch has done them)
     if (!fused) HIPCHK(h, launch_iso_finalize(h->model, h->d, a, ra, s));

@@ -144,44 +144,6 @@ int build_tv(const ssde_desc* d, ssde_handle* h, const std::vector<int64_t>& sta
     return SSDE_OK;
 }
 
-// spectral radius of the stationary closed-loop matrix T - K Z for constant parameters (see plan_windows)
-double closed_loop_rho(int model, double dt, double p1, double p2, double hobs, const double* p0) {
-    if (!(dt > 0.0) || !std::isfinite(dt)) return 1.0;
-    if (model == SSDE_MODEL_CTCRW) {
-        const double tau = exp(p1), nu = exp(p2);
-        CtcrwTrans tr;
-        ctcrw_trans(dt, tau, 1.0 / tau, 2.0 * nu / sqrt(M_PI * tau), tr);
-        double p11 = p0[0], p12 = p0[1], p22 = p0[2], k1 = 0, k2 = 0;
-        for (int it = 0; it < 20000; it++) {
-            const double F = p11 + hobs, iF = 1.0 / F;
-            const double tp11 = p11 + tr.t12 * p12, tp12 = p12 + tr.t12 * p22, tp21 = tr.e * p12, tp22 = tr.e * p22;
-            k1 = tp11 * iF; k2 = tp21 * iF;
-            const double n11 = tp11 * (1.0 - k1) + tp12 * tr.t12 + tr.q11, n12 = -tp11 * k2 + tp12 * tr.e + tr.q12,
-                         n22 = -tp21 * k2 + tp22 * tr.e + tr.q22;
-            const double ch = std::fabs(n11 - p11) + std::fabs(n12 - p12) + std::fabs(n22 - p22);
-            p11 = n11; p12 = n12; p22 = n22;
-            if (ch <= 1e-15 * (std::fabs(p11) + std::fabs(p22))) break;
-        }
-        const double trc = (1.0 - k1) + tr.e, det = (1.0 - k1) * tr.e + k2 * tr.t12;
-        const double disc = trc * trc - 4.0 * det;
-        return disc >= 0.0 ? std::max(std::fabs(0.5 * (trc + std::sqrt(disc))), std::fabs(0.5 * (trc - std::sqrt(disc))))
-                           : std::sqrt(std::fabs(det));
-    }
-    ScalTrans tr;
-    if (model == SSDE_MODEL_OU_SSM) ou_trans(dt, exp(p1), exp(p2), tr);
-    else bm_trans(dt, exp(p1), tr);
-    double p = p0[0], k = 0;
-    for (int it = 0; it < 20000; it++) {
-        const double F = p + hobs, tp = tr.t * p;
-        k = tp / F;
-        const double np_ = tp * (tr.t - k) + tr.q;
-        const double ch = std::fabs(np_ - p);
-        p = np_;
-        if (ch <= 1e-15 * std::fabs(p)) break;
-    }
-    return std::fabs(tr.t - k);
-}
-
 // Time windows of the tv path.  The warm-up length comes from the slowest-forgetting corner of the
 // parameter ranges the LAST evaluation's pre-pass saw (dt, par[d], par[d+1]); the device-side
 // hand-over check decides whether it was enough.  Rebuilds the work-item tables when the plan changes.
@@ -211,14 +173,9 @@ int tv_plan(ssde_handle* h, double hobs, hipStream_t s) {   // hobs: sigma_obs^2
                 rho = std::max(rho, std::isfinite(r) ? r : 1.0);
             }
         if (ok && rho < 0.9995) {
-            int64_t w = (int64_t)std::ceil(std::log(1e-18) / std::log(std::max(rho, 1e-300))) + 16;
             // (full-covariance lanes: the isotropic estimate of rho is optimistic for them -- measured on C1 with error ellipses: checks of
             //  1e-12 .. 7e-12 against the 1e-11 tolerance, two failures in 400 evaluations and 32 evaluations on a four-fold plan after each)
-            if (h->tv_dense) w += WIN_ALIGN;
-            w = std::max<int64_t>(w, 16);
-            if (h->knobs.window) w = *h->knobs.window;
-            w *= h->window_boost;
-            w = (w + WIN_ALIGN - 1) / WIN_ALIGN * WIN_ALIGN;
+            const int64_t w = align_rows(warmup_rows(rho, 16 + (h->tv_dense ? WIN_ALIGN : 0), h->knobs.window, h->policy().boost()), WIN_ALIGN);
             if (2 * w <= h->glen_max) W = (int)w;
         }
     }

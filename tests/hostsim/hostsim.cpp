@@ -13,6 +13,7 @@
 #include "../../smoothsde_amd/csrc/ssde_tv.hpp"
 #include "../../smoothsde_amd/csrc/ssde_adj.hpp"
 #include "../../smoothsde_amd/csrc/ssde_knobs.hpp"
+#include "../../smoothsde_amd/csrc/ssde_windows.hpp"
 #include <sstream>
 #include <vector>
 
@@ -324,6 +325,107 @@ int hostsim_knobs(int win_align, char* buf, int cap) {
     const std::string t = o.str();
     if ((int)t.size() < cap) memcpy(buf, t.c_str(), t.size() + 1);
     return (int)t.size();
+}
+
+}  // extern "C"
+
+// ---- the window policy (csrc/ssde_windows.hpp): thin entry points for tests/test_windows_host.py ---------------------------------
+namespace {
+using namespace ssde_engine;
+
+// the order of hostsim_lib.WINDOW_FACTS; window < 0: SSDE_WINDOW unset
+WindowFacts facts_from(const double* v) {
+    WindowFacts f;
+    f.model = (int)v[0]; f.uniform_dt = v[1] != 0.0; f.dt_uniform = v[2]; f.dt_min = v[3]; f.dt_max = v[4];
+    f.max_chunks = (int)v[5]; f.want_chunks = (int)v[6]; f.want_chunks_d = (int)v[7]; f.glen_max = (int)v[8]; f.n_groups = (int)v[9];
+    f.use_shared = v[10] != 0.0; f.drift = (int)v[11]; f.cv_adj = v[12] != 0.0; f.cv_one_wave = v[13] != 0.0; f.chunks_forced = v[14] != 0.0;
+    if (v[15] >= 0.0) f.window = (int)v[15];
+    f.cv_eta_lo[0] = v[16]; f.cv_eta_lo[1] = v[17]; f.cv_eta_hi[0] = v[18]; f.cv_eta_hi[1] = v[19];
+    f.any_dirty = v[20] != 0.0; f.quiet_ok = v[21] != 0.0; f.lag_ready = v[22] != 0.0; f.quiet_window = (int)v[23]; f.block_rows = (int)v[24];
+    return f;
+}
+WindowConsts consts_from(const int* c) { return WindowConsts{c[0], c[1], c[2], c[3]}; }
+WindowParams params_from(const double* v) { return WindowParams{v[0], v[1], v[2], v[3], {v[4], v[5], v[6]}}; }
+void put_plan(const WindowPlan& p, double* out) { out[0] = p.n_chunks; out[1] = p.window; out[2] = p.warmup; out[3] = p.rho; }
+
+// a policy with one stand-in engine's chunk limits under it
+struct PolicySim {
+    WindowPolicy p;
+    WindowPolicy::Call c;
+    int max_chunks = 1, want_chunks = 1, saved_max_chunks = 0, saved_want_chunks = 0;
+};
+}  // namespace
+
+extern "C" {
+
+double hostsim_closed_loop_rho(int model, double dt, double p1, double p2, double hobs, const double* p0) {
+    return closed_loop_rho(model, dt, p1, p2, hobs, p0);
+}
+// the transformed parameters of an evaluation at working-scale p1 = par[d], p2 = par[d + 1], decoded as eval_iso decodes them
+void hostsim_window_params(int model, double p1, double p2, double hobs, const double* p0, double* out) {
+    double tau = 0.0, beta = 0.0, sigma = 0.0;
+    if (model == M_CTCRW) { tau = exp(p1); const double nu = exp(p2); beta = 1.0 / tau; sigma = 2.0 * nu / sqrt(M_PI * tau); }
+    else if (model == M_OU_SSM) { tau = exp(p1); sigma = exp(p2); }
+    else sigma = exp(p1);
+    out[0] = tau; out[1] = beta; out[2] = sigma; out[3] = hobs; out[4] = p0[0]; out[5] = p0[1]; out[6] = p0[2];
+}
+// out = [n_chunks, window, warmup, rho]
+void hostsim_window_plan(const double* facts, const int* consts, const double* params, int boost, double* out) {
+    put_plan(plan_windows(facts_from(facts), consts_from(consts), params_from(params), boost), out);
+}
+// ev = [n_parts, can_derive, hess_req, gain_last, gain_usable]; out = the first plan (4), the plan in force (4), then
+// [n_chunks, window, t0, t0_delta, dual, n_chunks_d, t0_d, lag_K, s_stat, quiet_window, quiet_w, quiet_b0]
+void hostsim_window_geometry(const double* facts, const int* consts, const double* params, int boost, int gave_up, const double* ev,
+                             double* out) {
+    const WindowFacts f = facts_from(facts);
+    const WindowConsts c = consts_from(consts);
+    const WindowParams a = params_from(params);
+    const WindowPlan first = plan_windows(f, c, a, boost);
+    WindowEval e;
+    e.n_parts = (int)ev[0]; e.can_derive = ev[1] != 0.0; e.hess_req = ev[2] != 0.0; e.gain_last = (int)ev[3]; e.gain_usable = ev[4] != 0.0;
+    const WindowGeometry g = window_geometry(f, c, a, first, boost, gave_up != 0, e);
+    put_plan(first, out); put_plan(g.plan, out + 4);
+    const double v[12] = {(double)g.n_chunks, (double)g.window, (double)g.t0, (double)g.t0_delta, g.dual ? 1.0 : 0.0, (double)g.n_chunks_d,
+                          (double)g.t0_d, (double)g.lag_K, (double)g.s_stat, (double)g.quiet_window, (double)g.quiet_w, (double)g.quiet_b0};
+    for (int i = 0; i < 12; i++) out[8 + i] = v[i];
+}
+// the aligned warm-up of a planner (knob < 0: SSDE_WINDOW unset)
+int64_t hostsim_warmup(double rho, int slack, int knob, int boost, int align) {
+    return align_rows(warmup_rows(rho, slack, knob >= 0 ? std::optional<int>(knob) : std::nullopt, boost), align);
+}
+int hostsim_balanced_window0(int glen, int nc, int window, int can_derive, int win_align) {
+    return balanced_window0(glen, nc, window, can_derive != 0, win_align);
+}
+
+void* hostsim_policy_new(int max_chunks, int want_chunks) {
+    PolicySim* s = new PolicySim();
+    s->max_chunks = max_chunks; s->want_chunks = want_chunks;
+    return s;
+}
+void hostsim_policy_free(void* h) { delete (PolicySim*)h; }
+void hostsim_policy_begin(void* h) { ((PolicySim*)h)->c = WindowPolicy::Call(); }
+// one attempt's outcome; applies what the verdict asks of the engines; returns retry | action << 1
+int hostsim_policy_attempt(void* h, double check, int finite, int one_window, int dist, int replans) {
+    PolicySim* s = (PolicySim*)h;
+    const WindowPolicy::Verdict v = s->p.after_attempt(s->c, {check, finite != 0, one_window != 0, dist != 0, replans != 0});
+    apply_chunks(*s, v.engines);
+    return (v.retry ? 1 : 0) | ((int)v.engines << 1);
+}
+int hostsim_policy_end(void* h, int finite, int forced) {
+    PolicySim* s = (PolicySim*)h;
+    const ChunkAction a = s->p.end_call(s->c, finite != 0, forced != 0);
+    apply_chunks(*s, a);
+    return (int)a;
+}
+void hostsim_policy_widen(void* h, int factor) { ((PolicySim*)h)->p.widen(factor); }
+void hostsim_policy_relax(void* h) { ((PolicySim*)h)->p.relax(); }
+// the order of hostsim_lib.POLICY_STATE
+void hostsim_policy_state(void* h, double* out) {
+    const PolicySim* s = (const PolicySim*)h;
+    const double v[15] = {(double)s->p.window_boost, s->p.gave_up ? 1.0 : 0.0, (double)s->p.calm, (double)s->p.cooldown, (double)s->p.probe_from,
+                          s->p.probing ? 1.0 : 0.0, s->p.check_floor, s->p.check_max, s->p.last_check, (double)s->p.n_retries,
+                          (double)s->c.attempt, (double)s->max_chunks, (double)s->want_chunks, (double)s->saved_max_chunks, (double)s->saved_want_chunks};
+    for (int i = 0; i < 15; i++) out[i] = v[i];
 }
 
 }  // extern "C"

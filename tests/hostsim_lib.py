@@ -35,6 +35,27 @@ def load():
         lib.hostsim_kalman_adj_full.restype = C.c_int
         lib.hostsim_knobs.argtypes = [C.c_int, C.c_char_p, C.c_int]
         lib.hostsim_knobs.restype = C.c_int
+        _ip = C.POINTER(C.c_int)
+        lib.hostsim_closed_loop_rho.argtypes = [C.c_int] + [C.c_double] * 4 + [_dp]
+        lib.hostsim_closed_loop_rho.restype = C.c_double
+        lib.hostsim_window_params.argtypes = [C.c_int] + [C.c_double] * 3 + [_dp, _dp]
+        lib.hostsim_window_plan.argtypes = [_dp, _ip, _dp, C.c_int, _dp]
+        lib.hostsim_window_geometry.argtypes = [_dp, _ip, _dp, C.c_int, C.c_int, _dp, _dp]
+        lib.hostsim_warmup.argtypes = [C.c_double] + [C.c_int] * 4
+        lib.hostsim_warmup.restype = C.c_int64
+        lib.hostsim_balanced_window0.argtypes = [C.c_int] * 5
+        lib.hostsim_balanced_window0.restype = C.c_int
+        lib.hostsim_policy_new.argtypes = [C.c_int, C.c_int]
+        lib.hostsim_policy_new.restype = C.c_void_p
+        lib.hostsim_policy_free.argtypes = [C.c_void_p]
+        lib.hostsim_policy_begin.argtypes = [C.c_void_p]
+        lib.hostsim_policy_attempt.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int]
+        lib.hostsim_policy_attempt.restype = C.c_int
+        lib.hostsim_policy_end.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        lib.hostsim_policy_end.restype = C.c_int
+        lib.hostsim_policy_widen.argtypes = [C.c_void_p, C.c_int]
+        lib.hostsim_policy_relax.argtypes = [C.c_void_p]
+        lib.hostsim_policy_state.argtypes = [C.c_void_p, _dp]
         _LIB = lib
     return _LIB
 
@@ -45,6 +66,101 @@ def knobs(win_align):
     n = load().hostsim_knobs(win_align, buf, len(buf))
     assert 0 < n < len(buf)
     return dict(line.split("=", 1) for line in buf.value.decode().splitlines())
+
+
+# ---- the window policy (csrc/ssde_windows.hpp) ----------------------------------------------------------------------------------
+# WindowFacts, in the order hostsim.cpp reads them; window = -1: SSDE_WINDOW unset
+WINDOW_FACTS = dict(model=4, uniform_dt=1, dt_uniform=1.0, dt_min=1.0, dt_max=1.0, max_chunks=9, want_chunks=8, want_chunks_d=0,
+                    glen_max=4000, n_groups=16, use_shared=0, drift=0, cv_adj=0, cv_one_wave=0, chunks_forced=0, window=-1,
+                    eta_lo0=0.0, eta_lo1=0.0, eta_hi0=0.0, eta_hi1=0.0, any_dirty=0, quiet_ok=0, lag_ready=0, quiet_window=0,
+                    block_rows=4)
+WINDOW_EVAL = dict(n_parts=1, can_derive=1, hess_req=0, gain_last=40, gain_usable=1)
+GEOMETRY_OUT = ("n_chunks", "window", "t0", "t0_delta", "dual", "n_chunks_d", "t0_d", "lag_K", "s_stat", "quiet_window", "quiet_w",
+                "quiet_b0")
+POLICY_STATE = ("window_boost", "gave_up", "calm", "cooldown", "probe_from", "probing", "check_floor", "check_max", "last_check",
+                "n_retries", "attempt", "max_chunks", "want_chunks", "saved_max_chunks", "saved_want_chunks")
+CHUNK_ACTIONS = ("none", "sequential_saving", "sequential", "restore")
+
+
+def _vec(defaults, over):
+    unknown = set(over) - set(defaults)
+    assert not unknown, unknown
+    return np.array([float(over.get(k, v)) for k, v in defaults.items()])
+
+
+def closed_loop_rho(model, dt, p1, p2, hobs, p0):
+    p0 = np.asarray(p0, dtype=np.float64)
+    return load().hostsim_closed_loop_rho(model, dt, p1, p2, hobs, p0.ctypes.data_as(_dp))
+
+
+def window_params(model, p1, p2, hobs, p0):
+    """[tau, beta, sigma, h, p0[3]] at working-scale par[d] = p1, par[d + 1] = p2, decoded as an evaluation decodes them."""
+    p0 = np.asarray(p0, dtype=np.float64)
+    out = np.zeros(7)
+    load().hostsim_window_params(model, p1, p2, hobs, p0.ctypes.data_as(_dp), out.ctypes.data_as(_dp))
+    return out
+
+
+def _plan_dict(v):
+    return dict(n_chunks=int(v[0]), window=int(v[1]), warmup=int(v[2]), rho=float(v[3]))
+
+
+def window_plan(consts, params, boost=1, **facts):
+    """plan_windows: consts = (WIN_ALIGN, SHARED_U, LAG_A, LAG_KMAX)"""
+    f, c, out = _vec(WINDOW_FACTS, facts), np.asarray(consts, dtype=np.int32), np.zeros(4)
+    load().hostsim_window_plan(f.ctypes.data_as(_dp), c.ctypes.data_as(C.POINTER(C.c_int)), params.ctypes.data_as(_dp), boost,
+                               out.ctypes.data_as(_dp))
+    return _plan_dict(out)
+
+
+def window_geometry(consts, params, boost=1, gave_up=False, ev=None, **facts):
+    """plan_windows, then window_geometry: the geometry's fields, with `first` (the plan) and `plan` (the plan in force)"""
+    f, c, out = _vec(WINDOW_FACTS, facts), np.asarray(consts, dtype=np.int32), np.zeros(20)
+    e = _vec(WINDOW_EVAL, ev or {})
+    load().hostsim_window_geometry(f.ctypes.data_as(_dp), c.ctypes.data_as(C.POINTER(C.c_int)), params.ctypes.data_as(_dp), boost,
+                                   int(gave_up), e.ctypes.data_as(_dp), out.ctypes.data_as(_dp))
+    g = {k: int(v) for k, v in zip(GEOMETRY_OUT, out[8:])}
+    g["first"], g["plan"] = _plan_dict(out[:4]), _plan_dict(out[4:8])
+    return g
+
+
+class WindowPolicy:
+    """WindowPolicy over one stand-in engine's chunk limits; call() is the loop ssde_eval runs around an evaluation."""
+
+    def __init__(self, max_chunks=9, want_chunks=8):
+        self._lib = load()
+        self._h = self._lib.hostsim_policy_new(max_chunks, want_chunks)
+
+    def __del__(self):
+        self._lib.hostsim_policy_free(self._h)
+
+    def state(self):
+        out = np.zeros(len(POLICY_STATE))
+        load().hostsim_policy_state(self._h, out.ctypes.data_as(_dp))
+        return {k: (float(v) if k.startswith(("check", "last_check")) else int(v)) for k, v in zip(POLICY_STATE, out)}
+
+    def widen(self, factor):
+        load().hostsim_policy_widen(self._h, factor)
+
+    def relax(self):
+        load().hostsim_policy_relax(self._h)
+
+    def call(self, checks, finite=True, one_window=False, dist=False, replans=False, forced=False):
+        """One ssde_eval: `checks` is what each attempt's evaluation shows (a callable of the state, or a sequence whose last
+        entry repeats).  Returns the actions asked of the engines, in order, and the number of evaluations run."""
+        lib = load()
+        lib.hostsim_policy_begin(self._h)
+        actions, n = [], 0
+        while True:
+            chk = checks(self.state()) if callable(checks) else checks[min(n, len(checks) - 1)]
+            n += 1
+            r = lib.hostsim_policy_attempt(self._h, chk, int(finite), int(one_window), int(dist), int(replans))
+            actions.append(CHUNK_ACTIONS[r >> 1])
+            if not (r & 1):
+                break
+            assert n < 100
+        actions.append(CHUNK_ACTIONS[lib.hostsim_policy_end(self._h, int(finite), int(forced))])
+        return [a for a in actions if a != "none"], n
 
 
 def kalman_adj_full(pb, par):
