@@ -33,6 +33,9 @@ def load():
         lib.hostsim_kalman_adj_full.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int64, _lp, _lp, _dp, _dp, _dp,
                                                 C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp]
         lib.hostsim_kalman_adj_full.restype = C.c_int
+        lib.hostsim_smooth.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _lp, _lp, _dp, _dp, _dp, _dp, C.c_double,
+                                       _dp, _dp, _dp, _dp, _dp]
+        lib.hostsim_smooth.restype = C.c_int
         lib.hostsim_knobs.argtypes = [C.c_int, C.c_char_p, C.c_int]
         lib.hostsim_knobs.restype = C.c_int
         _ip = C.POINTER(C.c_int)
@@ -161,6 +164,43 @@ class WindowPolicy:
             assert n < 100
         actions.append(CHUNK_ACTIONS[lib.hostsim_policy_end(self._h, int(finite), int(forced))])
         return [a for a in actions if a != "none"], n
+
+
+def smooth(pb, par):
+    """The fixed-interval smoother by the lane math of csrc/ssde_smooth.hpp over csrc/ssde_dense.hpp (smooth_record_row ->
+    dense_step per state row, then smooth_back_row over the records), one track after the other: what smooth_ref returns,
+    {"mean": n x sdim, "cov": n x sdim x sdim, "resid": n x d}, NaN where no state / no update exists.  The linear predictors
+    are formed here (refimpl.linear_predictor), a0 and P0 default as the engine's create path sets them."""
+    import torch
+    from refimpl import linear_predictor
+    from smoothsde_amd.capi import MODEL_CODES
+    lib = load()
+    d, sd, n = pb.n_dim, pb.sdim, pb.n
+    par = np.asarray(par, dtype=np.float64)
+    parmat = np.ascontiguousarray(linear_predictor(pb, torch.as_tensor(par)).detach().numpy())          # n x q
+    row0 = np.ascontiguousarray(pb.seg_start, dtype=np.int64)
+    nrows = np.diff(np.append(pb.seg_start, n)).astype(np.int64)
+    z = (lambda a: 2 * a) if pb.model == "CTCRW" else (lambda a: a)
+    if pb.P0 is None:
+        P0 = np.diag([1.0, 10.0] * d) if pb.model == "CTCRW" else 10.0 * np.eye(d)
+    else:
+        P0 = np.asarray(pb.P0, dtype=np.float64)
+    p0f = np.ascontiguousarray(P0.ravel(order="F"))
+    if pb.a0 is None:
+        a0 = np.zeros((pb.n_seg, sd))
+        for a in range(d):
+            a0[:, z(a)] = pb.obs[row0, a]
+    else:
+        a0 = np.ascontiguousarray(pb.a0, dtype=np.float64)
+    harr = None if pb.H is None else np.ascontiguousarray(np.moveaxis(np.asarray(pb.H, dtype=np.float64), 2, 0))   # n x d x d
+    mean, cov, res = np.full((n, sd), np.nan), np.full((n, sd, sd), np.nan), np.full((n, d), np.nan)
+    st = lib.hostsim_smooth(MODEL_CODES[pb.model], d, int(pb.na_mode == 1), n, pb.n_seg, row0.ctypes.data_as(_lp),
+                            nrows.ctypes.data_as(_lp), pb.times.ctypes.data_as(_dp), pb.obs.ctypes.data_as(_dp),
+                            parmat.ctypes.data_as(_dp), None if harr is None else harr.ctypes.data_as(_dp),
+                            float(np.exp(par[0]) ** 2), p0f.ctypes.data_as(_dp), a0.ctypes.data_as(_dp),
+                            mean.ctypes.data_as(_dp), cov.ctypes.data_as(_dp), res.ctypes.data_as(_dp))
+    assert st == 0
+    return {"mean": mean, "cov": cov, "resid": res}
 
 
 def kalman_adj_full(pb, par):

@@ -78,6 +78,29 @@ def _setup(pb, par):
     return pm, dt, Z, H, P0, bounds, np.array(a0), na
 
 
+def _forward(C, v):
+    """C^-1 v by forward substitution (m x d x d lower triangular, m x d): component i reads v[: i + 1] only, as the kernel's does."""
+    e = np.zeros(v.shape)
+    for i in range(v.shape[1]):
+        e[:, i] = (v[:, i] - np.einsum("mk,mk->m", C[:, i, :i], e[:, :i])) / C[:, i, i]
+    return e
+
+
+def _whiten(F, v):
+    """C^-1 v per row, C the lower Cholesky factor of F (m x d x d); NaN on a row whose F has none (OU_SSM / BM_SSM update
+    whenever |det F| > 0, so a negative F reaches here: the kernel's sqrt gives NaN there)."""
+    try:
+        return _forward(np.linalg.cholesky(F), v)
+    except np.linalg.LinAlgError:
+        e = np.full(v.shape, np.nan)
+        for k in range(F.shape[0]):
+            try:
+                e[k] = _forward(np.linalg.cholesky(F[k:k + 1]), v[k:k + 1])[0]
+            except np.linalg.LinAlgError:
+                pass
+        return e
+
+
 def smooth_ref(pb, par):
     """{"mean": n x sdim, "cov": n x sdim x sdim, "resid": n x d, "pred_cov": the filter's P_j}, NaN where the definitions say so."""
     d, sd, n, model = pb.n_dim, pb.sdim, pb.n, pb.model
@@ -114,8 +137,7 @@ def smooth_ref(pb, par):
         P_new = TP @ T.transpose(0, 2, 1) + Q - TP @ Z.T @ K.transpose(0, 2, 1)
         if d > 1:
             P_new = 0.5 * (P_new + P_new.transpose(0, 2, 1))
-        C = np.linalg.cholesky(np.where(upd[:, None, None], 0.5 * (Fs + Fs.transpose(0, 2, 1)), np.eye(d)[None]))
-        e = np.linalg.solve(C, v[:, :, None])[:, :, 0]
+        e = _whiten(np.where(upd[:, None, None], 0.5 * (Fs + Fs.transpose(0, 2, 1)), np.eye(d)[None]), v)
         rec.append((rows, act, a.copy(), P.copy(), v, Fi, K, T))
         res[rows[act & upd]] = e[act & upd]
         pred[rows[act]] = P[act]
