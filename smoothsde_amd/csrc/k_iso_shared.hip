@@ -55,7 +55,7 @@ hipError_t launch_iso_shared(int model, int d, const IsoArgs& a0, const ReduceAr
     if (a0.n_parts != 1) return hipErrorInvalidValue;
     IsoArgs a = a0;
     const int g8 = (a.tv.n_groups + 7) / 8;
-    const int n_grid_chunks = a.t0 > 0 ? a.n_chunks - 1 : a.n_chunks;
+    const int n_grid_chunks = (a.t0 > 0 && a.t0_delta > 0) ? a.n_chunks - 1 : a.n_chunks;      // (t0_delta == 0: window 0 has a wave of its own)
     dim3 grid((g8 * 8 * n_grid_chunks + WG_WAVES - 1) / WG_WAVES);
     if (grid.x == 0) return hipSuccess;
     a.fuse_items = a.tv.n_groups * n_grid_chunks;              // (fused launches run every group: the engine sees to it)

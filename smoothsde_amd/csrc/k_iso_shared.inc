@@ -464,6 +464,8 @@ __device__ __forceinline__ int run_lane_shared(const IsoArgs& A, int g, int part
 // With a dedicated transient window (t0 > 0) the grid enumerates windows 1..n_chunks-1; the wave that
 // owns window 1 first runs window 0 (direction form, gain table), every window >= 1 runs the lean
 // basis-form code.  Without it (short tracks, a single window) every wave runs the general shared code.
+// A transient window with nothing taken off window 1 (t0 > 0, t0_delta == 0: the latency plan of the lag-statistics head,
+// ssde_windows.hpp) has a wave of its own: the grid enumerates every window, wave 0 of a group runs window 0 and nothing else.
 // the work of one wave; returns the rows it walked (SSDE_WAVE_CLOCK)
 // g, c_lo .. c_hi: the group and the windows the wave ran (the fused finalising work announces them)
 template <int MODEL, int D, int MASK, bool DEEP>
@@ -471,13 +473,14 @@ __device__ __forceinline__ int shared_wave(const IsoArgs& A, bool& valid, int& g
     int part, chunk, rows = 0;
     valid = false;
     if (A.t0 > 0) {
-        if (!decode_block(A, A.n_chunks - 1, g, part, chunk)) return 0;
+        const bool own = A.t0_delta == 0;
+        if (!decode_block(A, own ? A.n_chunks : A.n_chunks - 1, g, part, chunk)) return 0;
         if (!group_selected(A, g)) return 0;
         valid = true;
-        chunk += 1;
+        if (!own) chunk += 1;
         c_lo = c_hi = chunk;
-        if (chunk == 1) { rows += run_lane_shared<MODEL, D, MASK, false, DEEP>(A, g, part, 0); c_lo = 0; }
-        rows += run_lane_shared<MODEL, D, MASK, true, DEEP>(A, g, part, chunk);
+        if (chunk == (own ? 0 : 1)) { rows += run_lane_shared<MODEL, D, MASK, false, DEEP>(A, g, part, 0); c_lo = 0; }
+        if (chunk > 0) rows += run_lane_shared<MODEL, D, MASK, true, DEEP>(A, g, part, chunk);
     } else {
         if (!decode_block(A, A.n_chunks, g, part, chunk)) return 0;
         if (!group_selected(A, g)) return 0;

@@ -831,8 +831,8 @@ int ssde_info(const ssde_handle* h, ssde_info_t* info) {
     info->n_devices = 1; info->comm_ranks = h->comm_ranks; info->window_check_max = h->policy().check_max;
     info->comm_ranks_reported = h->comm_ranks_reported; info->kernel_id = h->last_kernel_id;
     info->exact_hess_scope = hess_exact_scope(h);
-    if (h->path == PATH_ISO)   // 4-wave workgroups; with a transient window the grid enumerates windows 1.. only
-        info->n_kernel_blocks = ((h->n_groups + 7) / 8 * 8 * h->iso_parts * ((h->use_shared && h->last_t0 > 0) ? h->last_chunks - 1 : h->last_chunks) + WG_WAVES - 1) / WG_WAVES;
+    if (h->path == PATH_ISO)   // 4-wave workgroups; with a transient window on the wave of window 1 the grid enumerates windows 1.. only
+        info->n_kernel_blocks = ((h->n_groups + 7) / 8 * 8 * h->iso_parts * ((h->use_shared && h->last_t0 > 0 && h->last_t0_delta > 0) ? h->last_chunks - 1 : h->last_chunks) + WG_WAVES - 1) / WG_WAVES;
     else if (h->path == PATH_DENSE) info->n_kernel_blocks = h->n_groups * h->n_dirblocks;
     else if (h->path == PATH_TV) info->n_kernel_blocks = (h->tv_n_items_g + WG_WAVES - 1) / WG_WAVES;
     else info->n_kernel_blocks = h->direct_blocks;

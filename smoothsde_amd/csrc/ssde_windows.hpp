@@ -19,6 +19,13 @@ constexpr double SSDE_WINDOW_TOL = 1e-11;  // largest tolerated relative hand-ov
 // Measured.  T0_COST: a row of the transient window, in stationary rows.  W0_RATIO: cost of a row of window 0 (every direction) over a
 // row of a later window (one derived) on the general kernel -- 0 .. 1.45 swept, 3 % on CTCRW at 1.2, nothing on the scalar models.
 constexpr double T0_COST = 3.0, W0_RATIO = 1.2;
+// HEAD_T0_COST: a row of the transient window [0, t0) of a LONE wave (one wave per SIMD or fewer: the head of the lag-statistics path),
+// in stationary rows of such a wave.  T0_COST was measured under throughput; this one from stamps inside the waves of the bench's
+// batch (profiles/r08_b_phase_stamps.txt; per wave: r08_a_wave_clock.txt): the wave of the transient window walks its 16 gain-table
+// rows in 6.3 us and its 48 stationary rows in direction form in 7.8 us -- 0.22 us a row, bound by its own dependent instructions;
+// a stationary-only wave walks 48 rows in 5.2 - 6.5 us -- 0.12 us a row, one 8-row block per memory round trip.
+constexpr double HEAD_T0_COST = 1.8;
+constexpr int HEAD_WAVE_SLOTS = 1024;      // SIMDs of the chip: one wave each is one round of the head's launch
 
 // the layout constants the policy reads: WIN_ALIGN and SHARED_U of ssde_device.hpp, LAG_A and LAG_KMAX of ssde_lagstats.hpp (a
 // host-only header does not include the former; the engine's one instance is WINDOW_CONSTS, ssde_engine.hpp)
@@ -224,7 +231,7 @@ struct WindowEval {
 struct WindowGeometry {
     WindowPlan plan;              // the plan in force (the head's own when the bulk comes from the lag statistics)
     int n_chunks = 1, window = 0; // windows launched (the transient window included) and their warm-up
-    int t0 = 0, t0_delta = 0;     // the transient window [0, t0); rows taken off window 1, whose wave runs it too
+    int t0 = 0, t0_delta = 0;     // the transient window [0, t0); rows taken off window 1, whose wave runs it too (0 with t0 > 0: it has a wave of its own)
     bool dual = false;            // mixed batch: the general launch runs a plan of its own ...
     int n_chunks_d = 0, t0_d = 0; // ... of this many windows, window 0 = [0, t0_d)
     int lag_K = 0;                // > 0: rows past LAG_A from the lag statistics, with this many taps
@@ -232,6 +239,50 @@ struct WindowGeometry {
     int quiet_window = 0;         // rows of memory of the quiet rows (0: none), in blocks: quiet_w, first quiet block: quiet_b0
     int quiet_w = 0, quiet_b0 = 0;
 };
+
+// The head of the lag-statistics path (rows [0, LAG_A) of every track) planned for latency.  Its launch is a few hundred waves on a
+// chip of 1024 SIMDs, so what it takes is the dependent chain of rows of its longest wave, times the rounds of waves the grid needs --
+// not the rows it walks in all: redundant warm-up rows on idle SIMDs cost nothing.  Compared, in stationary rows:
+//   * the shared-wave geometry the throughput rules give (g as it comes in: the transient window on the wave of window 1, which is
+//     shortened by t0_delta), its longest wave by window_bounds' rules (ssde_device.hpp);
+//   * the transient window on a wave of its own (t0_delta = 0) and k = 1 .. max_chunks - 1 stationary windows dealt [t0, LAG_A)
+//     equally: chain(k) = max(HEAD_T0_COST t0, W + ceil(units / k) WIN_ALIGN), rounds(k) = ceil(groups padded to 8 x (k + 1) / 1024).
+// The cheapest is taken; at equal cost the shorter stationary chain (the transient's cost is a measured average: the plan should
+// not hinge on it where more windows are free), then the fewer windows.  The shared-wave geometry stays unless one is strictly cheaper:
+// with more groups than wave slots the rounds term keeps it.  Buffers are sized by max_chunks, which bounds k + 1.
+inline void head_latency_plan(const WindowFacts& f, const WindowConsts& c, WindowGeometry& g) {
+    const int WA = c.win_align, W = g.window, t0 = g.t0, rest = c.lag_a - t0;
+    if (t0 <= 0 || rest <= 0 || g.n_chunks < 2) return;
+    const int64_t g8 = ((int64_t)f.n_groups + 7) / 8 * 8;
+    auto rounds = [&](int waves) { return (double)std::max<int64_t>(1, (g8 * waves + HEAD_WAVE_SLOTS - 1) / HEAD_WAVE_SLOTS); };
+    auto ceil_div = [](int a, int b) { return (a + b - 1) / b; };
+    const double transient = HEAD_T0_COST * t0;
+    // the shared-wave geometry: window 1 and the longest other window, as window_bounds deals them
+    double best_cost;
+    {
+        const int nw = g.n_chunks - 1, delta = g.t0_delta;
+        const int cl = ceil_div(ceil_div(rest + delta, WA), nw) * WA;
+        int len1, len_other = 0;
+        if (cl <= delta + WA) {                       // (its short-track branch: a token window 1, the others share the rest)
+            len1 = nw > 1 ? std::min(rest, 2 * WA) : rest;
+            if (nw > 1) len_other = ceil_div(ceil_div(rest - len1, WA), nw - 1) * WA;
+        } else {
+            len1 = cl - delta;
+            if (nw > 1) len_other = cl;
+        }
+        const double chain = std::max(transient + W + len1, len_other > 0 ? (double)(W + len_other) : 0.0);
+        best_cost = rounds(nw) * chain;
+    }
+    const int units = ceil_div(rest, WA);
+    const int kmax = std::min(std::max(2, f.max_chunks) - 1, std::max(1, units - 1));     // (k >= units: window_bounds would leave windows empty)
+    int best_k = 0, best_stat = 0;
+    for (int k = 1; k <= kmax; k++) {
+        const int stat = W + ceil_div(units, k) * WA;
+        const double cost = rounds(k + 1) * std::max(transient, (double)stat);
+        if (cost < best_cost || (best_k > 0 && cost == best_cost && stat < best_stat)) { best_cost = cost; best_k = k; best_stat = stat; }
+    }
+    if (best_k > 0) { g.n_chunks = best_k + 1; g.t0_delta = 0; }
+}
 
 inline WindowGeometry window_geometry(const WindowFacts& f, const WindowConsts& c, const WindowParams& a, const WindowPlan& first,
                                       int boost, bool gave_up, const WindowEval& e) {
@@ -276,6 +327,9 @@ inline WindowGeometry window_geometry(const WindowFacts& f, const WindowConsts& 
     // the transient window (gain table, direction form) runs on the wave that owns window 1: that window is
     // shortened by what the transient rows cost, in stationary rows (T0_COST x t0)
     g.t0_delta = (int)(T0_COST * g.t0 + c.win_align - 1) / c.win_align * c.win_align;
+    // ... except in the head of the lag-statistics path where a wave of its own is cheaper (t0 > 0 with t0_delta == 0, the meaning
+    // the general kernel's balanced window 0 already has); a forced window count (SSDE_CHUNKS) keeps the throughput geometry: A/B
+    if (g.lag_K > 0 && !f.chunks_forced) head_latency_plan(f, c, g);
     if (!f.use_shared && !f.drift && g.n_chunks > 1) {
         const int t0 = balanced_window0(f.glen_max, g.n_chunks, g.window, e.can_derive, c.win_align);
         if (t0 > 0) { g.t0 = t0; g.t0_delta = 0; }
