@@ -498,6 +498,28 @@ int ssde_lagstats_read(const ssde_handle *h, double *M, double *s, double *n_bul
    a stationary regime. */
 int ssde_lagforms_host(const double *M, const double *s, double n_bulk, int32_t d, const double *theta, double dt, const double *p0,
                        int32_t K, int32_t mask, int32_t taps_given, double *taps, double *raw, double *acc, double *chk);
+/* The same three for every model the lag-statistics path serves (SSDE_MODEL_CTCRW, SSDE_MODEL_OU_SSM, SSDE_MODEL_BM_SSM; DESIGN.md
+   §3.3d).  CTCRW and BM_SSM take the statistics of the INCREMENTS y_t - y_{t-1} (ssde_lagstats_host_m returns bitwise what
+   ssde_lagstats_host returns for them; ref is ignored); OU_SSM takes those of the LEVELS z_{a,t} = y_{a,t} - ref[a]:
+   M_ik = sum z_{t-i} z_{t-k}, s_{a,i} = sum z_{a,t-i} over the bulk rows, with ref[a] (d doubles) a value near the data -- a handle
+   keeps the one it chose at create (ssde_lagstats_read_m).  SSDE_ERR_ARG additionally for a model outside the three and, for OU_SSM
+   with y != NULL, for ref == NULL. */
+int ssde_lagstats_host_m(int32_t model, const double *y, const int64_t *rows, int64_t n_tracks, int d, const double *ref, double *M,
+                         double *s, double *n_bulk, int32_t *n_taps, int32_t *first_row);
+/* ssde_lagstats_read, and the handle's ref (2 doubles; zeros for a model whose statistics are those of the increments).
+   SSDE_ERR_ARG where ssde_lagstats_read gives it, and for ref == NULL. */
+int ssde_lagstats_read_m(const ssde_handle *h, double *M, double *s, double *n_bulk, double *ref);
+/* ssde_lagforms_host for `model`.  theta: OU_SSM (log sigma_obs, mu_1 .. mu_d, log tau, log kappa), BM_SSM (log sigma_obs,
+   mu_1 .. mu_d, log sigma); p0: one double (the variance the covariance recursion starts from) or NULL; ref: what the statistics
+   were built with (d doubles, OU_SSM; ignored otherwise); mask bits: 1 sigma_obs, 2 mu, 4 par d, 8 par d + 1 (< 0: all).
+   OU_SSM / BM_SSM: taps: 3 x n_taps doubles, the responses of u, A1 and A3 of the stationary lanes (ssde_tf.hpp: BasisScal) to a unit
+   impulse in the level (OU_SSM) or a unit increment (BM_SSM), as read by the row's products (A3 == 0 for BM_SSM); raw: 2 x 5 doubles,
+   S = sum u^2, S1 = sum u A1, S3 = sum u A3, su_1, su_2 (su_a = sum u_a) of the cut K and then of K - 16; acc, chk as above.
+   With model == SSDE_MODEL_CTCRW the call is ssde_lagforms_host (taps 2 x n_taps, raw 2 x 6).  SSDE_ERR_ARG as there, and for a
+   model outside the three or (OU_SSM) ref == NULL. */
+int ssde_lagforms_host_m(int32_t model, const double *M, const double *s, double n_bulk, const double *ref, int32_t d, const double *theta,
+                         double dt, const double *p0, int32_t K, int32_t mask, int32_t taps_given, double *taps, double *raw, double *acc,
+                         double *chk);
 
 #ifdef __cplusplus
 }

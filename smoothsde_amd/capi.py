@@ -507,6 +507,14 @@ def load_library():
     lib.ssde_lagforms_host.argtypes = [_dp, _dp, C.c_double, C.c_int32, _dp, C.c_double, _dp, C.c_int32, C.c_int32, C.c_int32,
                                        _dp, _dp, _dp, _dp]
     lib.ssde_lagforms_host.restype = C.c_int
+    lib.ssde_lagstats_host_m.argtypes = [C.c_int32, _dp, C.POINTER(C.c_int64), C.c_int64, C.c_int, _dp, _dp, _dp, _dp,
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.ssde_lagstats_host_m.restype = C.c_int
+    lib.ssde_lagstats_read_m.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp]
+    lib.ssde_lagstats_read_m.restype = C.c_int
+    lib.ssde_lagforms_host_m.argtypes = [C.c_int32, _dp, _dp, C.c_double, _dp, C.c_int32, _dp, C.c_double, _dp, C.c_int32, C.c_int32,
+                                         C.c_int32, _dp, _dp, _dp, _dp]
+    lib.ssde_lagforms_host_m.restype = C.c_int
     lib.ssde_abi_version.argtypes = []
     lib.ssde_abi_version.restype = C.c_int
     lib.ssde_laplace_eval.argtypes = [C.c_void_p, _dp, C.c_int32, C.c_int32, _dp, _dp, _dp, C.POINTER(SsdeLaplaceOpts)]
@@ -546,11 +554,13 @@ WINDOW_TOL = 1e-11  # largest tolerated relative hand-over disagreement between 
 
 EXPORTED_SYMBOLS = ("ssde_create", "ssde_eval", "ssde_eval_device", "ssde_penalty", "ssde_report", "ssde_widen_windows", "ssde_relax_windows",
                     "ssde_info", "ssde_destroy", "ssde_last_error", "ssde_abi_version", "ssde_comm_unique_id", "ssde_comm_init_rank", "ssde_forget", "ssde_laplace_eval", "ssde_last_kernel_ms", "ssde_kernel_ms_history",
-                    "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth")
+                    "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth",
+                    "ssde_lagstats_host_m", "ssde_lagstats_read_m", "ssde_lagforms_host_m")
 
-def lagstats_host(tracks):
+def lagstats_host(tracks, model="CTCRW", ref=None):
     """The lag statistics ssde_create builds for a stationary batch, computed on the host: `tracks` is a list of
-    (rows x d) arrays of tiled rows.  Returns (M, s, n_bulk, first_row): M (taps x taps), s (2 x taps), the bulk rows, the bulk's first row."""
+    (rows x d) arrays of tiled rows.  Returns (M, s, n_bulk, first_row): M (taps x taps), s (2 x taps), the bulk rows, the bulk's first row.
+    `model`: "CTCRW" and "BM_SSM" take the statistics of the increments, "OU_SSM" those of the levels y - `ref` (d numbers)."""
     lib = load_library()
     nt, a0 = C.c_int32(0), C.c_int32(0)
     lib.ssde_lagstats_host(None, None, 0, 1, None, None, None, C.byref(nt), C.byref(a0))
@@ -558,32 +568,54 @@ def lagstats_host(tracks):
     y = np.ascontiguousarray(np.concatenate([np.asarray(t, dtype=np.float64) for t in tracks]))
     rows = np.array([t.shape[0] for t in tracks], dtype=np.int64)
     M = np.zeros((nt.value, nt.value)); s = np.zeros((2, nt.value)); n = np.zeros(1)
-    st = lib.ssde_lagstats_host(y.ctypes.data_as(_dp), rows.ctypes.data_as(C.POINTER(C.c_int64)), len(tracks), d,
-                                M.ctypes.data_as(_dp), s.ctypes.data_as(_dp), n.ctypes.data_as(_dp), C.byref(nt), C.byref(a0))
+    if model == "CTCRW" and ref is None:
+        st = lib.ssde_lagstats_host(y.ctypes.data_as(_dp), rows.ctypes.data_as(C.POINTER(C.c_int64)), len(tracks), d,
+                                    M.ctypes.data_as(_dp), s.ctypes.data_as(_dp), n.ctypes.data_as(_dp), C.byref(nt), C.byref(a0))
+    else:
+        rf = None if ref is None else np.ascontiguousarray(np.atleast_1d(ref), dtype=np.float64)
+        if rf is not None and rf.size < d:
+            raise ValueError("lagstats_host: ref holds fewer than d numbers")
+        st = lib.ssde_lagstats_host_m(MODEL_CODES[model], y.ctypes.data_as(_dp), rows.ctypes.data_as(C.POINTER(C.c_int64)), len(tracks), d,
+                                      None if rf is None else rf.ctypes.data_as(_dp), M.ctypes.data_as(_dp), s.ctypes.data_as(_dp),
+                                      n.ctypes.data_as(_dp), C.byref(nt), C.byref(a0))
     if st != 0:
         raise ValueError(f"ssde_lagstats_host: status {st}")
     return M, s, float(n[0]), int(a0.value)
 
 
-def lagforms_host(M, s, n_bulk, theta, dt, K, d=None, p0=None, mask=-1, taps=None):
+def lagforms_host(M, s, n_bulk, theta, dt, K, d=None, p0=None, mask=-1, taps=None, model="CTCRW", ref=None):
     """The bulk's forms of one evaluation on the lag-statistics path, on the host: CTCRW on a regular grid of
     step `dt` at theta = (log sigma_obs, mu_1 .. mu_d, log tau, log nu), cut at `K` taps (the check's cut: K - 16), from the
     statistics M, s, n_bulk.  `taps` (2 x taps: the impulse responses of u and r): used as they are when given, computed otherwise.
-    Returns a dict: raw (2 x 6: S, C_1..3, su_1, su_2 of the cut K, then of K - 16), acc (the 4 + d accumulators), chk, taps."""
+    Returns a dict: raw (2 x 6: S, C_1..3, su_1, su_2 of the cut K, then of K - 16), acc (the 4 + d accumulators), chk, taps.
+    `model` "OU_SSM" (theta = log sigma_obs, mu, log tau, log kappa; `ref`: what the statistics were built with) or "BM_SSM" (theta =
+    log sigma_obs, mu, log sigma): taps is 3 x taps (u, A1, A3) and raw 2 x 5 (S, S1, S3, su_1, su_2)."""
     lib = load_library()
     M = np.ascontiguousarray(M, dtype=np.float64); s = np.ascontiguousarray(s, dtype=np.float64)
     theta = np.ascontiguousarray(theta, dtype=np.float64)
+    scal = model != "CTCRW"
+    npar = 2 if model == "BM_SSM" else 3                   # log sigma_obs and the model's one or two scale parameters
     if d is None:
-        d = theta.size - 3
+        d = theta.size - npar
     given = taps is not None
-    tp = np.ascontiguousarray(taps, dtype=np.float64).copy() if given else np.zeros((2, M.shape[0]))
-    if tp.shape != (2, M.shape[0]) or s.shape != (2, M.shape[0]) or theta.size != d + 3:
+    nrow, nraw = (3, 5) if scal else (2, 6)
+    tp = np.ascontiguousarray(taps, dtype=np.float64).copy() if given else np.zeros((nrow, M.shape[0]))
+    if tp.shape != (nrow, M.shape[0]) or s.shape != (2, M.shape[0]) or theta.size != d + npar:
         raise ValueError("lagforms_host: shapes")
-    p0a = None if p0 is None else np.ascontiguousarray(p0, dtype=np.float64)
-    raw = np.zeros((2, 6)); acc = np.zeros(4 + d); chk = np.zeros(1)
-    st = lib.ssde_lagforms_host(M.ctypes.data_as(_dp), s.ctypes.data_as(_dp), float(n_bulk), d, theta.ctypes.data_as(_dp), float(dt),
-                                None if p0a is None else p0a.ctypes.data_as(_dp), int(K), int(mask), 1 if given else 0,
-                                tp.ctypes.data_as(_dp), raw.ctypes.data_as(_dp), acc.ctypes.data_as(_dp), chk.ctypes.data_as(_dp))
+    p0a = None if p0 is None else np.ascontiguousarray(np.atleast_1d(p0), dtype=np.float64)
+    raw = np.zeros((2, nraw)); acc = np.zeros(4 + d); chk = np.zeros(1)
+    if not scal and ref is None:
+        st = lib.ssde_lagforms_host(M.ctypes.data_as(_dp), s.ctypes.data_as(_dp), float(n_bulk), d, theta.ctypes.data_as(_dp), float(dt),
+                                    None if p0a is None else p0a.ctypes.data_as(_dp), int(K), int(mask), 1 if given else 0,
+                                    tp.ctypes.data_as(_dp), raw.ctypes.data_as(_dp), acc.ctypes.data_as(_dp), chk.ctypes.data_as(_dp))
+    else:
+        rf = None if ref is None else np.ascontiguousarray(np.atleast_1d(ref), dtype=np.float64)
+        if rf is not None and rf.size < d:
+            raise ValueError("lagforms_host: ref holds fewer than d numbers")
+        st = lib.ssde_lagforms_host_m(MODEL_CODES[model], M.ctypes.data_as(_dp), s.ctypes.data_as(_dp), float(n_bulk),
+                                      None if rf is None else rf.ctypes.data_as(_dp), d, theta.ctypes.data_as(_dp), float(dt),
+                                      None if p0a is None else p0a.ctypes.data_as(_dp), int(K), int(mask), 1 if given else 0,
+                                      tp.ctypes.data_as(_dp), raw.ctypes.data_as(_dp), acc.ctypes.data_as(_dp), chk.ctypes.data_as(_dp))
     if st != 0:
         raise ValueError(f"ssde_lagforms_host: status {st}")
     return {"raw": raw, "acc": acc, "chk": float(chk[0]), "taps": tp}
@@ -687,6 +719,17 @@ class Engine:
         if st != 0:
             return None
         return M, s, float(n[0])
+
+    def lagstats_ref(self):
+        """The value the statistics' levels are centred on (OU_SSM: y - ref, one number per response coordinate, fixed at create;
+        zeros for CTCRW and BM_SSM, whose statistics are those of the increments), or None when the engine built no statistics."""
+        nt, a0 = C.c_int32(0), C.c_int32(0)
+        self.lib.ssde_lagstats_host(None, None, 0, 1, None, None, None, C.byref(nt), C.byref(a0))
+        M = np.zeros((nt.value, nt.value)); s = np.zeros((2, nt.value)); n = np.zeros(1); ref = np.zeros(2)
+        st = self.lib.ssde_lagstats_read_m(self._h, M.ctypes.data_as(_dp), s.ctypes.data_as(_dp), n.ctypes.data_as(_dp), ref.ctypes.data_as(_dp))
+        if st != 0:
+            return None
+        return ref
 
     def info(self) -> dict:
         inf = SsdeInfo()

@@ -1,6 +1,7 @@
 // k_lagstats.hip -- the lag statistics of a stationary batch (ssde_create, once).  The bulk forms built from them at every
 // evaluation that takes that path run on the host (ssde_lagforms.hpp).  Derivation and layout: ssde_lagstats.hpp, DESIGN.md
-// §3.3d.  Every sum runs in a fixed order: two creates of the same data give bitwise-equal statistics.
+// §3.3d.  Every sum runs in a fixed order: two creates of the same data give bitwise-equal statistics.  The kernels come in two
+// compile-time modes: the increments y_t - y_{t-1} (CTCRW, BM_SSM) and the levels y_t - ref (OU_SSM).
 #include "ssde_device.hpp"
 #include "ssde_lagstats.hpp"
 
@@ -10,12 +11,18 @@ namespace {
 
 constexpr int LAG_NB = LAG_N / LAG_LB;        // lag blocks of the Toeplitz pass
 
+// what the levels mode centres the data on (ssde_lagstats.hpp), by value
+struct LagRef { double v[2]; };
+
 // Toeplitz lag sums Q_l = sum_{t = LAG_A}^{n - 1} Dy_t Dy_{t-l} (summed over the coordinates) of the 64 tracks of a group, for the
 // LAG_LB lags of one block: one wave per (group, lag block), lane = track.  The rows walk in blocks of LAG_LB; the lagged
 // increments of the block before stay in registers (old), so each row is loaded twice per work item: as the current row and
 // as the lagged one.  A lane without a bulk (n <= LAG_A, or no track) contributes zeros; rows past a lane's track are zeroed
 // before they are multiplied (the tile slots there hold whatever the layout put there).
-__global__ __launch_bounds__(WG_WAVES * WAVE) void lag_toeplitz_kernel(const TileView tv, int d, double* Qg) {
+// LEVELS (OU_SSM): the same sums of the levels z_t = y_t - ref_a instead of the increments, and -- from the waves of lag block 0 --
+// s0g[g][a] = sum_{t >= LAG_A} z_{a,t} of the group, which no longer telescopes.
+template <bool LEVELS>
+__global__ __launch_bounds__(WG_WAVES * WAVE) void lag_toeplitz_kernel(const TileView tv, int d, double* Qg, const LagRef ref, double* s0g) {
     const int id = blockIdx.x * WG_WAVES + (threadIdx.x >> 6);
     const int g = id / LAG_NB, b = id % LAG_NB;
     if (g >= tv.n_groups) return;
@@ -35,33 +42,40 @@ __global__ __launch_bounds__(WG_WAVES * WAVE) void lag_toeplitz_kernel(const Til
     // only its own (padded) length, and the last group -- the shortest tracks -- may be shorter than the rows below.
     if (nmax <= LAG_A) {
         if (lane < LAG_LB) Qg[(int64_t)g * LAG_N + l0 + lane] = 0.0;
+        if (LEVELS && b == 0 && lane < 2) s0g[(int64_t)g * 2 + lane] = 0.0;
         return;
     }
+    double zsum[2] = {0.0, 0.0};
     for (int a = 0; a < d; a++) {
+        const double rf = LEVELS ? ref.v[a] : 0.0;
         const double* p = base + (int64_t)(c_obs + a) * WAVE;
         const int64_t rs = (int64_t)C * WAVE;
         double old[LAG_LB], nw[LAG_LB], cur[LAG_LB];
         // old[j] = Dy_{LAG_A - l0 - LAG_LB + j}: the lagged increments of the rows before the first block (row >= LAG_A - LAG_N - 1 >= 0)
-        double yl = p[(LAG_A - l0 - LAG_LB - 1) * rs];
+        double yl = LEVELS ? rf : p[(LAG_A - l0 - LAG_LB - 1) * rs];
 #pragma unroll
         for (int j = 0; j < LAG_LB; j++) {
             const double y = p[(LAG_A - l0 - LAG_LB + j) * rs];
             old[j] = ns > 0 ? y - yl : 0.0;
-            yl = y;
+            if (!LEVELS) yl = y;
         }
-        double yc = p[(LAG_A - 1) * rs];
+        double yc = LEVELS ? rf : p[(LAG_A - 1) * rs];
         for (int t0 = LAG_A; t0 < nmax; t0 += LAG_LB) {     // (loads reach row nmax + LAG_LB - 2 < group length + TILE_SPARE)
 #pragma unroll
             for (int j = 0; j < LAG_LB; j++) {
                 const double y = p[(t0 - l0 + j) * rs];
                 nw[j] = (t0 - l0 + j < ns) ? y - yl : 0.0;
-                yl = y;
+                if (!LEVELS) yl = y;
             }
 #pragma unroll
             for (int j = 0; j < LAG_LB; j++) {
                 const double y = p[(t0 + j) * rs];
                 cur[j] = (t0 + j < ns) ? y - yc : 0.0;
-                yc = y;
+                if (!LEVELS) yc = y;
+            }
+            if (LEVELS && b == 0) {
+#pragma unroll
+                for (int j = 0; j < LAG_LB; j++) zsum[a] += cur[j];
             }
             // row t0 + u, lag l0 + j: Dy_{t0 + u - l0 - j} = nw[u - j] (u >= j) or old[LAG_LB + u - j]
 #pragma unroll
@@ -77,6 +91,13 @@ __global__ __launch_bounds__(WG_WAVES * WAVE) void lag_toeplitz_kernel(const Til
         const double t = wave_sum(acc[j]);
         if (lane == 0) Qg[(int64_t)g * LAG_N + l0 + j] = t;
     }
+    if (LEVELS && b == 0) {
+#pragma unroll
+        for (int a = 0; a < 2; a++) {
+            const double t = wave_sum(zsum[a]);
+            if (lane == 0) s0g[(int64_t)g * 2 + a] = t;
+        }
+    }
 }
 
 __device__ __forceinline__ double readlane_d(double x, int k) {
@@ -88,7 +109,10 @@ __device__ __forceinline__ double readlane_d(double x, int k) {
 // The end corrections D_pq = sum (h_p h_q - g_p g_q) of one group (h_j = Dy_{LAG_A-1-j}, g_j = Dy_{n-1-j}) for 64 rows p x 64
 // columns q: one wave per (group, p block, q block), lane = p; the group's tracks one after the other (fixed order), column q's
 // values broadcast from the lane that loaded them.  The q block 0 waves also sum s_{a,p} = y_{n-1-p} - y_{LAG_A-1-p}.
-__global__ __launch_bounds__(WG_WAVES * WAVE) void lag_ends_kernel(const TileView tv, int d, double* Dg, double* sg) {
+// LEVELS: h_j = z_{LAG_A-1-j}, g_j = z_{n-1-j} of the levels z = y - ref_a, and the q block 0 waves sum e_{a,p} = h_{a,p} - g_{a,p}, the
+// steps of s_{a,p+1} = s_{a,p} + e_{a,p} (lag_levels_s, on the host).
+template <bool LEVELS>
+__global__ __launch_bounds__(WG_WAVES * WAVE) void lag_ends_kernel(const TileView tv, int d, double* Dg, double* sg, const LagRef ref) {
     constexpr int PB = LAG_N / 64;
     const int id = blockIdx.x * WG_WAVES + (threadIdx.x >> 6);
     const int g = id / (PB * PB), pb = (id / PB) % PB, qb = id % PB;
@@ -107,13 +131,22 @@ __global__ __launch_bounds__(WG_WAVES * WAVE) void lag_ends_kernel(const TileVie
         for (int a = 0; a < d; a++) {
             const double* y = bm + (int64_t)(c_obs + a) * WAVE;
             // rows >= n - LAG_N - 1 >= LAG_A - LAG_N >= 0, all < n
-            const double hp = y[(LAG_A - 1 - p) * rs] - y[(LAG_A - 2 - p) * rs];
-            const double gp = y[(int64_t)(n - 1 - p) * rs] - y[(int64_t)(n - 2 - p) * rs];
-            const double hq = y[(LAG_A - 1 - q) * rs] - y[(LAG_A - 2 - q) * rs];
-            const double gq = y[(int64_t)(n - 1 - q) * rs] - y[(int64_t)(n - 2 - q) * rs];
+            double hp, gp, hq, gq;
+            if (LEVELS) {
+                const double rf = ref.v[a];
+                hp = y[(LAG_A - 1 - p) * rs] - rf;
+                gp = y[(int64_t)(n - 1 - p) * rs] - rf;
+                hq = y[(LAG_A - 1 - q) * rs] - rf;
+                gq = y[(int64_t)(n - 1 - q) * rs] - rf;
+            } else {
+                hp = y[(LAG_A - 1 - p) * rs] - y[(LAG_A - 2 - p) * rs];
+                gp = y[(int64_t)(n - 1 - p) * rs] - y[(int64_t)(n - 2 - p) * rs];
+                hq = y[(LAG_A - 1 - q) * rs] - y[(LAG_A - 2 - q) * rs];
+                gq = y[(int64_t)(n - 1 - q) * rs] - y[(int64_t)(n - 2 - q) * rs];
+            }
 #pragma unroll
             for (int k = 0; k < 64; k++) acc[k] = fma(hp, readlane_d(hq, k), fma(-gp, readlane_d(gq, k), acc[k]));
-            if (qb == 0) sacc[a] += y[(int64_t)(n - 1 - p) * rs] - y[(LAG_A - 1 - p) * rs];
+            if (qb == 0) sacc[a] += LEVELS ? hp - gp : y[(int64_t)(n - 1 - p) * rs] - y[(LAG_A - 1 - p) * rs];
         }
     }
     double* o = Dg + ((int64_t)g * LAG_N + p) * LAG_N + qb * 64;
@@ -134,17 +167,29 @@ __global__ __launch_bounds__(256) void lag_group_sum_kernel(const double* src, i
 
 }  // namespace
 
-hipError_t launch_lagstats(const TileView& tv, int d, double* Qg, double* Dg, double* sg, double* Q, double* D, double* s, hipStream_t st) {
+hipError_t launch_lagstats(const TileView& tv, int d, double* Qg, double* Dg, double* sg, double* Q, double* D, double* s, hipStream_t st,
+                           const double* levels_ref, double* s0g, double* s0) {
     const int G = tv.n_groups;
-    hipLaunchKernelGGL(lag_toeplitz_kernel, dim3((G * LAG_NB + WG_WAVES - 1) / WG_WAVES), dim3(WG_WAVES * WAVE), 0, st, tv, d, Qg);
+    const dim3 grid_t((G * LAG_NB + WG_WAVES - 1) / WG_WAVES), block(WG_WAVES * WAVE);
     constexpr int PB = LAG_N / 64;
-    hipLaunchKernelGGL(lag_ends_kernel, dim3((G * PB * PB + WG_WAVES - 1) / WG_WAVES), dim3(WG_WAVES * WAVE), 0, st, tv, d, Dg, sg);
+    const dim3 grid_e((G * PB * PB + WG_WAVES - 1) / WG_WAVES);
+    if (levels_ref) {
+        if (!s0g || !s0) return hipErrorInvalidValue;
+        const LagRef ref = {{levels_ref[0], d > 1 ? levels_ref[1] : 0.0}};
+        hipLaunchKernelGGL(lag_toeplitz_kernel<true>, grid_t, block, 0, st, tv, d, Qg, ref, s0g);
+        hipLaunchKernelGGL(lag_ends_kernel<true>, grid_e, block, 0, st, tv, d, Dg, sg, ref);
+    } else {
+        const LagRef ref = {{0.0, 0.0}};
+        hipLaunchKernelGGL(lag_toeplitz_kernel<false>, grid_t, block, 0, st, tv, d, Qg, ref, (double*)nullptr);
+        hipLaunchKernelGGL(lag_ends_kernel<false>, grid_e, block, 0, st, tv, d, Dg, sg, ref);
+    }
     auto sum = [&](const double* src, int64_t n, double* dst) {
         hipLaunchKernelGGL(lag_group_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, n, G, dst);
     };
     sum(Qg, LAG_N, Q);
     sum(Dg, (int64_t)LAG_N * LAG_N, D);
     sum(sg, 2 * LAG_N, s);
+    if (levels_ref) sum(s0g, 2, s0);
     return hipGetLastError();
 }
 

@@ -290,8 +290,11 @@ struct ReduceArgs;
 // the hand-over checks and the final sums of an isotropic evaluation in ONE launch (the checks raise out[n_out])
 hipError_t launch_iso_finalize(int model, int d, const IsoArgs& a, const ReduceArgs& r, hipStream_t s);
 // lag statistics of a stationary batch (k_lagstats.hip, ssde_lagstats.hpp): per-group Toeplitz sums Qg [G][LAG_N], end corrections
-// Dg [G][LAG_N][LAG_N] and s [G][2][LAG_N], and their fixed-order sums over the groups into Q, D, s
-hipError_t launch_lagstats(const TileView& tv, int d, double* Qg, double* Dg, double* sg, double* Q, double* D, double* s, hipStream_t st);
+// Dg [G][LAG_N][LAG_N] and s [G][2][LAG_N], and their fixed-order sums over the groups into Q, D, s.  levels_ref != NULL (OU_SSM): the
+// statistics of the levels y - levels_ref[a] instead of the increments; s then holds the steps e of lag_levels_s (ssde_lagstats.hpp)
+// and s0g [G][2] / s0 [2] the sums of the bulk's levels
+hipError_t launch_lagstats(const TileView& tv, int d, double* Qg, double* Dg, double* sg, double* Q, double* D, double* s, hipStream_t st,
+                           const double* levels_ref = nullptr, double* s0g = nullptr, double* s0 = nullptr);
 void fill_stat_consts(int model, int d, IsoArgs& a);
 int iso_nstate(int model, int d);
 

@@ -264,6 +264,38 @@ int ssde_lagstats_host(const double* y, const int64_t* rows, int64_t n_tracks, i
     return SSDE_OK;
 }
 
+int ssde_lagstats_host_m(int32_t model, const double* y, const int64_t* rows, int64_t n_tracks, int d, const double* ref, double* M,
+                         double* s, double* n_bulk, int32_t* n_taps, int32_t* first_row) {
+    if (model != SSDE_MODEL_CTCRW && model != SSDE_MODEL_OU_SSM && model != SSDE_MODEL_BM_SSM) return SSDE_ERR_ARG;
+    if (model != SSDE_MODEL_OU_SSM) return ssde_lagstats_host(y, rows, n_tracks, d, M, s, n_bulk, n_taps, first_row);   // (increments)
+    if (n_taps) *n_taps = LAG_N;
+    if (first_row) *first_row = LAG_A;
+    if (!y) return SSDE_OK;
+    if (d < 1 || d > 2 || !rows || !M || !s || !n_bulk || !ref) return SSDE_ERR_ARG;
+    std::vector<double> Q(LAG_N, 0.0), D((size_t)LAG_N * LAG_N, 0.0), e(2 * LAG_N, 0.0);
+    double n = 0.0, s0[2] = {0.0, 0.0};
+    int64_t off = 0;
+    for (int64_t k = 0; k < n_tracks; k++) {
+        if (rows[k] > LAG_A) {
+            lag_track_stats_levels(y + off * d, (int)rows[k], d, ref, Q.data(), D.data(), e.data(), s0);
+            n += (double)(rows[k] - LAG_A);
+        }
+        off += rows[k];
+    }
+    lag_assemble(Q.data(), D.data(), M);
+    lag_levels_s(s0, e.data(), s);
+    *n_bulk = n;
+    return SSDE_OK;
+}
+
+int ssde_lagstats_read_m(const ssde_handle* h, double* M, double* s, double* n_bulk, double* ref) {
+    if (!ref) return SSDE_ERR_ARG;
+    const int st = ssde_lagstats_read(h, M, s, n_bulk);
+    if (st != SSDE_OK) return st;
+    ref[0] = h->lag_ref[0]; ref[1] = h->lag_ref[1];
+    return SSDE_OK;
+}
+
 int ssde_lagstats_read(const ssde_handle* h, double* M, double* s, double* n_bulk) {
     if (!h || !M || !s || !n_bulk || !h->lag_ready) return SSDE_ERR_ARG;
     if (hipSetDevice(h->device) != hipSuccess) return SSDE_ERR_HIP;

@@ -298,6 +298,7 @@ struct ssde_handle {
     DevBuf<int32_t> lag_glen, lag_ns;      // group_len / lane_nsteps capped at LAG_A: what the streamed head launch walks
     std::vector<double> lag_M_host, lag_s_host;   // the same on the host: what an evaluation's forms read (ssde_lagforms.hpp)
     double lag_n = 0.0;                    // bulk rows (past LAG_A) of the batch
+    double lag_ref[2] = {0.0, 0.0};        // OU_SSM: what the statistics' levels are centred on (ssde_lagstats.hpp); 0 otherwise
     int64_t lag_rows = 0, last_lag_rows = 0;   // ... and those the last evaluation took from the statistics (0: streamed)
     double lag_create_ms = 0.0;            // what building them cost at create
     int last_kernel_id = 0;                   // SSDE_KERNEL_*: the family that ran the last evaluation's rows

@@ -128,7 +128,7 @@ int lattice_pad(const ssde_desc* d, ssde_handle* h, const std::vector<int64_t>& 
 namespace ssde_engine {
 constexpr int SSDE_RETRY_WITHOUT_DRIFT = -77;     // internal: the drift layout was tried and the data do not qualify
 constexpr int SSDE_RETRY_WITHOUT_PP = -78;        // internal: the drift's blocks were tiled as covariates and the lanes that would read them are the general ones
-// The lag statistics of a stationary batch (ssde_lagstats.hpp): CTCRW on the shared-covariance path, every group
+// The lag statistics of a stationary batch (ssde_lagstats.hpp): CTCRW, OU_SSM or BM_SSM on the shared-covariance path, every group
 // complete, regular grid, no drift.  An evaluation on the path costs ~0.055 ms whatever the batch (the head launch's ~256-row critical
 // path, the finalize launch, the fixed costs; the forms run on the host while the head runs); the streamed one grows with the rows.
 // profiles/r07_c_lagstats_crossover.txt (bench.py both ways, SSDE_LAGSTATS=0 against =2, 1.4e6 - 2.7e7 bulk rows, two repetitions):
@@ -136,35 +136,60 @@ constexpr int SSDE_RETRY_WITHOUT_PP = -78;        // internal: the drift's block
 // 0.056, 1.24e7: 0.076-0.078 / 0.056-0.059.  The crossover lies below what was measured, so the rule sits at its floor: above the 4.3e6
 // below which the tests expect nothing built, 3 x the smallest size at which the path already won.
 constexpr double LAG_MIN_BULK_ROWS = 4.4e6;
+// OU_SSM and BM_SSM (the scalar-family forms of ssde_lagforms.hpp; OU_SSM from the statistics of the levels y - ref) sit on the same
+// head launch chain, but no crossover has been measured for them yet: their statistics are built only when forced (SSDE_LAGSTATS=2).
+constexpr double LAG_MIN_BULK_ROWS_OU_SSM = INFINITY, LAG_MIN_BULK_ROWS_BM_SSM = INFINITY;
 static int build_lagstats(ssde_handle* h, int G, const std::vector<int32_t>& lane_ns, const std::vector<int32_t>& glen) {
     if (h->knobs.lagstats == 0) return SSDE_OK;
-    if (!(h->model == SSDE_MODEL_CTCRW && h->use_shared && !h->drift && h->n_clean_groups == G && h->uniform_dt && h->iso_parts == 1 &&
+    const bool scal = h->model == SSDE_MODEL_OU_SSM || h->model == SSDE_MODEL_BM_SSM;
+    if (!((h->model == SSDE_MODEL_CTCRW || scal) && h->use_shared && !h->drift && h->n_clean_groups == G && h->uniform_dt && h->iso_parts == 1 &&
           (h->d == 1 || h->d == 2) && h->glen_max > LAG_A))
         return SSDE_OK;
     int64_t bulk = 0;
     for (int32_t ns : lane_ns) bulk += ns > LAG_A ? ns - LAG_A : 0;
     const bool forced = h->knobs.lagstats == 2;     // (testing: whatever the rule says)
-    if (!forced && (double)bulk < LAG_MIN_BULK_ROWS) return SSDE_OK;
+    const double min_rows = h->model == SSDE_MODEL_OU_SSM ? LAG_MIN_BULK_ROWS_OU_SSM : h->model == SSDE_MODEL_BM_SSM ? LAG_MIN_BULK_ROWS_BM_SSM : LAG_MIN_BULK_ROWS;
+    if (!forced && !((double)bulk >= min_rows)) return SSDE_OK;
     const auto t0 = std::chrono::steady_clock::now();
     TileView tv;
     tv.tiles = h->tiles.p; tv.group_off = h->group_off.p; tv.group_len = h->group_len.p; tv.lane_nsteps = h->lane_nsteps.p;
     tv.a0 = h->a0.p; tv.n_groups = G; tv.C = h->C; tv.c_obs = h->c_obs; tv.dt_all = h->dt_all;
-    DevBuf<double> Qg, Dg, sg, sums;
+    // OU_SSM: the levels y - ref, ref = the observation at row LAG_A - 1 of the first track in tiled order that has a bulk
+    const bool levels = h->model == SSDE_MODEL_OU_SSM;
+    double ref[2] = {0.0, 0.0};
+    if (levels) {
+        size_t first = 0;
+        while (first < lane_ns.size() && lane_ns[first] <= LAG_A) first++;
+        if (first == lane_ns.size()) return SSDE_OK;            // (glen_max > LAG_A: not reached)
+        std::vector<int64_t> goff(G);
+        HIPCHK(h, hipMemcpy(goff.data(), h->group_off.p, (size_t)G * sizeof(int64_t), hipMemcpyDeviceToHost));
+        const int g = (int)(first / WAVE), lane = (int)(first % WAVE);
+        for (int a = 0; a < h->d; a++)
+            HIPCHK(h, hipMemcpy(&ref[a], h->tiles.p + goff[g] + lane + (int64_t)(h->c_obs + a) * WAVE + (int64_t)(LAG_A - 1) * h->C * WAVE, 8,
+                                hipMemcpyDeviceToHost));
+    }
+    DevBuf<double> Qg, Dg, sg, sums, s0g;
     const size_t NN = (size_t)LAG_N * LAG_N;
     // The per-group temporaries (Dg: G x LAG_N^2 doubles, 46 MB at 10^4 tracks) are an optimisation's: a device that cannot hold them
     // streams every row, as without the statistics
     if (Qg.alloc((size_t)G * LAG_N) != hipSuccess || Dg.alloc((size_t)G * NN) != hipSuccess || sg.alloc((size_t)G * 2 * LAG_N) != hipSuccess ||
-        sums.alloc(LAG_N + NN + 2 * LAG_N) != hipSuccess) {
+        sums.alloc(LAG_N + NN + 2 * LAG_N + 2) != hipSuccess || (levels && s0g.alloc((size_t)G * 2) != hipSuccess)) {
         (void)hipGetLastError();
-        Qg.release(); Dg.release(); sg.release(); sums.release();
+        Qg.release(); Dg.release(); sg.release(); sums.release(); s0g.release();
         return SSDE_OK;
     }
-    HIPCHK(h, launch_lagstats(tv, h->d, Qg.p, Dg.p, sg.p, sums.p, sums.p + LAG_N, sums.p + LAG_N + NN, 0));
+    if (levels) HIPCHK(h, launch_lagstats(tv, h->d, Qg.p, Dg.p, sg.p, sums.p, sums.p + LAG_N, sums.p + LAG_N + NN, 0, ref, s0g.p, sums.p + LAG_N + NN + 2 * LAG_N));
+    else HIPCHK(h, launch_lagstats(tv, h->d, Qg.p, Dg.p, sg.p, sums.p, sums.p + LAG_N, sums.p + LAG_N + NN, 0));
     std::vector<double> host(sums.n), M(NN);
     HIPCHK(h, hipMemcpy(host.data(), sums.p, host.size() * 8, hipMemcpyDeviceToHost));
-    Qg.release(); Dg.release(); sg.release(); sums.release();
+    Qg.release(); Dg.release(); sg.release(); sums.release(); s0g.release();
     lag_assemble(host.data(), host.data() + LAG_N, M.data());
-    h->lag_s_host.assign(host.begin() + LAG_N + NN, host.end());
+    h->lag_s_host.assign(host.begin() + LAG_N + NN, host.begin() + LAG_N + NN + 2 * LAG_N);
+    if (levels) {                                      // (the device summed the steps of s: lag_levels_s)
+        const std::vector<double> e = h->lag_s_host;
+        lag_levels_s(host.data() + LAG_N + NN + 2 * LAG_N, e.data(), h->lag_s_host.data());
+    }
+    h->lag_ref[0] = ref[0]; h->lag_ref[1] = ref[1];
     HIPCHK(h, h->lag_M.upload(M));                     // (the device copies: ssde_lagstats_read)
     HIPCHK(h, h->lag_s.upload(h->lag_s_host));
     h->lag_M_host = std::move(M);

@@ -166,6 +166,50 @@ void lag_form_taps(const IsoArgs& a, int d, int mask, int K, LagFormArgs& f) {
     for (int i = 0; i < 48; i++) f.statc[i] = a.statc[i];
 }
 
+// The same for OU_SSM / BM_SSM (BasisScal::step_stat, ssde_tf.hpp, here on the host): the responses of u, A1 and A3 -- as the row's
+// products read them, before the step -- to a unit impulse in the level (OU_SSM) or a unit step in the level, which is a unit
+// increment (BM_SSM), with the step's constant inputs taken out; those give the affine parts, the fixed point of the same step
+// under y == ref (OU_SSM) or under increments == 0 (BM_SSM), in closed form: with c = t - k the closed-loop factor,
+//     OU_SSM:  x* - mu = k (ref - mu) / (1 - c)   (1 - c = b + k)
+//              kap_u = ref - x* = b (ref - mu) / (1 - c),  kap_A1 = kap_u / (1 - c),  kap_A3 = (dt_ x* + db mu) / (1 - c) = dt_ (x* - mu) / (1 - c)
+//     BM_SSM:  kap_u = -mu dt / k = -mu dt / (1 - c),  kap_A1 = kap_u / (1 - c),  A3 == 0
+// and mx* = b / (1 - c) for both.
+template <int MODEL>
+void lag_form_taps_scal_model(const IsoArgs& a, int K, LagScalArgs& f) {
+    BasisScal<MODEL, 1, DIR_SIG | DIR_MU | DIR_P1 | DIR_P2> T;
+    T.setup(a);
+    T.cmu[0] = T.dbmu[0] = 0.0;                 // (the constant inputs enter through the affine parts)
+    double y = 0.0;
+    T.init(&y);
+    for (int t = 0; t < LAG_N; t++) f.lam[t] = f.t1[t] = f.t3[t] = 0.0;
+    for (int t = 0; t <= K && t < LAG_N; t++) {         // (taps beyond the cut are zero: nothing reads them)
+        y = (MODEL == M_OU_SSM && t > 0) ? 0.0 : 1.0;
+        f.lam[t] = y - T.x[0]; f.t1[t] = T.A1[0]; f.t3[t] = T.A3[0];
+        T.step_stat(&y);
+    }
+}
+void lag_form_taps_scal(int model, const IsoArgs& a, int d, int mask, int K, const double* ref, LagScalArgs& f) {
+    if (model == SSDE_MODEL_OU_SSM) lag_form_taps_scal_model<M_OU_SSM>(a, K, f);
+    else lag_form_taps_scal_model<M_BM_SSM>(a, K, f);
+    f.K = K; f.Kc = K - LAG_CHECK; f.d = d; f.mask = mask; f.has_p2 = model == SSDE_MODEL_OU_SSM;
+    const double* c = a.statc;
+    const double k = c[1], omc = 1.0 - c[2], b = c[4], dt_ = c[5];
+    for (int i = 0; i < 2; i++) {
+        f.ku[i] = f.k1[i] = f.k3[i] = 0.0;
+        if (i >= d) continue;
+        if (model == SSDE_MODEL_OU_SSM) {
+            const double dm = ref[i] - a.mu[i];
+            f.ku[i] = b * dm / omc;
+            f.k3[i] = dt_ * (k * dm / omc) / omc;
+        } else {
+            f.ku[i] = -c[19 + i] / omc;
+        }
+        f.k1[i] = f.ku[i] / omc;
+    }
+    f.mxs = b / omc;
+    for (int i = 0; i < 48; i++) f.statc[i] = a.statc[i];
+}
+
 // ... and their result into the reducing launch's arguments, as the window after the `n_windows` that live in the partial sums
 int lag_forms_into(ssde_handle* h, const IsoArgs& a, int order, int K, int n_windows, ReduceArgs& ra) {
     // the reductions recognise the by-value window as the one after the windows of direction part 0 (reduce_slot, reduce_all_wave):
@@ -174,11 +218,19 @@ int lag_forms_into(ssde_handle* h, const IsoArgs& a, int order, int K, int n_win
         h->err = "lag statistics: the reduction's windows do not match the head's plan";
         return SSDE_ERR_ARG;
     }
-    LagFormArgs f;
     LagFormOut o;
-    lag_form_taps(a, h->d, order >= 1 ? a.part_mask[0] : 0, K, f);
-    f.M = h->lag_M_host.data(); f.s = h->lag_s_host.data(); f.n = h->lag_n;
-    lag_forms_host(f, o);
+    const int mask = order >= 1 ? a.part_mask[0] : 0;
+    if (h->model == SSDE_MODEL_CTCRW) {
+        LagFormArgs f;
+        lag_form_taps(a, h->d, mask, K, f);
+        f.M = h->lag_M_host.data(); f.s = h->lag_s_host.data(); f.n = h->lag_n;
+        lag_forms_host(f, o);
+    } else {
+        LagScalArgs f;
+        lag_form_taps_scal(h->model, a, h->d, mask, K, h->lag_ref, f);
+        f.M = h->lag_M_host.data(); f.s = h->lag_s_host.data(); f.n = h->lag_n;
+        lag_forms_scal_host(f, o);
+    }
     ra.lag_part = n_windows;
     for (int k = 0; k < NACC_MAX; k++) ra.lag_acc[k] = o.acc[k];
     ra.lag_chk = o.chk;
@@ -560,6 +612,61 @@ extern "C" int ssde_lagforms_host(const double* M, const double* s, double n_bul
     lag_forms_host(f, o);
     for (int c = 0; c < 2; c++)
         for (int j = 0; j < LAG_NRAW; j++) raw[c * LAG_NRAW + j] = o.raw[c][j];
+    for (int k = 0; k < 4 + d; k++) acc[k] = o.acc[k];
+    *chk = o.chk;
+    return SSDE_OK;
+}
+
+extern "C" int ssde_lagforms_host_m(int32_t model, const double* M, const double* s, double n_bulk, const double* ref, int32_t d,
+                                    const double* theta, double dt, const double* p0, int32_t K, int32_t mask, int32_t taps_given,
+                                    double* taps, double* raw, double* acc, double* chk) {
+    if (model == SSDE_MODEL_CTCRW) return ssde_lagforms_host(M, s, n_bulk, d, theta, dt, p0, K, mask, taps_given, taps, raw, acc, chk);
+    if (model != SSDE_MODEL_OU_SSM && model != SSDE_MODEL_BM_SSM) return SSDE_ERR_ARG;
+    const bool ou = model == SSDE_MODEL_OU_SSM;
+    if (!M || !s || !theta || !taps || !raw || !acc || !chk || d < 1 || d > 2 || (ou && !ref)) return SSDE_ERR_ARG;
+    if (K < LAG_CHECK || K > LAG_KMAX || !(dt > 0.0) || !std::isfinite(dt)) return SSDE_ERR_ARG;
+    IsoArgs a;
+    memset(&a, 0, sizeof(a));
+    const double sig = exp(theta[0]);
+    a.h = sig * sig;
+    for (int i = 0; i < d; i++) a.mu[i] = theta[1 + i];
+    if (ou) {
+        a.tau = exp(theta[1 + d]);
+        a.sigma = exp(theta[2 + d]);
+        ou_trans(dt, a.tau, a.sigma, a.str);
+    } else {
+        a.sigma = exp(theta[1 + d]);
+        bm_trans(dt, a.sigma, a.str);
+    }
+    // the stationary gains: the covariance half of the filter until it has stopped moving (as build_gain_table)
+    ScalCov<15> C;
+    C.init(p0 ? p0[0] : 1.0);
+    ScalGain G;
+    int stable = 0;
+    for (int t = 0; t < 100000 && stable < GAIN_SETTLED_ROWS; t++) {
+        const ScalCov<15> prev = C;
+        if (ou) { if (d == 1) scal_cov_step<1, 15, true>(C, a.str, a.h, false, G); else scal_cov_step<2, 15, true>(C, a.str, a.h, false, G); }
+        else { if (d == 1) scal_cov_step<1, 15, false>(C, a.str, a.h, false, G); else scal_cov_step<2, 15, false>(C, a.str, a.h, false, G); }
+        bool same = gain_close(C.p, prev.p);
+        for (int j = 0; j < NDIRP && same; j++) same = gain_close(C.dp[j], prev.dp[j]);
+        stable = same ? stable + 1 : 0;
+    }
+    if (stable < GAIN_SETTLED_ROWS || G.iF == 0.0) return SSDE_ERR_ARG;      // (no stationary regime: such an evaluation streams every row)
+    a.gain_stat[0] = G.iF; a.gain_stat[1] = G.k; a.gain_stat[2] = G.c;
+    for (int j = 0; j < NDIRP; j++) { a.gain_stat[4 + j] = G.diF[j]; a.gain_stat[7 + j] = G.dk[j]; }
+    fill_stat_consts(model, d, a);
+    LagScalArgs f;
+    LagFormOut o;
+    lag_form_taps_scal(model, a, d, mask < 0 ? (DIR_SIG | DIR_MU | DIR_P1 | DIR_P2) : mask, K, ref, f);
+    if (taps_given) {                                       // the caller's taps, as they are (nothing beyond the cut is read)
+        for (int i = 0; i < LAG_N; i++) { f.lam[i] = taps[i]; f.t1[i] = taps[LAG_N + i]; f.t3[i] = taps[2 * LAG_N + i]; }
+    } else {
+        for (int i = 0; i < LAG_N; i++) { taps[i] = f.lam[i]; taps[LAG_N + i] = f.t1[i]; taps[2 * LAG_N + i] = f.t3[i]; }
+    }
+    f.M = M; f.s = s; f.n = n_bulk;
+    lag_forms_scal_host(f, o);
+    for (int c = 0; c < 2; c++)
+        for (int j = 0; j < LAG_NRAW_SCAL; j++) raw[c * LAG_NRAW_SCAL + j] = o.raw[c][j];
     for (int k = 0; k < 4 + d; k++) acc[k] = o.acc[k];
     *chk = o.chk;
     return SSDE_OK;

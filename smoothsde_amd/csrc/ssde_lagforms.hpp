@@ -117,4 +117,95 @@ inline void lag_forms_host(const LagFormArgs& A, LagFormOut& o) {
 #pragma clang diagnostic pop
 #endif
 
+// ---- OU_SSM / BM_SSM (the scalar family: BasisScal of ssde_tf.hpp) ------------------------------------------------------------------
+// Over the stationary rows those lanes keep S = sum u^2, S1 = sum u A1, S3 = sum u A3 and macc_a = sum u_a mx_a.  In the bulk every
+// signal sig in {u, A1, A3} is sum_i tap_sig[i] z_{a,t-i} + kap_sig[a]: z the LEVEL y - ref (OU_SSM: the process is stationary around mu,
+// its transfer function has no factor 1 - q^-1) or the INCREMENT y_t - y_{t-1} (BM_SSM: T = 1, u_t = (1 - k) u_{t-1} + Dy_t - mu dt);
+// kap the fixed point of the same step under z == 0 (in closed form: lag_form_taps_scal).  mx has reached its fixed point mx*.  So
+//     sum_t u sig = lam' M tap_sig + sum_a (kap_u[a] tap_sig' s_a + kap_sig[a] lam' s_a + n kap_u[a] kap_sig[a]),
+//     su_a = sum_t u_a = lam' s_a + n kap_u[a],     macc_a = mx* su_a.
+constexpr int LAG_NRAW_SCAL = 5;      // raw sums of a cut: S, S1, S3, su_1, su_2
+
+struct LagScalArgs {
+    const double* M;                  // [LAG_N][LAG_N] (host)
+    const double* s;                  // [2][LAG_N] (host)
+    double n;                         // bulk rows
+    int K, Kc;                        // taps 0..K of the forms, 0..Kc of the check
+    int d, mask;                      // response coordinates, DIR_* bits of the evaluation
+    bool has_p2;                      // OU_SSM (a second scale parameter; A3 lives)
+    double lam[LAG_N], t1[LAG_N], t3[LAG_N];   // responses of u, A1, A3 (as the row's products read them)
+    double ku[2], k1[2], k3[2];       // the affine parts of u, A1, A3 per coordinate
+    double mxs;                       // mx*: d x / d mu at its fixed point
+    double statc[48];                 // the stationary constants (IsoArgs.statc): scal_tf_finish forms the accumulators from them
+};
+
+#if defined(__clang__)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wpass-failed"
+#endif
+// The order of lag_forms_host: per row four partial sums over the blocks of LAG_N / 4 taps, (q0 + q1) + (q2 + q3); the per-row terms;
+// a 256-wide halving tree over the rows; loops stopped at the cut.  o.raw[c][0..4] (raw[c][5] = 0).
+inline void lag_forms_scal_host(const LagScalArgs& A, LagFormOut& o) {
+    static_assert(LAG_N <= 256, "the tree over the rows is 256 wide");
+    constexpr int QB = LAG_N / 4, NR = LAG_NRAW_SCAL;
+    double red[2 * NR][256];
+    for (int j = 0; j < 2 * NR; j++)
+        for (int i = 0; i < 256; i++) red[j][i] = 0.0;
+    for (int c = 0; c < 2; c++) {
+        const int K = c ? A.Kc : A.K;
+        for (int i = 0; i <= K && i < LAG_N; i++) {
+            double q[4] = {0.0, 0.0, 0.0, 0.0};
+            const double* m = A.M + (int64_t)i * LAG_N;     // (symmetric: row i for column i)
+            for (int b = 0; b < 4; b++) {
+                const int k1 = K < (b + 1) * QB - 1 ? K : (b + 1) * QB - 1;
+                double v = 0.0;
+                for (int k = b * QB; k <= k1; k++) v += m[k] * A.lam[k];
+                q[b] = v;
+            }
+            const double V = (q[0] + q[1]) + (q[2] + q[3]);
+            const double li = A.lam[i], a1 = A.t1[i], a3 = A.t3[i];
+            double S = li * V, S1 = a1 * V, S3 = a3 * V;
+            for (int a = 0; a < A.d; a++) {
+                const double sa = A.s[a * LAG_N + i], ku = A.ku[a], k1 = A.k1[a], k3 = A.k3[a];
+                S += 2.0 * ku * li * sa;
+                S1 += (ku * a1 + k1 * li) * sa;
+                S3 += (ku * a3 + k3 * li) * sa;
+                double su = li * sa;
+                if (i == 0) {
+                    S += A.n * ku * ku;
+                    S1 += A.n * ku * k1;
+                    S3 += A.n * ku * k3;
+                    su += A.n * ku;
+                }
+                red[c * NR + 3 + a][i] = su;
+            }
+            red[c * NR + 0][i] = S; red[c * NR + 1][i] = S1; red[c * NR + 2][i] = S3;
+        }
+    }
+    for (int w = 128; w > 0; w >>= 1)
+        for (int j = 0; j < 2 * NR; j++)
+            for (int i = 0; i < w; i++) red[j][i] += red[j][i + w];
+    for (int c = 0; c < 2; c++) {
+        for (int j = 0; j < NR; j++) o.raw[c][j] = red[c * NR + j][0];
+        o.raw[c][NR] = 0.0;
+    }
+    for (int k = 0; k < NACC_MAX; k++) o.acc[k] = 0.0;
+    const double macc[2] = {A.mxs * o.raw[0][3], A.mxs * o.raw[0][4]};
+    scal_tf_finish(A.statc[0], A.statc + 10, A.statc + 13, A.d, A.mask, A.has_p2, o.raw[0][0], o.raw[0][1], o.raw[0][2], macc, o.acc);   // (what the streaming lanes finish with)
+    // the check: as lag_forms_host
+    const double floor_ = std::sqrt(std::fabs(o.raw[0][0]) * A.n);
+    double w = 0.0;
+    for (int j = 0; j < 3 + A.d; j++) {
+        const double a = o.raw[0][j], b = o.raw[1][j];
+        const double sc = std::fmax(std::fmax(std::fabs(a), std::fabs(b)), floor_);
+        const double r = std::fabs(a - b) / sc;
+        w = (r == r) ? std::fmax(w, r) : INFINITY;
+    }
+    if (!(w == w)) w = INFINITY;
+    o.chk = w;
+}
+#if defined(__clang__)
+#pragma clang diagnostic pop
+#endif
+
 }  // namespace ssde

@@ -56,6 +56,43 @@ inline void lag_track_stats(const double* y, int rows, int d, double* Q, double*
     }
 }
 
+// OU_SSM (stationary around mu: no factor 1 - q^-1 to take on the data) needs the same statistics of the LEVELS z_{a,t} = y_{a,t} - ref_a
+// instead of the increments; ref_a is one number per coordinate, fixed at create near the data (the handle's: the observation at
+// row LAG_A - 1 of the first track in tiled order that has a bulk), so that z stays within a few process standard deviations.  The
+// Toeplitz-plus-end-corrections identity holds for any sequence (h_j = z_{A-1-j}, g_j = z_{n-1-j}); s no longer telescopes:
+//     s_{a,0} = sum_{t >= A} z_{a,t},     s_{a,i+1} = s_{a,i} + h_{a,i} - g_{a,i}.
+// e[a][i] = sum over tracks of (h_{a,i} - g_{a,i}), s0[a] = sum over tracks of s_{a,0}  ->  s[a][i]; fixed order
+inline void lag_levels_s(const double* s0, const double* e, double* s) {
+    for (int a = 0; a < 2; a++) {
+        double run = s0[a];
+        for (int i = 0; i < LAG_N; i++) {
+            s[a * LAG_N + i] = run;
+            run += e[a * LAG_N + i];
+        }
+    }
+}
+
+// lag_track_stats for the levels y - ref: Q, D as there; e[a][i] and s0[a] as lag_levels_s takes them
+inline void lag_track_stats_levels(const double* y, int rows, int d, const double* ref, double* Q, double* D, double* e, double* s0) {
+    const int n = rows;
+    if (n <= LAG_A) return;
+    for (int a = 0; a < d; a++) {
+        auto Z = [&](int t) { return y[(int64_t)t * d + a] - ref[a]; };
+        for (int l = 0; l < LAG_N; l++) {
+            double q = 0.0;
+            for (int t = LAG_A; t < n; t++) q += Z(t) * Z(t - l);
+            Q[l] += q;
+        }
+        for (int p = 0; p < LAG_N; p++)
+            for (int q = 0; q < LAG_N; q++)
+                D[(int64_t)p * LAG_N + q] += Z(LAG_A - 1 - p) * Z(LAG_A - 1 - q) - Z(n - 1 - p) * Z(n - 1 - q);
+        for (int i = 0; i < LAG_N; i++) e[a * LAG_N + i] += Z(LAG_A - 1 - i) - Z(n - 1 - i);
+        double z0 = 0.0;
+        for (int t = LAG_A; t < n; t++) z0 += Z(t);
+        s0[a] += z0;
+    }
+}
+
 // (the per-evaluation forms built from M, s and n: ssde_lagforms.hpp, on the host)
 
 }  // namespace ssde

@@ -119,6 +119,26 @@ struct TfCtcrw {
     __device__ static __forceinline__ void warm_a0(const double*, double*) {}
 };
 
+// The accumulators [value | sigma_obs | mu_1 .. mu_d | par d | par d + 1] of the scalar family from the sums of the stationary rows:
+// S = sum u^2, S1 = sum u A1, S3 = sum u A3, macc_a = sum u_a mx_a, with iF, hd_j = 0.5 d iF / d theta_j and dk_j of the stationary
+// gain (IsoArgs.statc[0], [10 + j], [13 + j]).  BasisScal::finish and the bulk's forms (ssde_lagforms.hpp: lag_forms_scal_host) both
+// end here.
+SSDE_HD void scal_tf_finish(double iF, const double* hd, const double* dk, int d, int mask, bool has_p2, double S, double S1, double S3,
+                            const double* macc, double* out) {
+    out[0] = 0.5 * iF * S;
+    const double s3[NDIRP] = {0.0, S3, 0.0};
+    const int slot[NDIRP] = {1, 2 + d, 3 + d};
+#pragma unroll
+    for (int kk = 1; kk < 4 + d; kk++) out[kk] = 0.0;
+#pragma unroll
+    for (int j = 0; j < NDIRP; j++)
+        if ((mask & dir_bit(j)) && (j < 2 || has_p2)) out[slot[j]] = hd[j] * S - iF * (dk[j] * S1 + s3[j]);
+    if (mask & DIR_MU) {
+#pragma unroll
+        for (int a = 0; a < d; a++) out[2 + a] = -iF * macc[a];
+    }
+}
+
 // OU_SSM / BM_SSM: tx_j = dk_j A1 + [j = par n_dim] A3 with A1 <- forcing u, A3 <- forcing dt_ x + db mu
 template <int MODEL, int D, int MASK>
 struct BasisScal {
@@ -131,7 +151,7 @@ struct BasisScal {
     double acc2, S1, S3, macc[D];
     double k, c, t, b, iF, hd[NDIRP], dk[NDIRP], dt_, cmu[D], dbmu[D];
 
-    __device__ __forceinline__ void setup(const IsoArgs& A) {
+    SSDE_HD void setup(const IsoArgs& A) {
         const double* cc = A.statc;
         iF = cc[0]; k = cc[1]; c = cc[2]; t = cc[3]; b = cc[4]; dt_ = cc[5];
 #pragma unroll
@@ -139,18 +159,18 @@ struct BasisScal {
 #pragma unroll
         for (int a = 0; a < D; a++) { cmu[a] = cc[19 + a]; dbmu[a] = cc[21 + a]; }
     }
-    __device__ __forceinline__ void init(const double* a0) {
+    SSDE_HD void init(const double* a0) {
 #pragma unroll
         for (int a = 0; a < D; a++) { x[a] = a0[a]; A1[a] = A3[a] = mx[a] = 0.0; }
         reset_acc();
     }
-    __device__ __forceinline__ void reset_acc() {
+    SSDE_HD void reset_acc() {
         acc2 = S1 = S3 = 0.0;
 #pragma unroll
         for (int a = 0; a < D; a++) macc[a] = 0.0;
     }
-    __device__ __forceinline__ void step_table(const double*, const double*, const double*) {}
-    __device__ __forceinline__ void step_stat(const double* y) {
+    SSDE_HD void step_table(const double*, const double*, const double*) {}
+    SSDE_HD void step_stat(const double* y) {
 #pragma unroll
         for (int a = 0; a < D; a++) {
             const double xx = x[a];
@@ -174,20 +194,7 @@ struct BasisScal {
             x[a] = fma(k, u, fma(t, xx, cmu[a]));
         }
     }
-    __device__ __forceinline__ void finish(double* out) const {
-        out[0] = 0.5 * iF * acc2;
-        const double s3[NDIRP] = {0.0, S3, 0.0};
-        const int slot[NDIRP] = {1, 2 + D, 3 + D};
-#pragma unroll
-        for (int kk = 1; kk < 4 + D; kk++) out[kk] = 0.0;
-#pragma unroll
-        for (int j = 0; j < NDIRP; j++)
-            if ((MASK & dir_bit(j)) && (j < 2 || HAS_P2)) out[slot[j]] = hd[j] * acc2 - iF * (dk[j] * S1 + s3[j]);
-        if (MASK & DIR_MU) {
-#pragma unroll
-            for (int a = 0; a < D; a++) out[2 + a] = -iF * macc[a];
-        }
-    }
+    SSDE_HD void finish(double* out) const { scal_tf_finish(iF, hd, dk, D, MASK, HAS_P2, acc2, S1, S3, macc, out); }
     __device__ __forceinline__ void dump(double* o) const {
         int kk = 0;
 #pragma unroll
