@@ -520,6 +520,18 @@ int ssde_lagstats_read_m(const ssde_handle *h, double *M, double *s, double *n_b
 int ssde_lagforms_host_m(int32_t model, const double *M, const double *s, double n_bulk, const double *ref, int32_t d, const double *theta,
                          double dt, const double *p0, int32_t K, int32_t mask, int32_t taps_given, double *taps, double *raw, double *acc,
                          double *chk);
+/* The final sums of an evaluation whose head finished on the host, without a device: what a synchronous
+   single-device ssde_eval forms from the records its workgroups stored, in the fixed order of the device's reduction -- bitwise the
+   result of the finalize launch.  sums: [n_groups][n_windows][nacc] wave sums; group_chk: [n_groups] hand-over checks; lag_acc: the
+   bulk's `nacc` accumulators, the entry after the last one, or NULL (lag_chk is then ignored); add / add_slot: 4 data-independent
+   terms and the output slot each is added to (< 0: unused); map: [nacc - 1], accumulator k >= 1 -> output slot, or < 0 (slot 0 is
+   accumulator 0).  out: n_out sums, then the check -- the largest of the groups' checks and lag_chk, not-a-number counting as
+   infinity.  SSDE_ERR_ARG: a NULL pointer, a count < 1 or a slot >= n_out. */
+int ssde_reduce_host(const double *sums, const double *group_chk, int32_t n_groups, int32_t n_windows, int32_t nacc, const double *lag_acc,
+                     double lag_chk, const double *add, const int16_t *add_slot, const int16_t *map, int32_t n_out, double *out);
+/* What finished the handle's last evaluation: 0 a finalize launch after the main one, 1 the main launch itself
+   (SSDE_FUSED_FINALIZE=1), 2 the host.  A multi-device parent reports its first shard; -1 for NULL. */
+int ssde_last_finish_form(const ssde_handle *h);
 
 #ifdef __cplusplus
 }

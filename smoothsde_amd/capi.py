@@ -515,6 +515,11 @@ def load_library():
     lib.ssde_lagforms_host_m.argtypes = [C.c_int32, _dp, _dp, C.c_double, _dp, C.c_int32, _dp, C.c_double, _dp, C.c_int32, C.c_int32,
                                          C.c_int32, _dp, _dp, _dp, _dp]
     lib.ssde_lagforms_host_m.restype = C.c_int
+    lib.ssde_reduce_host.argtypes = [_dp, _dp, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_double, _dp, C.POINTER(C.c_int16), C.POINTER(C.c_int16),
+                                     C.c_int32, _dp]
+    lib.ssde_reduce_host.restype = C.c_int
+    lib.ssde_last_finish_form.argtypes = [C.c_void_p]
+    lib.ssde_last_finish_form.restype = C.c_int
     lib.ssde_abi_version.argtypes = []
     lib.ssde_abi_version.restype = C.c_int
     lib.ssde_laplace_eval.argtypes = [C.c_void_p, _dp, C.c_int32, C.c_int32, _dp, _dp, _dp, C.POINTER(SsdeLaplaceOpts)]
@@ -555,7 +560,32 @@ WINDOW_TOL = 1e-11  # largest tolerated relative hand-over disagreement between 
 EXPORTED_SYMBOLS = ("ssde_create", "ssde_eval", "ssde_eval_device", "ssde_penalty", "ssde_report", "ssde_widen_windows", "ssde_relax_windows",
                     "ssde_info", "ssde_destroy", "ssde_last_error", "ssde_abi_version", "ssde_comm_unique_id", "ssde_comm_init_rank", "ssde_forget", "ssde_laplace_eval", "ssde_last_kernel_ms", "ssde_kernel_ms_history",
                     "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth",
-                    "ssde_lagstats_host_m", "ssde_lagstats_read_m", "ssde_lagforms_host_m")
+                    "ssde_lagstats_host_m", "ssde_lagstats_read_m", "ssde_lagforms_host_m", "ssde_reduce_host", "ssde_last_finish_form")
+
+
+def reduce_host(sums, group_chk, n_out, map_, lag_acc=None, lag_chk=0.0, add=None, add_slot=None):
+    """The final sums of an evaluation whose head finished on the host: `sums` [groups][windows][accumulators] wave
+    sums and `group_chk` [groups] hand-over checks -> n_out sums and the check, in the fixed order of the device's reduction.
+    `map_`: accumulator k >= 1 -> output slot or -1; `lag_acc`: the bulk's accumulators (the entry after the last one) or None;
+    `add`, `add_slot`: up to four data-independent terms and their slots."""
+    lib = load_library()
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    G, W, nacc = sums.shape
+    chk = np.ascontiguousarray(group_chk, dtype=np.float64)
+    mp = np.ascontiguousarray(map_, dtype=np.int16)
+    if chk.shape != (G,) or mp.shape != (nacc - 1,):
+        raise ValueError("reduce_host: shapes")
+    ad = np.zeros(4); sl = np.full(4, -1, dtype=np.int16)
+    if add is not None:
+        ad[:len(add)] = add; sl[:len(add_slot)] = add_slot
+    la = None if lag_acc is None else np.ascontiguousarray(lag_acc, dtype=np.float64)
+    out = np.zeros(n_out + 1)
+    i16 = C.POINTER(C.c_int16)
+    st = lib.ssde_reduce_host(sums.ctypes.data_as(_dp), chk.ctypes.data_as(_dp), G, W, nacc, None if la is None else la.ctypes.data_as(_dp),
+                              float(lag_chk), ad.ctypes.data_as(_dp), sl.ctypes.data_as(i16), mp.ctypes.data_as(i16), int(n_out), out.ctypes.data_as(_dp))
+    if st != 0:
+        raise ValueError(f"ssde_reduce_host: status {st}")
+    return out
 
 def lagstats_host(tracks, model="CTCRW", ref=None):
     """The lag statistics ssde_create builds for a stationary batch, computed on the host: `tracks` is a list of
@@ -822,6 +852,10 @@ class Engine:
 
     def set_option(self, option: int, value: int):
         self._check(self.lib.ssde_set_option(self._h, option, value))
+
+    def last_finish_form(self) -> int:
+        """What finished the last evaluation: 0 a finalize launch, 1 the main launch itself, 2 the host."""
+        return int(self.lib.ssde_last_finish_form(self._h))
 
     def forget(self):
         """Drop the memoised last result: the next eval runs on the device even at the same par."""

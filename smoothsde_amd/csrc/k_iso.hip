@@ -814,10 +814,23 @@ __global__ __launch_bounds__(256) void iso_finalize_kernel(const IsoArgs A, cons
         publish_if_last(R, dep);
     } else {
         unsigned long long dep = 0ull;
+        if ((int)blockIdx.x == n_check && A.wg_form) {
+            // the hand-overs were checked inside the main launch (iso_shared_wg_kernel): one value per group in chk[], folded by max
+            double m = 0.0;
+            for (int b = threadIdx.x; b < R.n_chk; b += 256) m = fmax(m, R.chk[b] == R.chk[b] ? R.chk[b] : INFINITY);
+            sh[threadIdx.x] = m;
+            __syncthreads();
+            for (int o = 128; o > 0; o >>= 1) {
+                if ((int)threadIdx.x < o) sh[threadIdx.x] = fmax(sh[threadIdx.x], sh[threadIdx.x + o]);
+                __syncthreads();
+            }
+            if (threadIdx.x == 0 && sh[0] > 0.0) dep = atomicMax((unsigned long long*)A.chk_out, (unsigned long long)__double_as_longlong(sh[0]));
+            __syncthreads();                                     // (reduce_slot below takes sh[])
+        }
         if ((int)blockIdx.x == n_check && threadIdx.x == 0 && A.quiet_flag) {
             // what the switches to quiet rows found (k_iso.hip: run_lane), into the evaluation's check value
             const unsigned long long v = atomicExch((unsigned long long*)A.quiet_flag, 0ull);
-            if (v) dep = atomicMax((unsigned long long*)A.chk_out, v);
+            if (v) dep ^= atomicMax((unsigned long long*)A.chk_out, v);
         }
         if ((int)blockIdx.x == n_check && threadIdx.x == 0 && R.lag_part > 0 && lag_chk_bits(R.lag_chk)) {
             // the difference between the two cuts of the bulk's forms (ssde_lagforms.hpp, by value)
@@ -829,6 +842,7 @@ __global__ __launch_bounds__(256) void iso_finalize_kernel(const IsoArgs A, cons
 
 hipError_t launch_iso_finalize(int model, int d, const IsoArgs& a, const ReduceArgs& r, hipStream_t s) {
     const int n_check = a.dual ? a.tv.n_groups * (a.n_chunks - 1) + a.n_dirty_groups * (a.n_chunks_d - 1)
+                               : a.wg_form ? 0                        // (checked inside the main launch: iso_shared_wg_kernel)
                                : (a.n_chunks > 1 ? a.tv.n_groups * (a.n_chunks - 1) * a.n_parts : 0);
     ReduceArgs rr = r;
     rr.pub_blocks = n_check + r.n_out;

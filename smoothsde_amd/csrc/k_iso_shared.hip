@@ -58,6 +58,9 @@ hipError_t launch_iso_shared(int model, int d, const IsoArgs& a0, const ReduceAr
     const int n_grid_chunks = (a.t0 > 0 && a.t0_delta > 0) ? a.n_chunks - 1 : a.n_chunks;      // (t0_delta == 0: window 0 has a wave of its own)
     dim3 grid((g8 * 8 * n_grid_chunks + WG_WAVES - 1) / WG_WAVES);
     if (grid.x == 0) return hipSuccess;
+    // one workgroup per group (iso_shared_wg_kernel): its windows are the waves of a workgroup, the transient window's wave its own;
+    // the grid above is then one workgroup per group of the padded batch
+    if (a.wg_form && !(a.n_chunks == WG_WAVES && a.t0 > 0 && a.t0_delta == 0 && !a.fused && a.group_mode != 1)) return hipErrorInvalidValue;
     a.fuse_items = a.tv.n_groups * n_grid_chunks;              // (fused launches run every group: the engine sees to it)
     const bool deep = a.deep_prefetch != 0;
     if (model == M_CTCRW) return launch_iso_shared_ctcrw(d, a, r, grid, s, ev0, ev1, deep);

@@ -310,7 +310,8 @@ __device__ __forceinline__ void run_block(Lane& S, const IsoArgs& A, const doubl
 
 // rows [sa, sb) of the lane's window; STAT = stationary gains.  sa is a multiple of SHARED_U.
 // Two register blocks in ping-pong: while one is consumed the other is in flight (no copies).
-template <bool STAT, int D, bool DEEP, class Lane>
+// WG: the waves of the workgroup run the windows of ONE group (iso_shared_wg_kernel) -- only wave 0 walks table rows: one gain slab.
+template <bool STAT, int D, bool DEEP, bool WG, class Lane>
 __device__ __forceinline__ void run_segment(Lane& S, const IsoArgs& A, const double* base, int sa, int sb, int ns,
                                             int ns_min, const double* mu) {
     const int C = A.tv.C, c_obs = A.tv.c_obs;
@@ -322,8 +323,8 @@ __device__ __forceinline__ void run_segment(Lane& S, const IsoArgs& A, const dou
 #else
 #define SSDE_ROWPTR(s) (base + (int64_t)(s) * C * WAVE)
 #endif
-    __shared__ double gain_slab[STAT ? 1 : WG_WAVES][STAT ? 1 : GAIN_SLAB_ROWS * GAIN_ROW];
-    double* slab = gain_slab[STAT ? 0 : (threadIdx.x >> 6)];
+    __shared__ double gain_slab[(STAT || WG) ? 1 : WG_WAVES][STAT ? 1 : GAIN_SLAB_ROWS * GAIN_ROW];
+    double* slab = gain_slab[(STAT || WG) ? 0 : (threadIdx.x >> 6)];
     if constexpr (DEEP && STAT) {
         // THREE register blocks in rotation keep TWO blocks (16 rows) in flight: one response column is 8 B per lane and row,
         // a block in flight is half the bytes of the two-column case, and the stream sat at 4.7 TB/s against 5.7-6.2.  With two
@@ -359,8 +360,11 @@ __device__ __forceinline__ void run_segment(Lane& S, const IsoArgs& A, const dou
 
 // STATONLY: the whole window (warm-up included) lies past the covariance transient -- the lean
 // kernel; otherwise the window touches the transient and also carries the table-phase code.
-template <int MODEL, int D, int MASK, bool STATONLY, bool DEEP>
-__device__ __forceinline__ int run_lane_shared(const IsoArgs& A, int g, int part, int chunk) {
+// WG (iso_shared_wg_kernel): nothing of the window goes to global memory -- the record after its warm-up to rec_in (LDS, this lane's
+// column: component k at rec_in[k * WAVE]), the record at its end to rec_end and the lane's accumulators to acc_out (registers).
+template <int MODEL, int D, int MASK, bool STATONLY, bool DEEP, bool WG = false>
+__device__ __forceinline__ int run_lane_shared(const IsoArgs& A, int g, int part, int chunk, double* rec_in = nullptr,
+                                               double* rec_end = nullptr, double* acc_out = nullptr) {
     typedef typename SharedSel<MODEL, D, MASK, STATONLY>::type Lane;
     constexpr int NACC = 4 + D;
     constexpr int SD = Lane::SD;
@@ -413,22 +417,25 @@ __device__ __forceinline__ int run_lane_shared(const IsoArgs& A, int g, int part
     // warm-up rows [s_begin, s_acc), then scored rows [s_acc, s_end); each split at s_stat
     {
         const int m = STATONLY ? s_begin : min(max(s_stat, s_begin), s_acc);
-        if (!STATONLY) run_segment<false, D, DEEP>(S, A, base, s_begin, m, ns, ns_min, mu);
-        run_segment<true, D, DEEP>(S, A, base, m, s_acc, ns, ns_min, mu);
+        if (!STATONLY) run_segment<false, D, DEEP, WG>(S, A, base, s_begin, m, ns, ns_min, mu);
+        run_segment<true, D, DEEP, WG>(S, A, base, m, s_acc, ns, ns_min, mu);
     }
     if (s_acc > s_begin) {
         double st[Lane::NSTATE];
         S.dump(st);
-        double* o = A.bnd + (((int64_t)pc * tv.n_groups + g) * 2 + 0) * A.bnd_stride * WAVE + lane;
+        double* o = WG ? rec_in : A.bnd + (((int64_t)pc * tv.n_groups + g) * 2 + 0) * A.bnd_stride * WAVE + lane;
 #pragma unroll
-        for (int k = 0; k < Lane::NSTATE; k++) { if (A.fused) dev_store(o + k * WAVE, st[k]); else o[k * WAVE] = st[k]; }      // (fused: device scope -- another wave of this launch reads it)
+        for (int k = 0; k < Lane::NSTATE; k++) { if (!WG && A.fused) dev_store(o + k * WAVE, st[k]); else o[k * WAVE] = st[k]; }      // (fused: device scope -- another wave of this launch reads it)
         S.reset_acc();
     }
     {
         const int m = STATONLY ? s_acc : min(max(s_stat, s_acc), s_end);
-        if (!STATONLY) run_segment<false, D, DEEP>(S, A, base, s_acc, m, ns, ns_min, mu);
-        run_segment<true, D, DEEP>(S, A, base, m, s_end, ns, ns_min, mu);
+        if (!STATONLY) run_segment<false, D, DEEP, WG>(S, A, base, s_acc, m, ns, ns_min, mu);
+        run_segment<true, D, DEEP, WG>(S, A, base, m, s_end, ns, ns_min, mu);
     }
+    if (WG) {
+        if (chunk + 1 < A.n_chunks) S.dump(rec_end);
+    } else
     if (A.n_chunks > 1 && chunk + 1 < A.n_chunks) {
         double st[Lane::NSTATE];
         S.dump(st);
@@ -441,6 +448,11 @@ __device__ __forceinline__ int run_lane_shared(const IsoArgs& A, int g, int part
     if (s_acc >= s_end || ns == 0) {
 #pragma unroll
         for (int k = 0; k < NACC; k++) out[k] = 0.0;
+    }
+    if (WG) {
+#pragma unroll
+        for (int k = 0; k < NACC; k++) acc_out[k] = out[k];
+        return s_end - s_begin;
     }
 #pragma unroll
     for (int k = 0; k < NACC; k++) {
@@ -510,6 +522,93 @@ __global__ __launch_bounds__(WG_WAVES * WAVE, 1) void iso_shared_kernel(const Is
 }
 
 
+// ---- one workgroup per track group -----------------------------------------------------------------------------------------------------
+// The latency plan of the lag-statistics head with n_chunks == WG_WAVES (ssde_windows.hpp: head_latency_plan): the windows of a group
+// are the waves of ONE workgroup, one per SIMD of its CU -- wave 0 the transient window and nothing else, wave w >= 1 the lean
+// stationary-only code on window w.  Workgroup b owns group b (the groups padded to eight, as decode_block pads them; the padding
+// workgroups leave whole).  What the two sides of a window boundary have to say to each other never leaves the CU: window w's record
+// after its warm-up goes to LDS, the record at a window's end stays in registers, and after ONE barrier wave c compares its end with
+// window c + 1's record -- the arithmetic of window_check_wave (per component the largest |a - b| and max(|a|, |b|) over the lanes,
+// the worst ratio, not-a-number -> infinity, lanes whose track ends before the boundary masked): order-free maxima, so the value is
+// bitwise what iso_finalize_kernel's check workgroups and fused_finalize_wave find.  Every wave leaves its 4 + D wave sums and its
+// check in LDS; after a second barrier wave 0 owns the group's record and sends it out with ONE store instruction: to the host's
+// mailbox (A.mbx: system-scope stores, a wait for them -- no fence, as publish_if_last --, then the evaluation's sequence word, which
+// the host spins on: ssde_reduce_host.hpp forms the result) or to partials / chk[g] for a finalize launch without check workgroups.
+template <int MODEL, int D, int MASK, bool DEEP>
+__global__ __launch_bounds__(WG_WAVES * WAVE, 1) void iso_shared_wg_kernel(const IsoArgs A, const ReduceArgs R) {
+    typedef typename SharedSel<MODEL, D, MASK, false>::type Lane0;
+    typedef typename SharedSel<MODEL, D, MASK, true>::type LaneS;
+    constexpr int NACC = 4 + D, NST = Lane0::NSTATE;
+    static_assert(NST == LaneS::NSTATE, "both lane forms dump the direction-form record");
+    static_assert(WG_WAVES * NACC <= MBX_CHK && WG_WAVES * NACC < WAVE, "a group's record is one store of wave 0");
+    __shared__ double rec[WG_WAVES - 1][NST][WAVE];           // [c]: window c + 1's record after its warm-up
+    __shared__ double wsum[WG_WAVES][NACC + 1];               // a wave's sums | its boundary's check
+    static_assert(sizeof(double) * ((WG_WAVES - 1) * NST * WAVE + WG_WAVES * (NACC + 1) + GAIN_SLAB_ROWS * GAIN_ROW) <= 64 * 1024,
+                  "static LDS of a workgroup: the hand-over records, the sums and wave 0's gain slab");
+    if (blockIdx.x == 0 && threadIdx.x == 0 && A.chk_out && !A.mbx) *A.chk_out = 0.0;       // raised by the finalize launch
+    const int g = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (g >= A.tv.n_groups) return;                            // (the whole workgroup: nobody is left at a barrier)
+    const long long wc0 = A.wave_clock ? wall_clock64() : 0;
+    double end[NST], acc[NACC];
+    int rows;
+    if (w == 0) rows = run_lane_shared<MODEL, D, MASK, false, DEEP, true>(A, g, 0, 0, nullptr, end, acc);
+    else rows = run_lane_shared<MODEL, D, MASK, true, DEEP, true>(A, g, 0, w, &rec[w - 1][0][lane], end, acc);
+    __syncthreads();                                           // every window's record is in LDS (a wave whose lanes all ended early is here too)
+    double worst = 0.0;
+    if (w + 1 < WG_WAVES) {
+        int sb_, s_next, se_;
+        window_bounds(A.tv.group_len[g], A.n_chunks, A.window, A.t0, w + 1, sb_, s_next, se_, A.t0_delta);
+        const bool valid = (A.tv.lane_nsteps[g * WAVE + lane] > s_next) && (s_next < A.tv.group_len[g]);
+#pragma unroll
+        for (int k = 0; k < NST; k++) {
+            const double a = valid ? end[k] : 0.0, b = valid ? rec[w][k][lane] : 0.0;
+            double err = fabs(a - b), sc = fmax(fabs(a), fabs(b));
+            if (valid && !(err == err)) err = INFINITY;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                err = fmax(err, __shfl_xor(err, o, 64));
+                sc = fmax(sc, __shfl_xor(sc, o, 64));
+            }
+            if (err > 0.0) worst = fmax(worst, err / sc);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NACC; k++) {
+        const double t = wave_sum(acc[k]);
+        if (lane == 0) wsum[w][k] = t;
+    }
+    if (lane == 0) wsum[w][NACC] = worst;
+    __syncthreads();
+    if (w == 0) {
+        double chk = 0.0;
+#pragma unroll
+        for (int c = 0; c + 1 < WG_WAVES; c++) {
+            const double v = wsum[c][NACC];
+            chk = fmax(chk, v == v ? v : INFINITY);
+        }
+        const int c = lane / NACC, k = lane - c * NACC;
+        const bool sum_lane = lane < WG_WAVES * NACC;
+        const double v = sum_lane ? wsum[c][k] : chk;
+        if (A.mbx) {
+            double* o = A.mbx + (int64_t)g * MBX_STRIDE;
+            if (sum_lane || lane == MBX_CHK) __hip_atomic_store(o + lane, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the record has left before its sequence word does
+            if (lane == 0) __hip_atomic_store((unsigned long long*)(o + MBX_SEQ), A.mbx_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        } else {
+            const int G = A.tv.n_groups;
+            if (sum_lane) A.partials[((int64_t)c * NACC + k) * G + g] = v;        // ([window][accumulator][group], as iso_shared_kernel)
+            if (lane == WG_WAVES * NACC) A.chk[g] = chk;
+        }
+    }
+    if (A.wave_clock && lane == 0 && rows > 0) {
+        unsigned hw;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+        double* o = A.wave_clock + 4 * (int64_t)(blockIdx.x * WG_WAVES + w);
+        o[0] = (double)wc0; o[1] = (double)wall_clock64(); o[2] = (double)hw; o[3] = 1.0 + rows;
+    }
+}
+
+
 // One translation unit per model (k_iso_shared_ctcrw.hip, ..._ou.hip, ..._bm.hip): one kernel per (dimension, direction
 // mask, prefetch depth) is ~100 kernels, minutes of compile time each way -- split, they build side by side.
 template <int MODEL, int D, bool DEEP>
@@ -520,13 +619,15 @@ static hipError_t launch_masks(const IsoArgs& a, const ReduceArgs& r, dim3 grid,
     // hipExtLaunchKernelGGL stamps ev0 / ev1 with the kernel's own begin / end (what rocprof reports), not with the
     // stream position of separately recorded events
     // (ev0 == NULL: a plain launch -- SSDE_OPT_KERNEL_STAMPS off -- which costs the host and the queue a few microseconds less)
-#define SSDE_CASE(M) case M: if (ev0) hipExtLaunchKernelGGL((iso_shared_kernel<MODEL, D, M, DEEP>), grid, block, 0, s, ev0, ev1, 0, a, r); \
-                             else hipLaunchKernelGGL((iso_shared_kernel<MODEL, D, M, DEEP>), grid, block, 0, s, a, r); break;
+#define SSDE_LAUNCH_K(K, M) { if (ev0) hipExtLaunchKernelGGL((K<MODEL, D, M, DEEP>), grid, block, 0, s, ev0, ev1, 0, a, r); \
+                              else hipLaunchKernelGGL((K<MODEL, D, M, DEEP>), grid, block, 0, s, a, r); }
+#define SSDE_CASE(M) case M: if (a.wg_form) SSDE_LAUNCH_K(iso_shared_wg_kernel, M) else SSDE_LAUNCH_K(iso_shared_kernel, M) break;
         SSDE_CASE(0) SSDE_CASE(1) SSDE_CASE(2) SSDE_CASE(3) SSDE_CASE(4) SSDE_CASE(5) SSDE_CASE(6) SSDE_CASE(7)
 #if SSDE_SHARED_HAS_P2
         SSDE_CASE(8) SSDE_CASE(9) SSDE_CASE(10) SSDE_CASE(11) SSDE_CASE(12) SSDE_CASE(13) SSDE_CASE(14) SSDE_CASE(15)
 #endif
 #undef SSDE_CASE
+#undef SSDE_LAUNCH_K
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

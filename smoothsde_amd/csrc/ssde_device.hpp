@@ -27,7 +27,8 @@ constexpr int WAVE = 64;
 constexpr int WG_WAVES = 4;       // waves per workgroup of the register Kalman kernels: the four waves of a
                                  // workgroup land on the four SIMDs of one CU, which is what balances the SIMDs
                                  // (single-wave workgroups were observed to be packed unevenly); the waves are
-                                 // independent work items and never synchronise
+                                 // independent work items and never synchronise -- except in iso_shared_wg_kernel,
+                                 // where they are the windows of one track group and hand over through LDS
 constexpr int TILE_U = 4;        // steps per prefetch block of the general register kernel
 constexpr int WIN_ALIGN = 16;    // time-window starts / lengths / warm-ups are multiples of this many rows
 #ifndef SSDE_SHARED_U
@@ -44,6 +45,10 @@ constexpr int MAX_COLS = 96;     // streamed design columns (dense / direct kern
 constexpr int MAX_Q = 4;         // SDE parameters per row (d + 2, d <= 2)
 constexpr int HESS_T = 8;         // exact Hessians: coefficient pairs are cut into HESS_T x HESS_T tiles
 constexpr int DRIFT_KMAX = 24;   // streamed drift columns of the shared-covariance kernel with a row-varying drift (k_iso_drift.hip)
+// a group's record in the host's mailbox (IsoArgs.mbx; iso_shared_wg_kernel), in doubles: WG_WAVES windows x (4 + d <= 6) wave sums,
+// the group's hand-over check, the evaluation's sequence word; 256-byte records
+constexpr int MBX_CHK = WG_WAVES * 6, MBX_SEQ = MBX_CHK + 1, MBX_STRIDE = 32;
+static_assert(MBX_SEQ < MBX_STRIDE, "mailbox record");
 
 struct TileView {
     const double* tiles;
@@ -201,6 +206,14 @@ struct IsoArgs {
     int fuse_items;              // work items (waves that run a window) of this launch
     unsigned* fuse_arrive;       // [n_chunks - 1][n_groups] arrivals at a boundary (zero between launches)
     unsigned* fuse_done;         // one word: work items that have finished (zero between launches)
+    // One workgroup per track group (iso_shared_wg_kernel, k_iso_shared.inc: the transient window on a wave of its own and n_chunks ==
+    // WG_WAVES): the hand-overs are checked in LDS, wave 0 of a workgroup owns its group's record -- n_chunks x (4 + d) wave sums and
+    // the group's check.  mbx != NULL: the record goes to the host's mailbox (pinned; MBX_STRIDE doubles per group: the sums
+    // [window][accumulator], the check at MBX_CHK, then this evaluation's sequence number at MBX_SEQ) and the host forms the result
+    // (ssde_reduce_host.hpp); NULL: sums to `partials`, the group's check to chk[g], and a finalize launch without check workgroups follows.
+    int wg_form;
+    double* mbx;
+    unsigned long long mbx_seq;
     // ... the same models with the gradient by a reverse sweep (k_iso_adj.hip): the state entering every CB-th row of a window
     double* adj_ckpt;            // [work item][adj_ckpt_stride]
     int64_t adj_ckpt_stride;     // doubles per work item: checkpoints of its window x state doubles x 64

@@ -77,6 +77,7 @@ void release_device(ssde_handle* h) {
     h->partials.release(); h->out.release();
     if (h->par_pinned) (void)hipHostFree(h->par_pinned);
     if (h->pub_pinned) (void)hipHostFree(h->pub_pinned);
+    if (h->mbx_pinned) (void)hipHostFree(h->mbx_pinned);
     h->pub_count.release();
     if (h->par_ev_ok)
         for (int i = 0; i < PAR_RING; i++) (void)hipEventDestroy(h->par_ev[i]);
@@ -134,6 +135,9 @@ int eval_device(ssde_handle* h, const double* par, int order, double* out_dev, h
     ra.n_out = 1 + L.n_full;
     ra.out = out_dev;
     for (int k = 0; k < MAX_PAR + 16; k++) ra.map[k] = -1;
+    // (a synchronous single-engine evaluation: the head's workgroups may hand their records to the host instead -- eval_iso decides)
+    h->host_finish_ok = h->pub_request && !h->knobs.publish && !h->stamps && out_dev == h->out.p;
+    h->host_armed = false;
     if (h->pub_request && h->knobs.publish && out_dev == h->out.p) {
         // a synchronous evaluation: the reducing launch publishes the result itself (ssde_device.hpp: ReduceArgs.pub)
         ra.pub = h->pub_pinned; ra.pub_flag = h->pub_flag; ra.pub_seq = ++h->pub_seq; ra.pub_count = h->pub_count.p;
@@ -493,6 +497,33 @@ int run_once(ssde_handle* h, const double* par, int order, double* o) {
     // launches.  Rounds 1 and 2 had measured a pinned mirror as SLOWER; that was with the stamps on and a host that
     // synchronised the stream first.)  In the engine the two measure the same (round 3, fence-free counting); the blocking copy
     // stays the default and SSDE_PUBLISH=1 selects the spin.
+    if (h->host_armed) {
+        // The head's workgroups store their group's record into the pinned mailbox and this evaluation's sequence number after it
+        // (iso_shared_wg_kernel): wait for every group's word, then form the sums here in the device's order (ssde_reduce_host.hpp).
+        // No finalize launch, no read-back copy.
+        h->host_armed = false;
+        const unsigned long long want = h->mbx_seq;
+        const int G = h->n_groups;
+        int g = 0;
+        for (uint64_t spins = 1; g < G; spins++) {
+            const unsigned long long* word = (const unsigned long long*)(h->mbx_pinned + (size_t)g * MBX_STRIDE + MBX_SEQ);
+            if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == want) { g++; continue; }
+            if ((spins & 0xFFFF) == 0) {
+                // a launch that failed never writes: ask the runtime now and then instead of spinning for ever
+                const hipError_t q = hipStreamQuery(0);
+                if (q == hipSuccess && __atomic_load_n(word, __ATOMIC_ACQUIRE) != want) { h->err = "evaluation ended without its groups' records"; return SSDE_ERR_HIP; }
+                if (q != hipSuccess && q != hipErrorNotReady) { h->err = std::string("evaluation failed on the device: ") + hipGetErrorString(q); return SSDE_ERR_HIP; }
+            }
+            __builtin_ia32_pause();
+        }
+        const ReduceArgs& ra = h->host_ra;
+        ReduceHostArgs rh;
+        rh.sums = h->mbx_pinned; rh.group_stride = MBX_STRIDE; rh.chk = h->mbx_pinned + MBX_CHK; rh.chk_stride = MBX_STRIDE;
+        rh.n_groups = G; rh.n_windows = ra.n_value_parts; rh.nacc = ra.nacc;
+        rh.lag_acc = ra.lag_part > 0 ? ra.lag_acc : nullptr; rh.lag_chk = ra.lag_chk;
+        rh.add = ra.add; rh.add_slot = ra.add_slot; rh.map = ra.map; rh.n_out = ra.n_out;
+        reduce_host(rh, o, h->reduce_scratch);
+    } else
     if (h->pub_armed) {
         h->pub_armed = false;
         const unsigned long long want = h->pub_seq;

@@ -19,6 +19,7 @@
 #include "ssde_host.hpp"
 #include "ssde_knobs.hpp"
 #include "ssde_lagstats.hpp"
+#include "ssde_reduce_host.hpp"
 #include "ssde_tv.hpp"
 #include "ssde_windows.hpp"
 
@@ -170,7 +171,16 @@ struct ssde_handle {
     bool cv_single = false;        // ... with constant tau / nu: one wave per (group, window) runs filter and tangents (iso_full_kernel)
     bool cv_few = false;           // few design columns, H = sigma_obs^2 I: one wave per (group, window) too (iso_few_kernel)
     DevBuf<unsigned> fuse_words;   // the fused finalising work of iso_shared_kernel: [0] finished work items, [2..3] the check word, [4..] arrivals per (boundary, group)
-    bool last_fused = false;
+    int last_finish_form = 0;      // what finished the last evaluation: 0 a finalize launch, 1 fused in the main launch, 2 the host (ssde_last_finish_form)
+    // The head finished on the host (iso_shared_wg_kernel with IsoArgs.mbx, ssde_reduce_host.hpp): the workgroups store their group's
+    // record into this pinned mailbox, the synchronous call spins on the groups' sequence words and forms the result itself.  One per
+    // handle: a synchronous call has consumed it before the next one starts.
+    double* mbx_pinned = nullptr;             // [n_groups][MBX_STRIDE]
+    unsigned long long mbx_seq = 0;
+    bool host_finish_ok = false;              // eval_device: this evaluation is a synchronous single-engine ssde_eval into h->out
+    bool host_armed = false;                  // the evaluation just enqueued ends in the mailbox (set by eval_iso, consumed by run_once)
+    ReduceArgs host_ra;                       // ... and these are its reduction's arguments (add, map, the bulk's forms)
+    std::vector<double> reduce_scratch;
     bool cv_adj = false;           // gradient by a reverse sweep: one wave per (group, window), two passes (iso_adj_kernel)
     DevBuf<double> adj_ckpt;       // ... the state entering every adj_ckpt_rows-th row of every window (grown on demand)
     bool cv_one_wave() const { return cv_single || cv_few || cv_adj; }

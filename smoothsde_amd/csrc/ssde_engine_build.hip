@@ -495,6 +495,9 @@ static int plan_register_path(ssde_handle* h, int G, const std::vector<int32_t>&
         // (measured, profiles/r05_fused_finalize_ab.txt: SLOWER than the dependent launch it replaces -- a wave's way from "my rows are
         //  done" to "the result is out" is six device-scope round trips of ~2 us across the XCDs -- so the two-launch form stays the
         //  default and SSDE_FUSED_FINALIZE=1 selects this one, bitwise the same numbers)
+        // the mailbox of the head that finishes on the host (iso_shared_wg_kernel): one record per group
+        HIPCHK(h, hipHostMalloc((void**)&h->mbx_pinned, (size_t)G * MBX_STRIDE * 8, hipHostMallocDefault));
+        memset(h->mbx_pinned, 0, (size_t)G * MBX_STRIDE * 8);
     }
     if (h->drift == 3) HIPCHK(h, hipMemset(h->bnd.p, 0, h->bnd.n * 8));      // (a part dumps its own block of a hand-over record; the check reads all of it)
     h->partial_doubles = (size_t)std::max(MAX_PARTS, CV_WAVES) * buf_chunks * std::max(NACC_MAX, 2 + CV_KC + 2) * G;

@@ -450,7 +450,19 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
     }
     // The finalising work inside the main launch (fused_finalize_wave, ssde_device.hpp): the shared-covariance kernel alone on the
     // batch (no group on the general kernel, no drift columns); SSDE_FUSED_FINALIZE=0: the two-launch form (A/B -- bitwise the same)
-    const bool fused = h->use_shared && !h->drift && h->n_clean_groups == h->n_groups && !h->hess_req && h->fuse_words.p && h->knobs.fused_finalize.value_or(false);
+    const bool shared_alone = h->use_shared && !h->drift && h->n_clean_groups == h->n_groups && !h->hess_req;
+    const bool fused = shared_alone && h->fuse_words.p && h->knobs.fused_finalize.value_or(false);
+    // One workgroup per track group (iso_shared_wg_kernel): the latency plan's geometry -- the transient window on a wave of its own --
+    // with exactly a workgroup's worth of windows.  The hand-overs are checked in LDS; a synchronous single-engine call has the records
+    // sent to its mailbox and forms the result on the host (run_once), every other caller gets them in device memory and a finalize
+    // launch without check workgroups.  SSDE_FUSED_FINALIZE unset: this form; = 0: the two-launch form on iso_shared_kernel (A/B).
+    static_assert(HEAD_WG_WAVES == WG_WAVES, "the plan credits the windows of one workgroup");
+    const bool wg = shared_alone && !h->knobs.fused_finalize && a.n_parts == 1 && a.t0 > 0 && a.t0_delta == 0 && a.n_chunks == WG_WAVES;
+    const bool host_finish = wg && h->host_finish_ok && h->mbx_pinned;
+    if (wg) {
+        a.wg_form = 1;
+        if (host_finish) { a.mbx = h->mbx_pinned; a.mbx_seq = ++h->mbx_seq; }
+    }
     if (h->use_shared) {
         // two independent launches (NaN-free groups on the shared-covariance kernel, NaN-carrying groups on
         // the general kernel): fork onto a side stream so they share the chip, join before the hand-over check
@@ -553,10 +565,12 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
     }
     if (h->knobs.trace) { const double t = tick(); h->trace_us[2] += t - tk0; tk0 = t; }
     if (!fused) fill_reduce_args(h, a, order, add, ra);
+    if (wg) ra.n_chk = h->n_groups;                     // (one check per group, from the main launch)
     if (!fused && lag_K > 0) { const int st = lag_forms_into(h, a, order, lag_K, a.n_chunks, ra); if (st) return st; }     // (the head is running: this overlaps it)
     // the hand-over checks and the final sums in one launch (unless the main launch has done them)
-    if (!fused) HIPCHK(h, launch_iso_finalize(h->model, h->d, a, ra, s));
-    h->last_fused = fused;
+    if (host_finish) { h->host_ra = ra; h->host_armed = true; }      // (run_once: the spin on the mailbox and reduce_host)
+    else if (!fused) HIPCHK(h, launch_iso_finalize(h->model, h->d, a, ra, s));
+    h->last_finish_form = host_finish ? 2 : fused ? 1 : 0;
     if (h->knobs.trace) {
         const double t = tick(); h->trace_us[3] += t - tk0; h->trace_n++;
         if (h->trace_skip < 8) {                        // the first calls load code objects: not what is being measured
@@ -569,6 +583,23 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
 }
 
 }  // namespace ssde_engine
+
+extern "C" int ssde_reduce_host(const double* sums, const double* group_chk, int32_t n_groups, int32_t n_windows, int32_t nacc,
+                                const double* lag_acc, double lag_chk, const double* add, const int16_t* add_slot, const int16_t* map,
+                                int32_t n_out, double* out) {
+    if (!sums || !group_chk || !add || !add_slot || !map || !out || n_groups < 1 || n_windows < 1 || nacc < 1 || n_out < 1) return SSDE_ERR_ARG;
+    for (int k = 0; k + 1 < nacc; k++) if (map[k] >= n_out) return SSDE_ERR_ARG;
+    for (int i = 0; i < 4; i++) if (add_slot[i] >= n_out) return SSDE_ERR_ARG;
+    const ReduceHostArgs a = {sums, (int64_t)n_windows * nacc, group_chk, 1, n_groups, n_windows, nacc, lag_acc, lag_chk, add, add_slot, map, n_out};
+    std::vector<double> scratch;
+    reduce_host(a, out, scratch);
+    return SSDE_OK;
+}
+
+extern "C" int ssde_last_finish_form(const ssde_handle* h) {
+    if (!h) return -1;
+    return h->shards.empty() ? h->last_finish_form : h->shards[0]->last_finish_form;
+}
 
 extern "C" int ssde_lagforms_host(const double* M, const double* s, double n_bulk, int32_t d, const double* theta, double dt,
                                   const double* p0, int32_t K, int32_t mask, int32_t taps_given, double* taps, double* raw,

@@ -21,7 +21,8 @@ struct Knobs {
     std::optional<int> chunks, window, adj_tail, tv_waves, tv_minlen;   // time-window geometry (window, adj_tail, tv_waves >= 1; tv_minlen a multiple of WIN_ALIGN)
     std::optional<int> drift_min_tracks, cv_adj;     // a track count decides for the register lanes / 0: forward tangents everywhere, 2: the reverse sweep for few columns too
     std::optional<int> lagstats;                     // 0: never built, 2: built whatever the rule says, 1: the rule (as unset)
-    std::optional<bool> fused_finalize;              // the finalising work inside iso_shared_kernel (unset: off -- it is slower)
+    std::optional<bool> fused_finalize;              // 1: the finalising work inside iso_shared_kernel (slower); 0: always a finalize launch after
+                                                     // iso_shared_kernel; unset: one workgroup per group where the plan allows it (iso_shared_wg_kernel)
     std::optional<std::string> iso_split, wave_clock;   // "fused" / "split" / explicit masks ("3,4,8"); the file the per-wave stamps go to at destroy
     int quiet_window = 0, adj_diag = 0;              // rows of memory after a missing row (0: the plan's warm-up); timing-experiment bits of iso_adj_kernel
     double grid_rtol = 1e-12;                        // how far an interval may be from the grid step and still count as regular (lattice_pad)

@@ -26,6 +26,13 @@ constexpr double T0_COST = 3.0, W0_RATIO = 1.2;
 // a stationary-only wave walks 48 rows in 5.2 - 6.5 us -- 0.12 us a row, one 8-row block per memory round trip.
 constexpr double HEAD_T0_COST = 1.8;
 constexpr int HEAD_WAVE_SLOTS = 1024;      // SIMDs of the chip: one wave each is one round of the head's launch
+// A head whose windows are exactly the waves of ONE workgroup (HEAD_WG_WAVES = WG_WAVES of ssde_device.hpp, one wave per SIMD of a CU)
+// checks its hand-overs in LDS and needs no dependent finalize launch for them (k_iso_shared.inc: iso_shared_wg_kernel).
+// HEAD_WG_CREDIT: what that saves, in stationary rows of a lone wave (0.12 us a row) -- the two-launch form's extra microseconds per
+// evaluation over the one-launch form on the same four windows of the bench's batch, finalize launch and read-back copy together:
+// 5.7 us (medians 0.0478 against 0.0421 ms per step, profiles/r09_a_head_wg_ab.txt), 5.7 / 0.12 rows.
+constexpr int HEAD_WG_WAVES = 4;
+constexpr double HEAD_WG_CREDIT = 47.0;
 
 // the layout constants the policy reads: WIN_ALIGN and SHARED_U of ssde_device.hpp, LAG_A and LAG_KMAX of ssde_lagstats.hpp (a
 // host-only header does not include the former; the engine's one instance is WINDOW_CONSTS, ssde_engine.hpp)
@@ -246,7 +253,8 @@ struct WindowGeometry {
 //   * the shared-wave geometry the throughput rules give (g as it comes in: the transient window on the wave of window 1, which is
 //     shortened by t0_delta), its longest wave by window_bounds' rules (ssde_device.hpp);
 //   * the transient window on a wave of its own (t0_delta = 0) and k = 1 .. max_chunks - 1 stationary windows dealt [t0, LAG_A)
-//     equally: chain(k) = max(HEAD_T0_COST t0, W + ceil(units / k) WIN_ALIGN), rounds(k) = ceil(groups padded to 8 x (k + 1) / 1024).
+//     equally: chain(k) = max(HEAD_T0_COST t0, W + ceil(units / k) WIN_ALIGN), rounds(k) = ceil(groups padded to 8 x (k + 1) / 1024);
+//     k + 1 == HEAD_WG_WAVES is credited with HEAD_WG_CREDIT rows: those windows are one workgroup, which finishes in one launch.
 // The cheapest is taken; at equal cost the shorter stationary chain (the transient's cost is a measured average: the plan should
 // not hinge on it where more windows are free), then the fewer windows.  The shared-wave geometry stays unless one is strictly cheaper:
 // with more groups than wave slots the rounds term keeps it.  Buffers are sized by max_chunks, which bounds k + 1.
@@ -278,7 +286,7 @@ inline void head_latency_plan(const WindowFacts& f, const WindowConsts& c, Windo
     int best_k = 0, best_stat = 0;
     for (int k = 1; k <= kmax; k++) {
         const int stat = W + ceil_div(units, k) * WA;
-        const double cost = rounds(k + 1) * std::max(transient, (double)stat);
+        const double cost = rounds(k + 1) * std::max(transient, (double)stat) - (k + 1 == HEAD_WG_WAVES ? HEAD_WG_CREDIT : 0.0);
         if (cost < best_cost || (best_k > 0 && cost == best_cost && stat < best_stat)) { best_cost = cost; best_k = k; best_stat = stat; }
     }
     if (best_k > 0) { g.n_chunks = best_k + 1; g.t0_delta = 0; }

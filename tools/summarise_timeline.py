@@ -2,7 +2,7 @@
 """tools/summarise_timeline.py DIR STEM [WARMUP] -- the timeline of one lag-path evaluation from a rocprofv3 run
 (--kernel-trace --memory-copy-trace --hip-trace --output-format csv -d DIR -o STEM, bench.py after `--`).
 
-An evaluation = the commands around one iso_shared_kernel dispatch: host-to-device copies and the forms' launch before it (where
+An evaluation = the commands around one iso_shared_kernel (or iso_shared_wg_kernel) dispatch: host-to-device copies and the forms' launch before it (where
 the trace shows them), the finalize launch and device-to-host copies after it.  Prints, as medians over the evaluations that have
 the most frequent shape (the timed steps; the first WARMUP of them dropped, default 5 = bench.py's): each command's duration, each
 gap, the span from the first command's start to the last one's end, and the host side from the HIP API trace -- the evaluation's
@@ -36,9 +36,10 @@ for r in rows("memory_copy_trace"):
     n = "copy H2D" if "HOST_TO_DEVICE" in dirn else "copy D2H" if "DEVICE_TO_HOST" in dirn else "copy " + dirn
     ev.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), n))
 ev.sort()
-heads = [i for i, e in enumerate(ev) if e[2] == "iso_shared_kernel"]
+HEADS = ("iso_shared_kernel", "iso_shared_wg_kernel")      # (the second: one workgroup per track group)
+heads = [i for i, e in enumerate(ev) if e[2] in HEADS]
 if not heads:
-    sys.exit("no iso_shared_kernel dispatch in the trace")
+    sys.exit("no iso_shared_kernel / iso_shared_wg_kernel dispatch in the trace")
 NEAR = 200000       # ns: a command further than this from the head launch belongs to something else
 evals = []
 for a, b in zip(heads, heads[1:] + [len(ev)]):
