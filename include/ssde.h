@@ -25,6 +25,8 @@
  *                                                nllk_ou_ssm.hpp:215, nllk_bm_ssm.hpp:177)
  *   ssde_smooth        <- (new) fixed-interval Kalman smoother and whitened innovations of the state-space families: what
  *                         the reference's SDE$residuals() stops at (R/sde.R:1186-1228) and aest_all does not give
+ *   ssde_smooth_draws  <- (new) joint posterior draws of the whole state path (backward sampling over the smoother's records):
+ *                         what speed, distance travelled, time in a region or multiple imputation are computed from
  *   ssde_penalty       <- smoothing penalty     (nllk_ctcrw.hpp:254-280, nllk_sde.hpp:89-124)
  *   ssde_info          <- InfoADFunObject       (src/init.c:7)
  *   ssde_forget        <- (new) drops the memo of ssde_eval
@@ -334,6 +336,22 @@ int ssde_report(ssde_handle *h, const double *par, int32_t n_par_full, double *a
  * state and every later ssde_eval result as they were; the per-row records live in a buffer of the call's own, capped by
  * SSDE_OPT_SMOOTH_BUDGET_MB (tracks are processed in chunks of whole wavefront groups; the result does not depend on it). */
 int ssde_smooth(ssde_handle *h, const double *par, int32_t n_par_full, double *a_smooth, double *P_smooth, double *resid);
+
+/* Joint posterior draws of the whole state path at `par` (definitions: DESIGN.md §3.10): backward sampling over the smoother's own
+ * forward records, so a draw carries the dependence BETWEEN rows that the row-wise a_smooth / P_smooth leave out.
+ *   draws [n x sdim x n_draws]: element (i, c, k) at i + n * (c + sdim * k) -- draw k is one aest_all-layout matrix; it is draw number
+ *   draw0 + k of the stream `seed`.  NaN on rows without a state.  flags: SSDE_DRAWS_DEVICE_OUT (1) = `draws` is an HBM pointer on the
+ *   handle's device (single-device handles; nothing is copied to the host).
+ * Every deviate is a pure function of (seed, the track's ordinal in the caller's data, the state row's position in the track as the
+ * handle holds it -- the lattice position on a lattice-padded handle --, draw number, state column): Philox4x32-10 + Box-Muller as
+ * ssde_simulate.  The result does not depend on SSDE_OPT_SMOOTH_BUDGET_MB, on the devices or on how the draws are cut over calls.
+ * SSDE_ERR_MODEL for the direct families and ESEAL_SSM (as ssde_smooth) and for a handle whose response runs as ONE coupled filter of
+ * three or more columns (a per-row H_array or P0 that couples them); uncoupled wide responses run as column pairs and ARE served.
+ * SSDE_ERR_ARG for n_draws < 1, draw0 < 0, draw0 + n_draws >= 2^28, NULL pointers, an unknown flag, and SSDE_DRAWS_DEVICE_OUT on a
+ * multi-device handle.  Leaves the memo, the window state, the TV records and every later ssde_eval result as they were. */
+#define SSDE_DRAWS_DEVICE_OUT 1u
+int ssde_smooth_draws(ssde_handle *h, const double *par, int32_t n_par_full, uint64_t seed, int64_t draw0, int32_t n_draws,
+                      double *draws, uint32_t flags);
 
 /* Multiply the warm-up overlap of the time windows by `factor` for all later evaluations
  * (factor <= 0: force one sequential window). */

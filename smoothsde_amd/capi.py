@@ -489,6 +489,8 @@ def load_library():
     lib.ssde_report.restype = C.c_int
     lib.ssde_smooth.argtypes = [C.c_void_p, _dp, C.c_int32, _dp, _dp, _dp]
     lib.ssde_smooth.restype = C.c_int
+    lib.ssde_smooth_draws.argtypes = [C.c_void_p, _dp, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.c_void_p, C.c_uint32]
+    lib.ssde_smooth_draws.restype = C.c_int
     lib.ssde_widen_windows.argtypes = [C.c_void_p, C.c_int32]
     lib.ssde_widen_windows.restype = C.c_int
     lib.ssde_relax_windows.argtypes = [C.c_void_p]
@@ -555,11 +557,13 @@ class EngineError(RuntimeError):
     status = None
 
 
+DRAWS_DEVICE_OUT = 1   # ssde_smooth_draws flag: `draws` is an HBM pointer on the handle's device (include/ssde.h)
+
 WINDOW_TOL = 1e-11  # largest tolerated relative hand-over disagreement between time windows
 
 EXPORTED_SYMBOLS = ("ssde_create", "ssde_eval", "ssde_eval_device", "ssde_penalty", "ssde_report", "ssde_widen_windows", "ssde_relax_windows",
                     "ssde_info", "ssde_destroy", "ssde_last_error", "ssde_abi_version", "ssde_comm_unique_id", "ssde_comm_init_rank", "ssde_forget", "ssde_laplace_eval", "ssde_last_kernel_ms", "ssde_kernel_ms_history",
-                    "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth",
+                    "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth", "ssde_smooth_draws",
                     "ssde_lagstats_host_m", "ssde_lagstats_read_m", "ssde_lagforms_host_m", "ssde_reduce_host", "ssde_last_finish_form")
 
 
@@ -903,6 +907,27 @@ class Engine:
         self._check(self.lib.ssde_smooth(self._h, par.ctypes.data_as(_dp), self.n_par_full, mean.ctypes.data_as(_dp),
                                          P.ctypes.data_as(_dp) if cov else None, e.ctypes.data_as(_dp) if resid else None))
         return {"mean": mean, "cov": P, "resid": e}
+
+    def smooth_draws(self, par, n_draws: int, seed: int = 0, draw0: int = 0, out=None):
+        """Joint posterior draws of the whole state path at `par` (ssde_smooth_draws): an array of shape
+        (n_draws, n, sdim), draw k being draw number draw0 + k of the stream `seed`; NaN on rows without a state (a track's first
+        row).  A draw is the same numbers whichever call, batch or device computes it.  `out`: a contiguous float64 torch tensor of
+        that shape on the handle's device -- the draws are left in HBM (SSDE_DRAWS_DEVICE_OUT) and `out` is returned."""
+        par = np.ascontiguousarray(par, dtype=np.float64)
+        if par.shape != (self.n_par_full,):
+            raise ValueError(f"par must have length {self.n_par_full}")
+        n, sd = self.problem.n, self.problem.sdim
+        if out is not None:
+            import torch
+            if tuple(out.shape) != (n_draws, sd, n) or not out.is_contiguous() or not out.is_cuda or out.dtype != torch.float64:
+                raise ValueError("out must be a contiguous float64 device tensor of shape (n_draws, sdim, n): the C layout of the draws")
+            self._check(self.lib.ssde_smooth_draws(self._h, par.ctypes.data_as(_dp), self.n_par_full, int(seed), int(draw0), int(n_draws),
+                                                   C.c_void_p(out.data_ptr()), DRAWS_DEVICE_OUT))
+            return out.transpose(1, 2)
+        buf = np.zeros((max(int(n_draws), 0), sd, n))                                  # element (i, c, k) at i + n (c + sdim k)
+        self._check(self.lib.ssde_smooth_draws(self._h, par.ctypes.data_as(_dp), self.n_par_full, int(seed), int(draw0), int(n_draws),
+                                               buf.ctypes.data_as(C.c_void_p), 0))
+        return buf.transpose(0, 2, 1)
 
     def close(self):
         if self._h:

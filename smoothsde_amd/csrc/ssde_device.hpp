@@ -603,6 +603,22 @@ struct SmoothArgs {
 int smooth_rec_doubles(int model, int d);
 hipError_t launch_smooth_back(const SmoothArgs& a, hipStream_t s);
 hipError_t launch_smooth_tv_record(const TvArgs& t, const SmoothArgs& a, hipStream_t s);   // PATH_TV: lane = track, long-format rows
+// ---- joint posterior draws of the state path (k_smooth_draws.hip, ssde_draws.hpp) ----
+// The records, groups and lanes of a SmoothArgs `s` (its outputs are not read); a batch of n_draws draws, number draw0 + k of the
+// stream `seed`, draw k one [n_out x sdim] matrix at out + k * draw_stride (n_out * sdim, or more where the columns sit inside a wider
+// state's matrix).  DRAW_CH draws per wave: the grid's second dimension.
+constexpr int DRAW_CH = 4;
+struct DrawArgs {
+    SmoothArgs s;
+    const int64_t* lane_trk;     // [groups * 64]: the lane's ID segment in the handle's data (ssde_handle::lane_seg) ...
+    int64_t track0;              // ... and the segments of the shards before it: their sum is the deviates' track counter
+    int64_t draw_stride;         // doubles from one draw's matrix to the next
+    uint64_t seed;
+    uint32_t draw0;
+    int n_draws, col0;           // col0: the handle's first state column inside the whole state (column pairs), even
+    double* out;
+};
+hipError_t launch_smooth_draws(const DrawArgs& a, hipStream_t s);
 hipError_t launch_tv_a0(const TvArgs& a, const double* a0_src, const int64_t* trk_seg, int64_t n_seg, int sdim,
                         double* a0_dst, hipStream_t s);
 hipError_t launch_tv_prepare(const TvArgs& a, hipStream_t s);

@@ -237,6 +237,9 @@ struct ssde_handle {
     bool tv_dense = false;         // full-covariance lanes: per-row H_array and / or a P0 that is not block-identical
     DevBuf<TvDir> tv_dirs;
     DevBuf<int64_t> tv_row0;
+    // [lanes] the ID segment (in the handle's data) of every lane's track, tiled routes and PATH_TV alike: a0 at create, and the
+    // deviates' track counter of ssde_smooth_draws
+    DevBuf<int64_t> lane_seg;
     DevBuf<int32_t> tv_ns;
     DevBuf<TvItem> tv_items_g, tv_items_v;     // work items of a gradient / a value-only evaluation
     std::vector<int32_t> tv_ns_host;

@@ -1130,12 +1130,12 @@ static int build_impl(const ssde_desc* d, ssde_handle* h, const ParLayout* part_
         HIPCHK(h, h->group_len.upload(glen));
         HIPCHK(h, h->lane_row0.upload(lane_row0));
         HIPCHK(h, h->lane_nsteps.upload(lane_ns));
+        HIPCHK(h, h->lane_seg.upload(lane_seg));
         h->glen_host = glen; h->lane_ns_host = lane_ns;
 
         // stage the caller's arrays (host data) -- freed again after tiling
         DevBuf<double> s_h, s_a0, s_cols;
         DevBuf<const double*> s_colptr;
-        DevBuf<int64_t> s_lane_seg;
         const double* p_h = d->h_array;
         if (!t_on_dev) {
             if (h->has_h) { HIPCHK(h, stage(d->h_array, (size_t)tn * d->n_dim * d->n_dim, false, s_h)); p_h = s_h.p; }
@@ -1163,7 +1163,6 @@ static int build_impl(const ssde_desc* d, ssde_handle* h, const ParLayout* part_
             // a0 is tiny (n_seg x sdim): always treated as a host array
             HIPCHK(h, stage(d->a0, (size_t)h->n_seg * h->sdim, false, s_a0));
             p_a0 = s_a0.p;
-            HIPCHK(h, s_lane_seg.upload(lane_seg));
         }
         const int ych = ingest_ychunks(G);
         DevBuf<double> mm;
@@ -1174,7 +1173,7 @@ static int build_impl(const ssde_desc* d, ssde_handle* h, const ParLayout* part_
         ia.lane_row0 = h->lane_row0.p; ia.lane_nsteps = h->lane_nsteps.p;
         ia.group_off = h->group_off.p; ia.group_len = h->group_len.p;
         ia.n_groups = G; ia.C = h->C; ia.c_obs = h->c_obs; ia.tiles = h->tiles.p; ia.a0 = h->a0.p;
-        ia.a0_src = p_a0; ia.lane_seg = s_lane_seg.p; ia.n_seg = h->n_seg;
+        ia.a0_src = p_a0; ia.lane_seg = h->lane_seg.p; ia.n_seg = h->n_seg;
         ia.sdim = h->sdim; ia.model = d->model; ia.dt_minmax = mm.p; ia.ychunks = ych; ia.last_dt = h->last_dt;
         HIPCHK(h, launch_ingest(ia, 0));
         std::vector<double> mmh((size_t)G * ych * 3);
@@ -1197,7 +1196,7 @@ static int build_impl(const ssde_desc* d, ssde_handle* h, const ParLayout* part_
         h->dt_min = std::isfinite(dmin) ? dmin : 0.0;
         h->dt_max = std::isfinite(dmax) ? dmax : 0.0;
         mm.release(); s_times.release(); s_obs.release(); s_h.release(); s_a0.release(); s_cols.release();
-        s_colptr.release(); s_lane_seg.release();
+        s_colptr.release();
         pad_times.release(); pad_obs.release();
         h->hbm_bytes = h->tile_doubles * 8;
 

@@ -1,4 +1,5 @@
-// ssde_engine_smooth.hip -- ssde_smooth: the fixed-interval smoother of the Kalman families.
+// ssde_engine_smooth.hip -- ssde_smooth: the fixed-interval smoother of the Kalman families, and
+// ssde_smooth_draws: joint posterior draws of the state path from the same records.
 //
 // A forward pass in record mode (dense_kernel MODE 2 on the tiled routes, smooth_tv_record_kernel on PATH_TV) writes every state
 // row's record, smooth_back_kernel walks them back and writes the smoothed mean, covariance and whitened innovation in the long
@@ -33,91 +34,99 @@ std::vector<int> chunk_groups(const std::vector<int64_t>& goff, int64_t budget) 
     return cut;
 }
 
-int smooth_single(ssde_handle* h, const double* par, double* a_smooth, double* P_smooth, double* resid) {
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(0));
-    const int sd = h->sdim, d = h->d;
-    const int R = smooth_rec_doubles(h->model, d);
-    if (R <= 0) { h->err = "ssde_smooth: no smoother for this response width"; return SSDE_ERR_MODEL; }
-    const bool tv = h->path == PATH_TV;
-    const int64_t nt = (!tv && h->n_pad > 0) ? h->n_pad : h->n;        // rows of the layout the kernels write
-    DevBuf<double> am, Vm, em, rec, pbuf;
+// The record-producing half of a smoother call, shared by ssde_smooth and ssde_smooth_draws: the parameter vector, the groups' record
+// offsets, the chunk plan under the budget, the record buffer and the forward launch's arguments.  produce(c) fills the buffer with
+// chunk c's records and leaves `s` addressing them.
+struct RecordRun {
+    ssde_handle* h = nullptr;
+    bool tv = false;
+    int R = 0;
+    int64_t nt = 0, n_lanes = 0, budget = 0;
+    DevBuf<double> rec, pbuf;
     DevBuf<int64_t> offb;
-    SmoothBufs guard{{&am, &Vm, &em, &rec, &pbuf}, {&offb}};
-    // the outputs, NaN (all bits set) where no state row writes
-    if (a_smooth) { HIPCHK(h, am.alloc((size_t)nt * sd)); HIPCHK(h, hipMemset(am.p, 0xff, (size_t)nt * sd * 8)); }
-    if (P_smooth) { HIPCHK(h, Vm.alloc((size_t)nt * sd * sd)); HIPCHK(h, hipMemset(Vm.p, 0xff, (size_t)nt * sd * sd * 8)); }
-    if (resid) { HIPCHK(h, em.alloc((size_t)nt * d)); HIPCHK(h, hipMemset(em.p, 0xff, (size_t)nt * d * 8)); }
-    HIPCHK(h, pbuf.upload(std::vector<double>(par, par + h->L.n_full)));
-
-    // the groups' record offsets (doubles; 64-bit throughout)
-    std::vector<int32_t> glen;
-    int64_t n_lanes = 0;
-    if (tv) {
-        std::vector<int32_t> ns((size_t)h->n_seg);
-        if (h->n_seg) HIPCHK(h, hipMemcpy(ns.data(), h->tv_ns.p, (size_t)h->n_seg * 4, hipMemcpyDeviceToHost));
-        n_lanes = h->n_seg;
-        for (int64_t t = 0; t < h->n_seg; t += WAVE) {
-            int32_t m = 0;
-            for (int64_t k = t; k < std::min<int64_t>(t + WAVE, h->n_seg); k++) m = std::max(m, ns[k]);
-            glen.push_back(m);
-        }
-    } else {
-        glen.resize((size_t)h->n_groups);
-        if (h->n_groups) HIPCHK(h, hipMemcpy(glen.data(), h->group_len.p, (size_t)h->n_groups * 4, hipMemcpyDeviceToHost));
-        n_lanes = (int64_t)h->n_groups * WAVE;
-    }
-    const int G = (int)glen.size();
-    std::vector<int64_t> goff((size_t)G + 1, 0);
-    for (int g = 0; g < G; g++) goff[g + 1] = goff[g] + (int64_t)glen[g] * R * WAVE;
-    HIPCHK(h, offb.upload(goff));
-    int64_t budget;
-    if (h->smooth_budget_mb > 0) budget = h->smooth_budget_mb * (int64_t)(1 << 20) / 8;
-    else {
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
-        budget = (int64_t)(free_b / 4 / 8);
-    }
-    const std::vector<int> cut = chunk_groups(goff, budget);
-    int64_t biggest = 0;
-    for (size_t c = 0; c + 1 < cut.size(); c++) biggest = std::max(biggest, goff[cut[c + 1]] - goff[cut[c]]);
-    HIPCHK(h, rec.alloc((size_t)std::max<int64_t>(biggest, 1)));
-
+    DevBuf<SlotTable> stb;
+    std::vector<int64_t> goff;
+    std::vector<int> cut;
     SmoothArgs s;
-    memset(&s, 0, sizeof(s));
-    s.model = h->model; s.d = d; s.rec = rec.p; s.rec_off = offb.p;
-    s.am = am.p; s.Vm = Vm.p; s.em = em.p; s.n_out = nt; s.n_lanes = n_lanes;
     TvArgs ta;
     DenseArgs da;
     SlotTable stab;
-    DevBuf<SlotTable> stb;
-    if (tv) {
-        tv_base_args(h, ta);
-        ta.par = pbuf.p;
-        const double sig = exp(par[0]);
-        ta.h = sig * sig;
-        s.lane_row0 = h->tv_row0.p; s.lane_ns = h->tv_ns.p;
-    } else {
-        memset(&stab, 0, sizeof(stab));
-        stab.n_slots = (int)h->slots.size(); stab.q = h->q;
-        for (size_t k = 0; k < h->slots.size(); k++) {
-            stab.par_j[k] = (int16_t)h->slots[k].par_j; stab.col[k] = (int16_t)h->slots[k].col;
-            stab.pidx[k] = (int16_t)h->slots[k].pidx; stab.is_free[k] = 0;
+    ~RecordRun() { rec.release(); pbuf.release(); offb.release(); stb.release(); }
+    size_t n_chunks() const { return cut.size() - 1; }
+
+    int setup(ssde_handle* h_, const double* par, const char* who) {
+        h = h_;
+        const int d = h->d;
+        R = smooth_rec_doubles(h->model, d);
+        if (R <= 0) { h->err = std::string(who) + ": no smoother for this response width"; return SSDE_ERR_MODEL; }
+        tv = h->path == PATH_TV;
+        nt = (!tv && h->n_pad > 0) ? h->n_pad : h->n;        // rows of the layout the kernels write
+        HIPCHK(h, pbuf.upload(std::vector<double>(par, par + h->L.n_full)));
+
+        // the groups' record offsets (doubles; 64-bit throughout)
+        std::vector<int32_t> glen;
+        if (tv) {
+            std::vector<int32_t> ns((size_t)h->n_seg);
+            if (h->n_seg) HIPCHK(h, hipMemcpy(ns.data(), h->tv_ns.p, (size_t)h->n_seg * 4, hipMemcpyDeviceToHost));
+            n_lanes = h->n_seg;
+            for (int64_t t = 0; t < h->n_seg; t += WAVE) {
+                int32_t m = 0;
+                for (int64_t k = t; k < std::min<int64_t>(t + WAVE, h->n_seg); k++) m = std::max(m, ns[k]);
+                glen.push_back(m);
+            }
+        } else {
+            glen.resize((size_t)h->n_groups);
+            if (h->n_groups) HIPCHK(h, hipMemcpy(glen.data(), h->group_len.p, (size_t)h->n_groups * 4, hipMemcpyDeviceToHost));
+            n_lanes = (int64_t)h->n_groups * WAVE;
         }
-        HIPCHK(h, stb.upload(std::vector<SlotTable>(1, stab)));
-        memset(&da, 0, sizeof(da));
-        da.tv.tiles = h->tiles.p; da.tv.group_off = h->group_off.p; da.tv.group_len = h->group_len.p;
-        da.tv.lane_nsteps = h->lane_nsteps.p; da.tv.a0 = h->a0.p; da.tv.n_groups = h->n_groups; da.tv.C = h->C; da.tv.c_obs = h->c_obs;
-        da.tv.dt_all = h->dt_all;
-        da.model = h->model; da.d = d; da.any_nan = h->na_any; da.has_h = h->has_h ? 1 : 0;
-        da.slots = stb.p; da.par = pbuf.p; da.n_slots = stab.n_slots;
-        for (int i = 0; i < 256; i++) da.p0[i] = h->p0_full[i];
-        da.n_dirblocks = 1; da.pp = h->pp_drift;
-        da.lane_row0 = h->lane_row0.p; da.n = nt; da.last_dt = h->last_dt;
-        da.srec = rec.p; da.srec_off = offb.p;
-        s.lane_row0 = h->lane_row0.p; s.lane_ns = h->lane_nsteps.p;
+        const int G = (int)glen.size();
+        goff.assign((size_t)G + 1, 0);
+        for (int g = 0; g < G; g++) goff[g + 1] = goff[g] + (int64_t)glen[g] * R * WAVE;
+        HIPCHK(h, offb.upload(goff));
+        if (h->smooth_budget_mb > 0) budget = h->smooth_budget_mb * (int64_t)(1 << 20) / 8;
+        else {
+            size_t free_b = 0, total_b = 0;
+            HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
+            budget = (int64_t)(free_b / 4 / 8);
+        }
+        cut = chunk_groups(goff, budget);
+        int64_t biggest = 0;
+        for (size_t c = 0; c + 1 < cut.size(); c++) biggest = std::max(biggest, goff[cut[c + 1]] - goff[cut[c]]);
+        HIPCHK(h, rec.alloc((size_t)std::max<int64_t>(biggest, 1)));
+
+        memset(&s, 0, sizeof(s));
+        s.model = h->model; s.d = d; s.rec = rec.p; s.rec_off = offb.p;
+        s.n_out = nt; s.n_lanes = n_lanes;
+        if (tv) {
+            tv_base_args(h, ta);
+            ta.par = pbuf.p;
+            const double sig = exp(par[0]);
+            ta.h = sig * sig;
+            s.lane_row0 = h->tv_row0.p; s.lane_ns = h->tv_ns.p;
+        } else {
+            memset(&stab, 0, sizeof(stab));
+            stab.n_slots = (int)h->slots.size(); stab.q = h->q;
+            for (size_t k = 0; k < h->slots.size(); k++) {
+                stab.par_j[k] = (int16_t)h->slots[k].par_j; stab.col[k] = (int16_t)h->slots[k].col;
+                stab.pidx[k] = (int16_t)h->slots[k].pidx; stab.is_free[k] = 0;
+            }
+            HIPCHK(h, stb.upload(std::vector<SlotTable>(1, stab)));
+            memset(&da, 0, sizeof(da));
+            da.tv.tiles = h->tiles.p; da.tv.group_off = h->group_off.p; da.tv.group_len = h->group_len.p;
+            da.tv.lane_nsteps = h->lane_nsteps.p; da.tv.a0 = h->a0.p; da.tv.n_groups = h->n_groups; da.tv.C = h->C; da.tv.c_obs = h->c_obs;
+            da.tv.dt_all = h->dt_all;
+            da.model = h->model; da.d = d; da.any_nan = h->na_any; da.has_h = h->has_h ? 1 : 0;
+            da.slots = stb.p; da.par = pbuf.p; da.n_slots = stab.n_slots;
+            for (int i = 0; i < 256; i++) da.p0[i] = h->p0_full[i];
+            da.n_dirblocks = 1; da.pp = h->pp_drift;
+            da.lane_row0 = h->lane_row0.p; da.n = nt; da.last_dt = h->last_dt;
+            da.srec = rec.p; da.srec_off = offb.p;
+            s.lane_row0 = h->lane_row0.p; s.lane_ns = h->lane_nsteps.p;
+        }
+        return SSDE_OK;
     }
-    for (size_t c = 0; c + 1 < cut.size(); c++) {
+
+    int produce(size_t c) {
         const int g0 = cut[c], ng = cut[c + 1] - cut[c];
         s.g0 = g0; s.n_groups = ng; s.rec_base = goff[g0];
         if (tv) {
@@ -126,7 +135,29 @@ int smooth_single(ssde_handle* h, const double* par, double* a_smooth, double* P
             da.g0 = g0; da.srec_groups = ng; da.srec_base = goff[g0];
             HIPCHK(h, launch_dense(da, false, 0));
         }
-        HIPCHK(h, launch_smooth_back(s, 0));
+        return SSDE_OK;
+    }
+};
+
+int smooth_single(ssde_handle* h, const double* par, double* a_smooth, double* P_smooth, double* resid) {
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(0));
+    const int sd = h->sdim, d = h->d;
+    if (smooth_rec_doubles(h->model, d) <= 0) { h->err = "ssde_smooth: no smoother for this response width"; return SSDE_ERR_MODEL; }
+    const int64_t nt = (h->path != PATH_TV && h->n_pad > 0) ? h->n_pad : h->n;
+    DevBuf<double> am, Vm, em;
+    SmoothBufs guard{{&am, &Vm, &em}, {}};
+    // the outputs, NaN (all bits set) where no state row writes
+    if (a_smooth) { HIPCHK(h, am.alloc((size_t)nt * sd)); HIPCHK(h, hipMemset(am.p, 0xff, (size_t)nt * sd * 8)); }
+    if (P_smooth) { HIPCHK(h, Vm.alloc((size_t)nt * sd * sd)); HIPCHK(h, hipMemset(Vm.p, 0xff, (size_t)nt * sd * sd * 8)); }
+    if (resid) { HIPCHK(h, em.alloc((size_t)nt * d)); HIPCHK(h, hipMemset(em.p, 0xff, (size_t)nt * d * 8)); }
+    RecordRun run;
+    { int st = run.setup(h, par, "ssde_smooth"); if (st) return st; }
+    run.s.am = am.p; run.s.Vm = Vm.p; run.s.em = em.p;
+    for (size_t c = 0; c < run.n_chunks(); c++) {
+        int st = run.produce(c);
+        if (st) return st;
+        HIPCHK(h, launch_smooth_back(run.s, 0));
     }
     // back to the caller's rows (a lattice-padded handle: the lattice row OF each caller row), then to the host
     auto fetch = [&](DevBuf<double>& src, int ncol, double* dst) -> int {
@@ -146,8 +177,69 @@ int smooth_single(ssde_handle* h, const double* par, double* a_smooth, double* P
     if (!st) st = fetch(Vm, sd * sd, P_smooth);
     if (!st) st = fetch(em, d, resid);
     if (!st) HIPCHK(h, hipStreamSynchronize(0));
-    stb.release();
     return st;
+}
+
+// draws [n x sdim x n_draws] of one engine, into host memory or (dev_out) HBM on the handle's device.  Draw k's matrix starts at
+// draws + k * stride doubles (stride = n * sdim for a handle of its own; a column pair writes its columns into the parent's wider
+// matrices).  track0: the ID segments of the shards before this one; col0: the handle's first state column in the whole state.
+int draws_single(ssde_handle* h, const double* par, uint64_t seed, int64_t draw0, int n_draws, double* draws, bool dev_out,
+                 int64_t stride, int64_t track0, int col0) {
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(0));
+    const int sd = h->sdim;
+    if (h->d > 2) {
+        h->err = "ssde_smooth_draws: a response of three or more columns that runs as ONE coupled filter is not served (uncoupled wide responses run as column pairs and are)";
+        return SSDE_ERR_MODEL;
+    }
+    RecordRun run;
+    { int st = run.setup(h, par, "ssde_smooth_draws"); if (st) return st; }
+    const int64_t nt = run.nt, n = h->n;
+    if ((int64_t)h->lane_seg.n < run.n_lanes) { h->err = "ssde_smooth_draws: the handle holds no track ordinals for its lanes"; return SSDE_ERR_ARG; }
+    DevBuf<double> batch, rows;
+    SmoothBufs guard{{&batch, &rows}, {}};
+    // Draws per batch: what fits beside the records (the budget again; a draw always goes).  A device output on the caller's own rows is
+    // written in place; otherwise a batch is staged (and, on a lattice-padded handle, gathered to the caller's rows) before it leaves.
+    const bool in_place = dev_out && nt == n;
+    const int64_t per_draw = std::max<int64_t>(nt * sd, 1);
+    int64_t budget = run.budget;
+    if (h->smooth_budget_mb <= 0) {
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
+        budget = (int64_t)(free_b / 4 / 8);
+    }
+    const int64_t nb_max = std::min<int64_t>(std::max<int64_t>(budget / per_draw, 1), (int64_t)DRAW_CH << 15);
+    const int nb_cap = (int)std::min<int64_t>(nb_max, n_draws);
+    if (!in_place) HIPCHK(h, batch.alloc((size_t)nt * sd * nb_cap));
+    if (nt != n) HIPCHK(h, rows.alloc((size_t)n * sd * nb_cap));
+    DrawArgs a;
+    memset(&a, 0, sizeof(a));
+    a.lane_trk = h->lane_seg.p; a.track0 = track0; a.seed = seed; a.col0 = col0;
+    a.draw_stride = in_place ? stride : nt * sd;
+    bool have_records = false;
+    for (int k0 = 0; k0 < n_draws; k0 += nb_cap) {
+        const int nb = std::min(nb_cap, n_draws - k0);
+        double* dst = in_place ? draws + (size_t)k0 * stride : batch.p;
+        // NaN (all bits set) where no state row writes
+        if (nt * sd > 0) HIPCHK(h, hipMemset2D(dst, (size_t)a.draw_stride * 8, 0xff, (size_t)nt * sd * 8, (size_t)nb));
+        a.draw0 = (uint32_t)(draw0 + k0); a.n_draws = nb; a.out = dst;
+        for (size_t c = 0; c < run.n_chunks(); c++) {
+            if (!have_records || run.n_chunks() > 1) { int st = run.produce(c); if (st) return st; }
+            have_records = true;
+            a.s = run.s;
+            HIPCHK(h, launch_smooth_draws(a, 0));
+        }
+        if (in_place || n * sd == 0) continue;
+        const double* src = batch.p;
+        if (nt != n) {                                                      // the lattice row OF each caller row, every draw's columns
+            HIPCHK(h, launch_lattice_gather(h->pad_row.p, batch.p, n, nt, sd * nb, rows.p, 0));
+            src = rows.p;
+        }
+        HIPCHK(h, hipMemcpy2D(draws + (size_t)k0 * stride, (size_t)stride * 8, src, (size_t)n * sd * 8, (size_t)n * sd * 8, (size_t)nb,
+                              dev_out ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    }
+    HIPCHK(h, hipStreamSynchronize(0));
+    return SSDE_OK;
 }
 
 }  // namespace
@@ -183,9 +275,56 @@ int smooth_sharded(ssde_handle* parent, const double* par, double* a_smooth, dou
     return SSDE_OK;
 }
 
+// the shards' and column pairs' draws, each counted by the GLOBAL track ordinal and state column, placed in the parent's layout
+int draws_sharded(ssde_handle* parent, const double* par, uint64_t seed, int64_t draw0, int n_draws, double* draws, bool dev_out) {
+    const int64_t n = parent->n;
+    const int SD = parent->sdim, P = std::max(parent->n_dim_parts, 1);
+    if (!dev_out) std::fill(draws, draws + (size_t)n * SD * n_draws, std::numeric_limits<double>::quiet_NaN());
+    int64_t track0 = 0;
+    for (size_t k = 0; k < parent->shards.size(); k++) {
+        ssde_handle* sh = parent->shards[k];
+        const int64_t lo = parent->shard_row0[k], m = parent->shard_nrows[k];
+        const int sd = sh->sdim, c0 = parent->shard_col0[k];
+        if (dev_out) {
+            // the column pairs of ONE device: every pair holds all the rows and writes (or gathers) its columns straight into the
+            // parent's matrices in HBM, batch by batch under the budget like any single handle
+            if (lo != 0 || m != n) { parent->err = "ssde_smooth_draws: SSDE_DRAWS_DEVICE_OUT needs a single-device handle"; return SSDE_ERR_ARG; }
+            int st = draws_single(sh, par, seed, draw0, n_draws, draws + (size_t)n * c0, true, (int64_t)n * SD, track0, c0);
+            if (st) { parent->err = sh->err; return st; }
+        } else {
+            std::vector<double> t((size_t)m * sd * n_draws);
+            int st = draws_single(sh, par, seed, draw0, n_draws, t.data(), false, (int64_t)m * sd, track0, c0);
+            if (st) { parent->err = sh->err; return st; }
+            for (int q = 0; q < n_draws; q++)
+                for (int c = 0; c < sd; c++)
+                    memcpy(draws + (size_t)n * ((c0 + c) + (size_t)SD * q) + lo, t.data() + (size_t)m * (c + (size_t)sd * q), (size_t)m * 8);
+        }
+        if ((k + 1) % P == 0) track0 += sh->n_seg;                          // the next track shard's first ordinal
+    }
+    return SSDE_OK;
+}
+
 }  // namespace ssde_engine
 
 extern "C" {
+
+int ssde_smooth_draws(ssde_handle* h, const double* par, int32_t n_par_full, uint64_t seed, int64_t draw0, int32_t n_draws,
+                      double* draws, uint32_t flags) {
+    if (!h || !par || !draws) { if (h) h->err = "ssde_smooth_draws: no parameter vector, or no output"; return SSDE_ERR_ARG; }
+    if (n_par_full != h->L.n_full) { h->err = "parameter vector has the wrong length"; return SSDE_ERR_ARG; }
+    if (n_draws < 1 || draw0 < 0 || draw0 + (int64_t)n_draws >= ((int64_t)1 << 28)) {
+        h->err = "ssde_smooth_draws: n_draws >= 1, draw0 >= 0 and draw0 + n_draws < 2^28 are required";
+        return SSDE_ERR_ARG;
+    }
+    if (flags & ~(uint32_t)SSDE_DRAWS_DEVICE_OUT) { h->err = "ssde_smooth_draws: unknown flag"; return SSDE_ERR_ARG; }
+    if (!is_kalman(h->model)) { h->err = "the smoother serves the Kalman families only (the direct families have no state; ESEAL_SSM no REPORT)"; return SSDE_ERR_MODEL; }
+    const bool dev_out = (flags & SSDE_DRAWS_DEVICE_OUT) != 0;
+    if (!h->shards.empty()) {
+        if (dev_out && h->n_track_shards > 1) { h->err = "ssde_smooth_draws: SSDE_DRAWS_DEVICE_OUT needs a single-device handle"; return SSDE_ERR_ARG; }
+        return draws_sharded(h, par, seed, draw0, n_draws, draws, dev_out);
+    }
+    return draws_single(h, par, seed, draw0, n_draws, draws, dev_out, (int64_t)h->n * h->sdim, 0, 0);
+}
 
 int ssde_smooth(ssde_handle* h, const double* par, int32_t n_par_full, double* a_smooth, double* P_smooth, double* resid) {
     if (!h || !par || (!a_smooth && !P_smooth && !resid)) { if (h) h->err = "ssde_smooth: no parameter vector, or no output asked for"; return SSDE_ERR_ARG; }

@@ -72,6 +72,7 @@ int build_tv(const ssde_desc* d, ssde_handle* h, const std::vector<int64_t>& sta
     }
     HIPCHK(h, h->tv_row0.upload(row0));
     HIPCHK(h, h->tv_ns.upload(ns));
+    HIPCHK(h, h->lane_seg.upload(seg));
     h->tv_ns_host = ns;
     h->glen_max = M > 0 ? ns[0] : 0;
     // gradient directions: log_sigma_obs, then every free coefficient slot
@@ -130,14 +131,12 @@ int build_tv(const ssde_desc* d, ssde_handle* h, const std::vector<int64_t>& sta
     HIPCHK(h, launch_tv_weights(a, 0));
     {
         DevBuf<double> s_a0;
-        DevBuf<int64_t> s_seg;
         if (d->a0) {
             HIPCHK(h, stage(d->a0, (size_t)h->n_seg * h->sdim, false, s_a0));   // a0 is tiny: always a host array
-            HIPCHK(h, s_seg.upload(seg));
         }
-        HIPCHK(h, launch_tv_a0(a, s_a0.p, s_seg.p, h->n_seg, h->sdim, h->tv_a0.p, 0));
+        HIPCHK(h, launch_tv_a0(a, s_a0.p, d->a0 ? h->lane_seg.p : nullptr, h->n_seg, h->sdim, h->tv_a0.p, 0));
         HIPCHK(h, hipDeviceSynchronize());
-        s_a0.release(); s_seg.release();
+        s_a0.release();
     }
     h->hbm_bytes = (int64_t)(h->times.n + h->obs.n + h->colbuf.n + h->tv_wdir.n + h->tv_rec.n + h->tv_a0.n + h->tv_harr.n) * 8 +
                    (int64_t)h->scored.n * 4;

@@ -483,6 +483,15 @@ class SDE:
         out = self.engine_.smooth(self._current_par_full(), cov=cov, resid=False)
         return {"mean": out["mean"], "cov": out["cov"]}
 
+    def sample_states(self, n_draws, seed=0):
+        """Joint posterior draws of the whole state path of a state-space model (CTCRW, OU_SSM, BM_SSM) at the current parameters
+        (ssde_smooth_draws): an array (n_draws, n, sdim), columns as in smooth_states, NaN on a track's first row.
+        Unlike the row-wise smooth_states, a draw carries the dependence between rows: speed, distance travelled, time inside a
+        region or multiple imputation of the true positions are summaries of these paths."""
+        if self.type_ not in ("CTCRW", "OU_SSM", "BM_SSM"):
+            raise NotImplementedError(f"sample_states: no latent state in the model {self.type_!r}")
+        return self.engine_.smooth_draws(self._current_par_full(), n_draws, seed=seed)
+
     def residuals(self):
         """Model residuals, iid N(0, 1) under the model (one column per response variable).
 
