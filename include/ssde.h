@@ -27,6 +27,8 @@
  *                         the reference's SDE$residuals() stops at (R/sde.R:1186-1228) and aest_all does not give
  *   ssde_smooth_draws  <- (new) joint posterior draws of the whole state path (backward sampling over the smoother's records):
  *                         what speed, distance travelled, time in a region or multiple imputation are computed from
+ *   ssde_predict       <- (new) the smoothed state at any time between or after the rows, from the smoother's records: what the
+ *                         reference gets by rebuilding the data with NA rows at the wanted times
  *   ssde_penalty       <- smoothing penalty     (nllk_ctcrw.hpp:254-280, nllk_sde.hpp:89-124)
  *   ssde_info          <- InfoADFunObject       (src/init.c:7)
  *   ssde_forget        <- (new) drops the memo of ssde_eval
@@ -352,6 +354,21 @@ int ssde_smooth(ssde_handle *h, const double *par, int32_t n_par_full, double *a
 #define SSDE_DRAWS_DEVICE_OUT 1u
 int ssde_smooth_draws(ssde_handle *h, const double *par, int32_t n_par_full, uint64_t seed, int64_t draw0, int32_t n_draws,
                       double *draws, uint32_t flags);
+
+/* The smoothed state at any time from the smoother's records at `par` (definitions: DESIGN.md §3.11).  Query k is (q_row[k], q_off[k]):
+ * a caller's row (0-based) and an offset >= 0 past its time stamp; the answer is the smoothed state of a NA row inserted there that
+ * carries row q_row[k]'s covariates.  An offset inside the row's interval interpolates; past a track's last row it forecasts.
+ *   a_pred [n_query x sdim]        column-major: E[state at the query time | the whole track]
+ *   P_pred [n_query x sdim x sdim] element (k, r, c) at k + n_query * (r + sdim * c): its covariance; may be NULL
+ * Queries may come in any order, repeat and share intervals.  NaN in every output of a query, with status SSDE_OK, where the row is a
+ * track's first row (or a one-row track), where the offset passes the next fix of the track by more than rounding, and where the row
+ * attempted an update and rejected it (det F <= 0); a NA row is served.  SSDE_ERR_ARG for NULL q_row / q_off / a_pred, n_query < 1, a
+ * row outside [0, n), an offset that is negative or not finite; SSDE_ERR_MODEL exactly where ssde_smooth_draws gives it.  Multi-device
+ * handles and column pairs are served (cross-pair covariance blocks are exactly 0).  Leaves the memo, the window state, the TV
+ * records and every later ssde_eval / ssde_smooth / ssde_smooth_draws result as they were; its buffers are its own, chunked by whole
+ * wavefront groups under SSDE_OPT_SMOOTH_BUDGET_MB, and the result does not depend on the chunking. */
+int ssde_predict(ssde_handle *h, const double *par, int32_t n_par_full, const int64_t *q_row, const double *q_off, int64_t n_query,
+                 double *a_pred, double *P_pred);
 
 /* Multiply the warm-up overlap of the time windows by `factor` for all later evaluations
  * (factor <= 0: force one sequential window). */

@@ -491,6 +491,8 @@ def load_library():
     lib.ssde_smooth.restype = C.c_int
     lib.ssde_smooth_draws.argtypes = [C.c_void_p, _dp, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.c_void_p, C.c_uint32]
     lib.ssde_smooth_draws.restype = C.c_int
+    lib.ssde_predict.argtypes = [C.c_void_p, _dp, C.c_int32, C.POINTER(C.c_int64), _dp, C.c_int64, _dp, _dp]
+    lib.ssde_predict.restype = C.c_int
     lib.ssde_widen_windows.argtypes = [C.c_void_p, C.c_int32]
     lib.ssde_widen_windows.restype = C.c_int
     lib.ssde_relax_windows.argtypes = [C.c_void_p]
@@ -563,7 +565,7 @@ WINDOW_TOL = 1e-11  # largest tolerated relative hand-over disagreement between 
 
 EXPORTED_SYMBOLS = ("ssde_create", "ssde_eval", "ssde_eval_device", "ssde_penalty", "ssde_report", "ssde_widen_windows", "ssde_relax_windows",
                     "ssde_info", "ssde_destroy", "ssde_last_error", "ssde_abi_version", "ssde_comm_unique_id", "ssde_comm_init_rank", "ssde_forget", "ssde_laplace_eval", "ssde_last_kernel_ms", "ssde_kernel_ms_history",
-                    "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth", "ssde_smooth_draws",
+                    "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth", "ssde_smooth_draws", "ssde_predict",
                     "ssde_lagstats_host_m", "ssde_lagstats_read_m", "ssde_lagforms_host_m", "ssde_reduce_host", "ssde_last_finish_form")
 
 
@@ -928,6 +930,25 @@ class Engine:
         self._check(self.lib.ssde_smooth_draws(self._h, par.ctypes.data_as(_dp), self.n_par_full, int(seed), int(draw0), int(n_draws),
                                                buf.ctypes.data_as(C.c_void_p), 0))
         return buf.transpose(0, 2, 1)
+
+    def predict(self, par, rows, offsets, cov: bool = True) -> dict:
+        """The smoothed state at any time at `par` (ssde_predict).  Query k is (rows[k], offsets[k]): a row of the
+        data (0-based) and an offset >= 0 past its time stamp -- inside the row's interval an interpolation, past a track's last row
+        a forecast.  {"mean": (n_query x sdim), "cov": (n_query x sdim x sdim) or None}; NaN for a query on a track's first row, past
+        the track's next fix, or on a row that rejected its update."""
+        par = np.ascontiguousarray(par, dtype=np.float64)
+        if par.shape != (self.n_par_full,):
+            raise ValueError(f"par must have length {self.n_par_full}")
+        rows = np.ascontiguousarray(rows, dtype=np.int64).ravel()
+        offsets = np.ascontiguousarray(offsets, dtype=np.float64).ravel()
+        if rows.shape != offsets.shape:
+            raise ValueError("rows and offsets must have the same length")
+        m, sd = len(rows), self.problem.sdim
+        mean = np.zeros((m, sd), order="F")
+        P = np.zeros((m, sd, sd), order="F") if cov else None
+        self._check(self.lib.ssde_predict(self._h, par.ctypes.data_as(_dp), self.n_par_full, rows.ctypes.data_as(C.POINTER(C.c_int64)),
+                                          offsets.ctypes.data_as(_dp), m, mean.ctypes.data_as(_dp), P.ctypes.data_as(_dp) if cov else None))
+        return {"mean": mean, "cov": P}
 
     def close(self):
         if self._h:

@@ -9,6 +9,7 @@
 // the GPU); the throughput path for the headline configurations is k_iso.hip.
 #include "ssde_dense.hpp"
 #include "ssde_device.hpp"
+#include "ssde_predict.hpp"
 #include "ssde_smooth.hpp"
 
 namespace ssde {
@@ -92,7 +93,14 @@ __global__ __launch_bounds__(WAVE) void dense_kernel(const DenseArgs A) {
         if constexpr (MODE == 2) {
             // records of the group at srec_off[g] (chunk-relative), double k of step s at (s * R + k) * 64 + lane
             double* rp = A.srec + (A.srec_off[g] - A.srec_base) + (int64_t)s0 * SmoothRec<MODEL, D>::R * WAVE + lane;
-            smooth_record_row<MODEL, D>(S, par, H, dt, y, is_na(y[0], A.any_nan), [&](int k) -> double& { return rp[(int64_t)k * WAVE]; });
+            const bool upd = smooth_record_row<MODEL, D>(S, par, H, dt, y, is_na(y[0], A.any_nan), [&](int k) -> double& { return rp[(int64_t)k * WAVE]; });
+            if constexpr (D <= 2) {
+                if (A.sside) {                                                   // ssde_predict: the row's linear predictors and interval
+                    constexpr int SW = PredictPk<MODEL, D>::SW;
+                    double* sp = A.sside + (A.srec_off[g] - A.srec_base) / SmoothRec<MODEL, D>::R * SW + (int64_t)s0 * SW * WAVE + lane;
+                    predict_side_row<MODEL, D>(par, dt, is_na(y[0], A.any_nan), upd, [&](int k) -> double& { return sp[(int64_t)k * WAVE]; });
+                }
+            }
         }
         dense_step<MODEL, D, N>(S, par, H, dt, y, is_na(y[0], A.any_nan));
         if (REPORT) {

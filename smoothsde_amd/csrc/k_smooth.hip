@@ -7,6 +7,7 @@
 // Outputs go straight to the long format: lane l writes row row0_l + 1 + s, so a wave store touches 64 rows, but successive steps of
 // a lane fill the same cache lines and the outputs are a third of the bytes moved (DESIGN.md §3.9 has the measurement).
 #include "ssde_device.hpp"
+#include "ssde_predict.hpp"
 #include "ssde_smooth.hpp"
 
 namespace ssde {
@@ -97,7 +98,12 @@ __global__ __launch_bounds__(WAVE) void smooth_tv_record_kernel(const TvArgs T, 
         }
         const bool na = is_na(y[0], T.any_nan);
         double* rp = base + (int64_t)s * RC::R * WAVE;
-        smooth_record_row<MODEL, D>(S, par, H, dt, y, na, [&](int k) -> double& { return rp[(int64_t)k * WAVE]; });
+        const bool upd = smooth_record_row<MODEL, D>(S, par, H, dt, y, na, [&](int k) -> double& { return rp[(int64_t)k * WAVE]; });
+        if (A.side) {                                                            // ssde_predict: the row's linear predictors and interval
+            constexpr int SW = PredictPk<MODEL, D>::SW;
+            double* sp = A.side + (A.rec_off[g] - A.rec_base) / RC::R * SW + (int64_t)s * SW * WAVE + lane;
+            predict_side_row<MODEL, D>(par, dt, na, upd, [&](int k) -> double& { return sp[(int64_t)k * WAVE]; });
+        }
         dense_step<MODEL, D, 0>(S, par, H, dt, y, na);
     }
 }

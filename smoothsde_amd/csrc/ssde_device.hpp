@@ -520,6 +520,7 @@ struct DenseArgs {
     const int64_t* srec_off;     // [n_groups] in doubles, over all groups
     int64_t srec_base;           // srec_off[g0]
     int g0, srec_groups;
+    double* sside;               // ssde_predict: the rows' side rows (SmoothArgs.side), or NULL
 };
 hipError_t launch_dense(const DenseArgs& a, bool want_grad, hipStream_t s);
 
@@ -599,6 +600,10 @@ struct SmoothArgs {
     double* Vm;                  // [n_out x sdim x sdim] or NULL
     double* em;                  // [n_out x d] or NULL
     int64_t n_out;
+    // ssde_predict (ssde_predict.hpp): the record pass also writes every state row's linear predictors and interval, Q + 1 doubles in the
+    // records' layout with a row width of its own: double k of step s at side + (rec_off[g] - rec_base) / R * (Q + 1) + (s * (Q + 1) + k) * 64
+    // + lane.  NULL (ssde_smooth, ssde_smooth_draws): nothing is written.
+    double* side;
 };
 int smooth_rec_doubles(int model, int d);
 hipError_t launch_smooth_back(const SmoothArgs& a, hipStream_t s);
@@ -619,6 +624,28 @@ struct DrawArgs {
     double* out;
 };
 hipError_t launch_smooth_draws(const DrawArgs& a, hipStream_t s);
+// ---- the state at any time from the records (k_predict.hip, ssde_predict.hpp) ----
+// The records, side rows, groups and lanes of a SmoothArgs `s`.  Lane l wants the steps want_step[want_off[l] .. want_off[l + 1]) (ascending);
+// entry i of that list is slot i, and the walk stores its packet's double k at pk + k * pk_stride + (i - slot0).  The query kernel
+// runs the queries order[q0 .. q1) (sorted by slot): query order[i] reads slot q_slot[i], steps q_off[i] past it and writes row
+// order[i] of a_pred [n_query x sdim] / P_pred [n_query x sdim x sdim] (or NULL).
+struct PredictArgs {
+    SmoothArgs s;
+    const int64_t* want_off;     // [n_lanes + 1]
+    const int32_t* want_step;    // [n_slots]
+    double* pk;
+    int64_t slot0, pk_stride;
+    const int64_t* order;        // [n_valid] the caller's query index
+    const int64_t* q_slot;       // [n_valid]
+    const double* q_off;         // [n_valid]
+    int64_t q0, q1, n_query;
+    double* a_pred;
+    double* P_pred;
+};
+int predict_packet_doubles(int model, int d);
+int predict_side_doubles(int model, int d);
+hipError_t launch_predict_walk(const PredictArgs& a, hipStream_t s);
+hipError_t launch_predict_query(const PredictArgs& a, hipStream_t s);
 hipError_t launch_tv_a0(const TvArgs& a, const double* a0_src, const int64_t* trk_seg, int64_t n_seg, int sdim,
                         double* a0_dst, hipStream_t s);
 hipError_t launch_tv_prepare(const TvArgs& a, hipStream_t s);

@@ -1,17 +1,21 @@
 // ssde_engine_smooth.hip -- ssde_smooth: the fixed-interval smoother of the Kalman families, and
-// ssde_smooth_draws: joint posterior draws of the state path from the same records.
+// ssde_smooth_draws: joint posterior draws of the state path from the same records, and ssde_predict: the smoothed
+// state between and after the rows from them.
 //
 // A forward pass in record mode (dense_kernel MODE 2 on the tiled routes, smooth_tv_record_kernel on PATH_TV) writes every state
 // row's record, smooth_back_kernel walks them back and writes the smoothed mean, covariance and whitened innovation in the long
 // format.  Groups of 64 tracks are independent, so the records are produced and consumed chunk by chunk (SSDE_OPT_SMOOTH_BUDGET_MB)
 // and the result does not depend on the chunking.  Every buffer is the call's own: the handle's record / stats buffers, memo and
 // window state are not touched.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <functional>
 #include <limits>
+#include <numeric>
 
 #include "ssde_engine.hpp"
+#include "ssde_predict.hpp"
 
 using namespace ssde_engine;
 
@@ -42,7 +46,8 @@ struct RecordRun {
     bool tv = false;
     int R = 0;
     int64_t nt = 0, n_lanes = 0, budget = 0;
-    DevBuf<double> rec, pbuf;
+    int SW = 0;                        // > 0 (set before setup): the record pass also writes side rows of SW doubles (ssde_predict)
+    DevBuf<double> rec, pbuf, side;
     DevBuf<int64_t> offb;
     DevBuf<SlotTable> stb;
     std::vector<int64_t> goff;
@@ -51,7 +56,7 @@ struct RecordRun {
     TvArgs ta;
     DenseArgs da;
     SlotTable stab;
-    ~RecordRun() { rec.release(); pbuf.release(); offb.release(); stb.release(); }
+    ~RecordRun() { rec.release(); pbuf.release(); side.release(); offb.release(); stb.release(); }
     size_t n_chunks() const { return cut.size() - 1; }
 
     int setup(ssde_handle* h_, const double* par, const char* who) {
@@ -89,14 +94,16 @@ struct RecordRun {
             HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
             budget = (int64_t)(free_b / 4 / 8);
         }
+        if (SW > 0) budget = budget / (R + SW) * R;                // the side rows share the budget
         cut = chunk_groups(goff, budget);
         int64_t biggest = 0;
         for (size_t c = 0; c + 1 < cut.size(); c++) biggest = std::max(biggest, goff[cut[c + 1]] - goff[cut[c]]);
         HIPCHK(h, rec.alloc((size_t)std::max<int64_t>(biggest, 1)));
+        if (SW > 0) HIPCHK(h, side.alloc((size_t)std::max<int64_t>(biggest / R * SW, 1)));
 
         memset(&s, 0, sizeof(s));
         s.model = h->model; s.d = d; s.rec = rec.p; s.rec_off = offb.p;
-        s.n_out = nt; s.n_lanes = n_lanes;
+        s.n_out = nt; s.n_lanes = n_lanes; s.side = side.p;
         if (tv) {
             tv_base_args(h, ta);
             ta.par = pbuf.p;
@@ -120,7 +127,7 @@ struct RecordRun {
             for (int i = 0; i < 256; i++) da.p0[i] = h->p0_full[i];
             da.n_dirblocks = 1; da.pp = h->pp_drift;
             da.lane_row0 = h->lane_row0.p; da.n = nt; da.last_dt = h->last_dt;
-            da.srec = rec.p; da.srec_off = offb.p;
+            da.srec = rec.p; da.srec_off = offb.p; da.sside = side.p;
             s.lane_row0 = h->lane_row0.p; s.lane_ns = h->lane_nsteps.p;
         }
         return SSDE_OK;
@@ -242,6 +249,164 @@ int draws_single(ssde_handle* h, const double* par, uint64_t seed, int64_t draw0
     return SSDE_OK;
 }
 
+// ---- ssde_predict -------------------------------------------------------------------------------------------------------------
+// One engine's queries.  Planning on the host: every query goes to the state row (lane, step) that starts its interval in the
+// handle's resident layout, plus a residual offset; the wanted steps become a list per lane (slots) and the queries are ordered by
+// slot.  Then, chunk by chunk: the record pass with side rows, the walk that fills the chunk's packets, the query kernel.
+int predict_single(ssde_handle* h, const double* par, const int64_t* q_row, const double* q_off, int64_t nq, double* a_pred,
+                   double* P_pred) {
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(0));
+    const int sd = h->sdim;
+    if (h->d > 2) {
+        h->err = "ssde_predict: a response of three or more columns that runs as ONE coupled filter is not served (uncoupled wide responses run as column pairs and are)";
+        return SSDE_ERR_MODEL;
+    }
+    RecordRun run;
+    run.SW = predict_side_doubles(h->model, h->d);
+    const int PKD = predict_packet_doubles(h->model, h->d);
+    if (run.SW <= 0 || PKD <= 0) { h->err = "ssde_predict: no kernels for this model and width"; return SSDE_ERR_MODEL; }
+    { int st = run.setup(h, par, "ssde_predict"); if (st) return st; }
+    const int64_t nl = run.n_lanes, n = h->n;
+    const bool lattice = run.nt != n;
+
+    // the lanes' tracks in the resident layout: first row and state rows, sorted by first row
+    std::vector<int64_t> row0((size_t)nl);
+    std::vector<int32_t> lns((size_t)nl);
+    if (nl) {
+        HIPCHK(h, hipMemcpy(row0.data(), run.s.lane_row0, (size_t)nl * 8, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(lns.data(), run.s.lane_ns, (size_t)nl * 4, hipMemcpyDeviceToHost));
+    }
+    std::vector<int64_t> by_row;
+    for (int64_t l = 0; l < nl; l++) if (lns[l] > 0) by_row.push_back(l);
+    std::sort(by_row.begin(), by_row.end(), [&](int64_t a, int64_t b) { return row0[a] < row0[b]; });
+    std::vector<int64_t> start(by_row.size());
+    for (size_t k = 0; k < by_row.size(); k++) start[k] = row0[by_row[k]];
+    std::vector<int64_t> prow;
+    if (lattice) {
+        prow.resize((size_t)n);
+        HIPCHK(h, hipMemcpy(prow.data(), h->pad_row.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    }
+
+    // queries -> (lane, step, residual); key = lane * 2^31 + step orders them by slot
+    std::vector<int64_t> key((size_t)nq, -1);
+    std::vector<double> res((size_t)nq, 0.0);
+    for (int64_t k = 0; k < nq; k++) {
+        const int64_t p = lattice ? prow[q_row[k]] : q_row[k];
+        const size_t t = std::upper_bound(start.begin(), start.end(), p) - start.begin();
+        if (t == 0) continue;
+        const int64_t l = by_row[t - 1], r0 = row0[l], ns = lns[l];
+        if (p > r0 + ns) continue;                                  // (a one-row track: no lane holds it)
+        int64_t st = p - r0 - 1;
+        if (st < 0) continue;                                       // a track's first row carries no state
+        double off = q_off[k];
+        if (lattice && st < ns - 1) {
+            // a caller's interval may span several lattice steps: the whole steps inside `off` move the row, the rest is the residual
+            const double step = h->pad_step;
+            int64_t w = (int64_t)std::floor(off / step + PREDICT_DT_RTOL);
+            double rest = off - (double)w * step;
+            if (rest < 0.0) rest = 0.0;
+            const int64_t pn = prow[q_row[k] + 1];                  // the caller's next row (same track: row j is not its last)
+            if (p + w > pn || (p + w == pn && rest > PREDICT_DT_RTOL * step)) continue;   // past the next fix: NaN
+            if (p + w == pn) rest = 0.0;
+            st += w; off = rest;
+        }
+        key[k] = (l << 31) | st;
+        res[k] = off;
+    }
+    std::vector<int64_t> order;
+    for (int64_t k = 0; k < nq; k++) if (key[k] >= 0) order.push_back(k);
+    std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return key[a] < key[b]; });
+    const int64_t nv = (int64_t)order.size();
+    std::vector<int64_t> want_off((size_t)nl + 1, 0), q_slot((size_t)nv);
+    std::vector<int32_t> want_step;
+    std::vector<double> off_sorted((size_t)nv);
+    for (int64_t i = 0; i < nv; i++) {
+        const int64_t kk = key[order[i]];
+        if (i == 0 || kk != key[order[i - 1]]) {
+            want_step.push_back((int32_t)(kk & 0x7fffffff));
+            want_off[(size_t)(kk >> 31) + 1]++;
+        }
+        q_slot[i] = (int64_t)want_step.size() - 1;
+        off_sorted[i] = res[order[i]];
+    }
+    for (int64_t l = 0; l < nl; l++) want_off[l + 1] += want_off[l];
+
+    // the outputs, NaN (all bits set) where no query writes
+    DevBuf<double> am, Vm, pk, offd;
+    DevBuf<int64_t> wo, ord, qs;
+    DevBuf<int32_t> ws;
+    struct Guard { DevBuf<int32_t>* w; ~Guard() { w->release(); } } g32{&ws};
+    SmoothBufs guard{{&am, &Vm, &pk, &offd}, {&wo, &ord, &qs}};
+    HIPCHK(h, am.alloc((size_t)nq * sd)); HIPCHK(h, hipMemset(am.p, 0xff, (size_t)nq * sd * 8));
+    if (P_pred) { HIPCHK(h, Vm.alloc((size_t)nq * sd * sd)); HIPCHK(h, hipMemset(Vm.p, 0xff, (size_t)nq * sd * sd * 8)); }
+    if (nv > 0) {
+        HIPCHK(h, wo.upload(want_off)); HIPCHK(h, ws.upload(want_step));
+        HIPCHK(h, ord.upload(order)); HIPCHK(h, qs.upload(q_slot)); HIPCHK(h, offd.upload(off_sorted));
+        // the chunks' slot ranges (a chunk's lanes hold consecutive slots) and the queries of each
+        int64_t most = 0;
+        for (size_t c = 0; c < run.n_chunks(); c++) {
+            const int64_t l0 = std::min<int64_t>((int64_t)run.cut[c] * WAVE, nl), l1 = std::min<int64_t>((int64_t)run.cut[c + 1] * WAVE, nl);
+            most = std::max(most, want_off[l1] - want_off[l0]);
+        }
+        HIPCHK(h, pk.alloc((size_t)most * PKD));
+        PredictArgs a;
+        memset(&a, 0, sizeof(a));
+        a.want_off = wo.p; a.want_step = ws.p; a.pk = pk.p; a.order = ord.p; a.q_slot = qs.p; a.q_off = offd.p;
+        a.n_query = nq; a.a_pred = am.p; a.P_pred = Vm.p;
+        for (size_t c = 0; c < run.n_chunks(); c++) {
+            const int64_t l0 = std::min<int64_t>((int64_t)run.cut[c] * WAVE, nl), l1 = std::min<int64_t>((int64_t)run.cut[c + 1] * WAVE, nl);
+            const int64_t s0 = want_off[l0], s1 = want_off[l1];
+            if (s1 == s0) continue;                                 // no query on this chunk's tracks
+            int st = run.produce(c);
+            if (st) return st;
+            a.s = run.s;
+            a.slot0 = s0; a.pk_stride = s1 - s0;
+            a.q0 = std::lower_bound(q_slot.begin(), q_slot.end(), s0) - q_slot.begin();
+            a.q1 = std::lower_bound(q_slot.begin(), q_slot.end(), s1) - q_slot.begin();
+            HIPCHK(h, launch_predict_walk(a, 0));
+            HIPCHK(h, launch_predict_query(a, 0));
+        }
+    }
+    HIPCHK(h, hipMemcpy(a_pred, am.p, (size_t)nq * sd * 8, hipMemcpyDeviceToHost));
+    if (P_pred) HIPCHK(h, hipMemcpy(P_pred, Vm.p, (size_t)nq * sd * sd * 8, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipStreamSynchronize(0));
+    return SSDE_OK;
+}
+
+// the shards' and column pairs' queries: each engine gets the queries on its rows, its columns land in the parent's layout
+int predict_sharded(ssde_handle* parent, const double* par, const int64_t* q_row, const double* q_off, int64_t nq, double* a_pred,
+                    double* P_pred) {
+    const int SD = parent->sdim;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    std::fill(a_pred, a_pred + (size_t)nq * SD, nan);
+    if (P_pred) std::fill(P_pred, P_pred + (size_t)nq * SD * SD, 0.0);           // cross-pair blocks: zero
+    for (size_t k = 0; k < parent->shards.size(); k++) {
+        ssde_handle* sh = parent->shards[k];
+        const int64_t lo = parent->shard_row0[k], m = parent->shard_nrows[k];
+        const int sd = sh->sdim, c0 = parent->shard_col0[k];
+        std::vector<int64_t> idx, rows;
+        std::vector<double> offs;
+        for (int64_t i = 0; i < nq; i++)
+            if (q_row[i] >= lo && q_row[i] < lo + m) { idx.push_back(i); rows.push_back(q_row[i] - lo); offs.push_back(q_off[i]); }
+        const int64_t mq = (int64_t)idx.size();
+        if (mq == 0) continue;
+        std::vector<double> ta((size_t)mq * sd), tP(P_pred ? (size_t)mq * sd * sd : 0);
+        int st = ssde_predict(sh, par, parent->L.n_full, rows.data(), offs.data(), mq, ta.data(), P_pred ? tP.data() : nullptr);
+        if (st) { parent->err = sh->err; return st; }
+        for (int64_t i = 0; i < mq; i++) {
+            for (int c = 0; c < sd; c++) a_pred[(size_t)(c0 + c) * nq + idx[i]] = ta[(size_t)c * mq + i];
+            if (!P_pred) continue;
+            for (int c = 0; c < sd; c++)
+                for (int r = 0; r < sd; r++)
+                    P_pred[(size_t)nq * ((c0 + r) + (size_t)SD * (c0 + c)) + idx[i]] = tP[(size_t)mq * (r + (size_t)sd * c) + i];
+            if (std::isnan(tP[i]))                                  // a query without a state has no covariance at all
+                for (int q = 0; q < SD * SD; q++) P_pred[(size_t)nq * q + idx[i]] = nan;
+        }
+    }
+    return SSDE_OK;
+}
+
 }  // namespace
 
 namespace ssde_engine {
@@ -324,6 +489,20 @@ int ssde_smooth_draws(ssde_handle* h, const double* par, int32_t n_par_full, uin
         return draws_sharded(h, par, seed, draw0, n_draws, draws, dev_out);
     }
     return draws_single(h, par, seed, draw0, n_draws, draws, dev_out, (int64_t)h->n * h->sdim, 0, 0);
+}
+
+int ssde_predict(ssde_handle* h, const double* par, int32_t n_par_full, const int64_t* q_row, const double* q_off, int64_t n_query,
+                 double* a_pred, double* P_pred) {
+    if (!h || !par || !q_row || !q_off || !a_pred) { if (h) h->err = "ssde_predict: no parameter vector, no queries, or no output"; return SSDE_ERR_ARG; }
+    if (n_par_full != h->L.n_full) { h->err = "parameter vector has the wrong length"; return SSDE_ERR_ARG; }
+    if (n_query < 1) { h->err = "ssde_predict: n_query >= 1 is required"; return SSDE_ERR_ARG; }
+    for (int64_t k = 0; k < n_query; k++) {
+        if (q_row[k] < 0 || q_row[k] >= h->n) { h->err = "ssde_predict: a query row outside [0, n)"; return SSDE_ERR_ARG; }
+        if (!std::isfinite(q_off[k]) || q_off[k] < 0.0) { h->err = "ssde_predict: a query offset that is negative or not finite"; return SSDE_ERR_ARG; }
+    }
+    if (!is_kalman(h->model)) { h->err = "the smoother serves the Kalman families only (the direct families have no state; ESEAL_SSM no REPORT)"; return SSDE_ERR_MODEL; }
+    if (!h->shards.empty()) return predict_sharded(h, par, q_row, q_off, n_query, a_pred, P_pred);
+    return predict_single(h, par, q_row, q_off, n_query, a_pred, P_pred);
 }
 
 int ssde_smooth(ssde_handle* h, const double* par, int32_t n_par_full, double* a_smooth, double* P_smooth, double* resid) {

@@ -22,9 +22,10 @@ struct SmoothRec {
     SSDE_HD static constexpr int up(int r, int c) { return r <= c ? c * (c + 1) / 2 + r : r * (r + 1) / 2 + c; }
 };
 
-// The row's record, from the lane's state before dense_step.  par / H as dense_step takes them (values only).
+// The row's record, from the lane's state before dense_step.  par / H as dense_step takes them (values only).  Returns whether the
+// row takes an update (false: a NA row, or det F <= 0 -- what ssde_predict's side row tells apart).
 template <int MODEL, int D, class W>
-SSDE_HD void smooth_record_row(const DenseLane<MODEL, D, 0>& L, const DualN<0>* par, const DualN<0> (&H)[D][D], double dt,
+SSDE_HD bool smooth_record_row(const DenseLane<MODEL, D, 0>& L, const DualN<0>* par, const DualN<0> (&H)[D][D], double dt,
                                const double* y, bool na, W&& rec) {
     typedef DenseDims<MODEL, D> DM;
     typedef SmoothRec<MODEL, D> RC;
@@ -60,7 +61,7 @@ SSDE_HD void smooth_record_row(const DenseLane<MODEL, D, 0>& L, const DualN<0>* 
         SSDE_DLOOP for (int k = 0; k < RC::NF; k++) rec(RC::FI + k) = 0.0;
         SSDE_DLOOP for (int k = 0; k < SD * D; k++) rec(RC::K + k) = 0.0;
         SSDE_DLOOP for (int i = 0; i < D; i++) rec(RC::E + i) = __builtin_nan("");
-        return;
+        return false;
     }
     T_ Fi[D][D];
     if constexpr (D == 1) {
@@ -106,6 +107,7 @@ SSDE_HD void smooth_record_row(const DenseLane<MODEL, D, 0>& L, const DualN<0>* 
         v[i] = s / C[i][i];                       // (in place: v[k < i] already hold the whitened values)
         rec(RC::E + i) = v[i];
     }
+    return true;
 }
 
 // Backward step over row j's record: r <- Z'F^-1 v + L'r, N <- Z'F^-1 Z + L'N L (L = T - K Z), then the smoothed mean / covariance

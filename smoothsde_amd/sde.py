@@ -483,6 +483,45 @@ class SDE:
         out = self.engine_.smooth(self._current_par_full(), cov=cov, resid=False)
         return {"mean": out["mean"], "cov": out["cov"]}
 
+    def predict_states(self, ID, time, cov=True):
+        """Smoothed states of a state-space model (CTCRW, OU_SSM, BM_SSM) at any times, at the current parameters (ssde_predict,
+        DESIGN.md §3.11).  `ID` and `time` are arrays of equal length: query k asks for the state of track ID[k] at time[k].  Between two
+        rows of the track the state is interpolated (with the covariates of the row before), after its last row it is a forecast.
+        Returns {"mean": n_query x sdim, "cov": n_query x sdim x sdim or None}, columns as in smooth_states; NaN for an unknown ID
+        and for a time before the track's second time stamp (the first row carries no state)."""
+        if self.type_ not in ("CTCRW", "OU_SSM", "BM_SSM"):
+            raise NotImplementedError(f"predict_states: no latent state in the model {self.type_!r}")
+        if self.engine_ is None:
+            raise RuntimeError("call setup() or fit() first")
+        ID, time = np.asarray(ID).ravel(), np.asarray(time, dtype=np.float64).ravel()
+        if ID.shape != time.shape:
+            raise ValueError("ID and time must have the same length")
+        ids = np.asarray(self.data_["ID"])
+        t = np.asarray(self.data_["time"], dtype=np.float64)
+        n, m, sd = len(ids), len(ID), self.problem_.sdim
+        start = np.r_[0, np.nonzero(ids[1:] != ids[:-1])[0] + 1]
+        end = np.r_[start[1:], n]
+        seg_of = {}
+        for k, s0 in enumerate(start):
+            seg_of.setdefault(ids[s0], k)
+        rows = np.full(m, -1, dtype=np.int64)
+        for k in range(m):
+            seg = seg_of.get(ID[k])
+            if seg is None or not np.isfinite(time[k]):
+                continue
+            j = int(np.searchsorted(t[start[seg]:end[seg]], time[k], side="right")) - 1      # the last row with time <= the query's
+            if j >= 0:
+                rows[k] = start[seg] + j
+        ok = rows >= 0
+        mean = np.full((m, sd), np.nan)
+        P = np.full((m, sd, sd), np.nan) if cov else None
+        if ok.any():
+            out = self.engine_.predict(self._current_par_full(), rows[ok], time[ok] - t[rows[ok]], cov=cov)
+            mean[ok] = out["mean"]
+            if cov:
+                P[ok] = out["cov"]
+        return {"mean": mean, "cov": P}
+
     def sample_states(self, n_draws, seed=0):
         """Joint posterior draws of the whole state path of a state-space model (CTCRW, OU_SSM, BM_SSM) at the current parameters
         (ssde_smooth_draws): an array (n_draws, n, sdim), columns as in smooth_states, NaN on a track's first row.
