@@ -567,6 +567,11 @@ int ssde_reduce_host(const double *sums, const double *group_chk, int32_t n_grou
 /* What finished the handle's last evaluation: 0 a finalize launch after the main one, 1 the main launch itself
    (SSDE_FUSED_FINALIZE=1), 2 the host.  A multi-device parent reports its first shard; -1 for NULL. */
 int ssde_last_finish_form(const ssde_handle *h);
+/* How the main launch of the handle's last evaluation got its gain table: 0 through a pinned slot and a copy on the stream, 1 by value
+   in the launch's own argument block (the head of the lag-statistics path with one workgroup per track group, a table short enough
+   to fit).  ssde_last_gain_rows: the rows of that table.  A multi-device parent reports its first shard; -1 for NULL. */
+int ssde_last_gain_feed(const ssde_handle *h);
+int ssde_last_gain_rows(const ssde_handle *h);
 
 #ifdef __cplusplus
 }

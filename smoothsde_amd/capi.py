@@ -524,6 +524,9 @@ def load_library():
     lib.ssde_reduce_host.restype = C.c_int
     lib.ssde_last_finish_form.argtypes = [C.c_void_p]
     lib.ssde_last_finish_form.restype = C.c_int
+    for name in ("ssde_last_gain_feed", "ssde_last_gain_rows"):
+        getattr(lib, name).argtypes = [C.c_void_p]
+        getattr(lib, name).restype = C.c_int
     lib.ssde_abi_version.argtypes = []
     lib.ssde_abi_version.restype = C.c_int
     lib.ssde_laplace_eval.argtypes = [C.c_void_p, _dp, C.c_int32, C.c_int32, _dp, _dp, _dp, C.POINTER(SsdeLaplaceOpts)]
@@ -566,7 +569,7 @@ WINDOW_TOL = 1e-11  # largest tolerated relative hand-over disagreement between 
 EXPORTED_SYMBOLS = ("ssde_create", "ssde_eval", "ssde_eval_device", "ssde_penalty", "ssde_report", "ssde_widen_windows", "ssde_relax_windows",
                     "ssde_info", "ssde_destroy", "ssde_last_error", "ssde_abi_version", "ssde_comm_unique_id", "ssde_comm_init_rank", "ssde_forget", "ssde_laplace_eval", "ssde_last_kernel_ms", "ssde_kernel_ms_history",
                     "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth", "ssde_smooth_draws", "ssde_predict",
-                    "ssde_lagstats_host_m", "ssde_lagstats_read_m", "ssde_lagforms_host_m", "ssde_reduce_host", "ssde_last_finish_form")
+                    "ssde_lagstats_host_m", "ssde_lagstats_read_m", "ssde_lagforms_host_m", "ssde_reduce_host", "ssde_last_finish_form", "ssde_last_gain_feed", "ssde_last_gain_rows")
 
 
 def reduce_host(sums, group_chk, n_out, map_, lag_acc=None, lag_chk=0.0, add=None, add_slot=None):
@@ -862,6 +865,14 @@ class Engine:
     def last_finish_form(self) -> int:
         """What finished the last evaluation: 0 a finalize launch, 1 the main launch itself, 2 the host."""
         return int(self.lib.ssde_last_finish_form(self._h))
+
+    def last_gain_feed(self) -> int:
+        """How the last evaluation's main launch got its gain table: 0 a copy on the stream, 1 by value in its argument block."""
+        return int(self.lib.ssde_last_gain_feed(self._h))
+
+    def last_gain_rows(self) -> int:
+        """Rows of the last evaluation's gain table (the covariance transient, in rows)."""
+        return int(self.lib.ssde_last_gain_rows(self._h))
 
     def forget(self):
         """Drop the memoised last result: the next eval runs on the device even at the same par."""

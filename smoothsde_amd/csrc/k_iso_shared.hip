@@ -6,9 +6,9 @@
 
 namespace ssde {
 
-hipError_t launch_iso_shared_ctcrw(int d, const IsoArgs& a, const ReduceArgs& r, dim3 grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, bool deep);
-hipError_t launch_iso_shared_ou(int d, const IsoArgs& a, const ReduceArgs& r, dim3 grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, bool deep);
-hipError_t launch_iso_shared_bm(int d, const IsoArgs& a, const ReduceArgs& r, dim3 grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, bool deep);
+hipError_t launch_iso_shared_ctcrw(int d, const IsoArgs& a, const ReduceArgs& r, dim3 grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, bool deep, const HeadGain* hg);
+hipError_t launch_iso_shared_ou(int d, const IsoArgs& a, const ReduceArgs& r, dim3 grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, bool deep, const HeadGain* hg);
+hipError_t launch_iso_shared_bm(int d, const IsoArgs& a, const ReduceArgs& r, dim3 grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, bool deep, const HeadGain* hg);
 
 // host side: the stationary constants (layout in ssde_device.hpp)
 void fill_stat_consts(int model, int d, IsoArgs& a) {
@@ -51,7 +51,7 @@ void fill_stat_consts(int model, int d, IsoArgs& a) {
 
 // the shared path runs all directions in one part (n_parts == 1, mask = part_mask[0]).  r: the reduction's arguments, read by the kernel
 // only when a.fused (the finalising work inside this launch); a.fuse_items is set here
-hipError_t launch_iso_shared(int model, int d, const IsoArgs& a0, const ReduceArgs& r, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+hipError_t launch_iso_shared(int model, int d, const IsoArgs& a0, const ReduceArgs& r, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, const HeadGain* hg) {
     if (a0.n_parts != 1) return hipErrorInvalidValue;
     IsoArgs a = a0;
     const int g8 = (a.tv.n_groups + 7) / 8;
@@ -61,11 +61,13 @@ hipError_t launch_iso_shared(int model, int d, const IsoArgs& a0, const ReduceAr
     // one workgroup per group (iso_shared_wg_kernel): its windows are the waves of a workgroup, the transient window's wave its own;
     // the grid above is then one workgroup per group of the padded batch
     if (a.wg_form && !(a.n_chunks == WG_WAVES && a.t0 > 0 && a.t0_delta == 0 && !a.fused && a.group_mode != 1)) return hipErrorInvalidValue;
+    if (hg && hg->rows > 0 && !(a.wg_form && hg->rows <= HEAD_GAIN_ROWS)) return hipErrorInvalidValue;      // (by value: that entry only)
+    if (!a.wg_form) hg = nullptr;
     a.fuse_items = a.tv.n_groups * n_grid_chunks;              // (fused launches run every group: the engine sees to it)
     const bool deep = a.deep_prefetch != 0;
-    if (model == M_CTCRW) return launch_iso_shared_ctcrw(d, a, r, grid, s, ev0, ev1, deep);
-    if (model == M_OU_SSM) return launch_iso_shared_ou(d, a, r, grid, s, ev0, ev1, deep);
-    if (model == M_BM_SSM) return launch_iso_shared_bm(d, a, r, grid, s, ev0, ev1, deep);
+    if (model == M_CTCRW) return launch_iso_shared_ctcrw(d, a, r, grid, s, ev0, ev1, deep, hg);
+    if (model == M_OU_SSM) return launch_iso_shared_ou(d, a, r, grid, s, ev0, ev1, deep, hg);
+    if (model == M_BM_SSM) return launch_iso_shared_bm(d, a, r, grid, s, ev0, ev1, deep, hg);
     return hipErrorInvalidValue;
 }
 

@@ -286,6 +286,23 @@ __device__ __forceinline__ void stage_gain(const IsoArgs& A, double* slab, int r
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// The same slab from a table that came BY VALUE in the launch's argument block (HeadGain, ssde_gain_feed.hpp; iso_shared_wg_kernel): no
+// copy precedes the launch and no pointer is chased -- the lanes read the packed rows straight from the block, same lane -> slab
+// element map as above, rows past the last repeat it, the columns no model writes are zero.
+__device__ __forceinline__ void stage_gain_value(const HeadGain& G, double* slab, int row0) {
+    const int lane = threadIdx.x & 63, rows = G.rows;
+    constexpr int NL = GAIN_SLAB_ROWS / (WAVE / GAIN_ROW);
+    // every load of the slab is issued before the first store waits for one: one round trip to the block
+    double t[NL];
+#pragma unroll
+    for (int i = 0; i < NL; i++) t[i] = head_gain_slab_at(G.v, rows, row0 + i * (WAVE / GAIN_ROW) + lane / GAIN_ROW, lane % GAIN_ROW);
+#pragma unroll
+    for (int i = 0; i < NL; i++) slab[(i * (WAVE / GAIN_ROW) + lane / GAIN_ROW) * GAIN_ROW + (lane % GAIN_ROW)] = t[i];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // rows [s0, s0 + SHARED_U) from a register block; `grow` = the slab row of s0 (table phase)
 template <bool STAT, int D, class Lane>
 __device__ __forceinline__ void run_block(Lane& S, const IsoArgs& A, const double (&blk)[SHARED_U][D], int s0, int ns,
@@ -313,7 +330,7 @@ __device__ __forceinline__ void run_block(Lane& S, const IsoArgs& A, const doubl
 // WG: the waves of the workgroup run the windows of ONE group (iso_shared_wg_kernel) -- only wave 0 walks table rows: one gain slab.
 template <bool STAT, int D, bool DEEP, bool WG, class Lane>
 __device__ __forceinline__ void run_segment(Lane& S, const IsoArgs& A, const double* base, int sa, int sb, int ns,
-                                            int ns_min, const double* mu) {
+                                            int ns_min, const double* mu, const HeadGain* G = nullptr) {
     const int C = A.tv.C, c_obs = A.tv.c_obs;
     const bool nt = A.stream_nt != 0;
     if (sa >= sb) return;
@@ -351,7 +368,10 @@ __device__ __forceinline__ void run_segment(Lane& S, const IsoArgs& A, const dou
         // TILE_SPARE (>= 3 blocks) keeps the look-ahead loads inside the allocation
         load_obs_block<D>(bufB, SSDE_ROWPTR(s0 + SHARED_U), C, c_obs, nt);
         const int srow = (s0 - sa) % GAIN_SLAB_ROWS;
-        if (!STAT && srow == 0) stage_gain(A, slab, s0);
+        if (!STAT && srow == 0) {
+            if (WG && G->rows > 0) stage_gain_value(*G, slab, s0);
+            else stage_gain(A, slab, s0);
+        }
         run_block<STAT, D>(S, A, bufA, s0, ns, ns_min, mu, slab + srow * GAIN_ROW);
         load_obs_block<D>(bufA, SSDE_ROWPTR(s0 + 2 * SHARED_U), C, c_obs, nt);
         if (s0 + SHARED_U < sb) run_block<STAT, D>(S, A, bufB, s0 + SHARED_U, ns, ns_min, mu, slab + (srow + SHARED_U) * GAIN_ROW);
@@ -364,7 +384,7 @@ __device__ __forceinline__ void run_segment(Lane& S, const IsoArgs& A, const dou
 // column: component k at rec_in[k * WAVE]), the record at its end to rec_end and the lane's accumulators to acc_out (registers).
 template <int MODEL, int D, int MASK, bool STATONLY, bool DEEP, bool WG = false>
 __device__ __forceinline__ int run_lane_shared(const IsoArgs& A, int g, int part, int chunk, double* rec_in = nullptr,
-                                               double* rec_end = nullptr, double* acc_out = nullptr) {
+                                               double* rec_end = nullptr, double* acc_out = nullptr, const HeadGain* G = nullptr) {
     typedef typename SharedSel<MODEL, D, MASK, STATONLY>::type Lane;
     constexpr int NACC = 4 + D;
     constexpr int SD = Lane::SD;
@@ -417,7 +437,7 @@ __device__ __forceinline__ int run_lane_shared(const IsoArgs& A, int g, int part
     // warm-up rows [s_begin, s_acc), then scored rows [s_acc, s_end); each split at s_stat
     {
         const int m = STATONLY ? s_begin : min(max(s_stat, s_begin), s_acc);
-        if (!STATONLY) run_segment<false, D, DEEP, WG>(S, A, base, s_begin, m, ns, ns_min, mu);
+        if (!STATONLY) run_segment<false, D, DEEP, WG>(S, A, base, s_begin, m, ns, ns_min, mu, G);
         run_segment<true, D, DEEP, WG>(S, A, base, m, s_acc, ns, ns_min, mu);
     }
     if (s_acc > s_begin) {
@@ -430,7 +450,7 @@ __device__ __forceinline__ int run_lane_shared(const IsoArgs& A, int g, int part
     }
     {
         const int m = STATONLY ? s_acc : min(max(s_stat, s_acc), s_end);
-        if (!STATONLY) run_segment<false, D, DEEP, WG>(S, A, base, s_acc, m, ns, ns_min, mu);
+        if (!STATONLY) run_segment<false, D, DEEP, WG>(S, A, base, s_acc, m, ns, ns_min, mu, G);
         run_segment<true, D, DEEP, WG>(S, A, base, m, s_end, ns, ns_min, mu);
     }
     if (WG) {
@@ -535,7 +555,7 @@ __global__ __launch_bounds__(WG_WAVES * WAVE, 1) void iso_shared_kernel(const Is
 // mailbox (A.mbx: system-scope stores, a wait for them -- no fence, as publish_if_last --, then the evaluation's sequence word, which
 // the host spins on: ssde_reduce_host.hpp forms the result) or to partials / chk[g] for a finalize launch without check workgroups.
 template <int MODEL, int D, int MASK, bool DEEP>
-__global__ __launch_bounds__(WG_WAVES * WAVE, 1) void iso_shared_wg_kernel(const IsoArgs A, const ReduceArgs R) {
+__global__ __launch_bounds__(WG_WAVES * WAVE, 1) void iso_shared_wg_kernel(const IsoArgs A, const HeadGain GV) {
     typedef typename SharedSel<MODEL, D, MASK, false>::type Lane0;
     typedef typename SharedSel<MODEL, D, MASK, true>::type LaneS;
     constexpr int NACC = 4 + D, NST = Lane0::NSTATE;
@@ -551,7 +571,7 @@ __global__ __launch_bounds__(WG_WAVES * WAVE, 1) void iso_shared_wg_kernel(const
     const long long wc0 = A.wave_clock ? wall_clock64() : 0;
     double end[NST], acc[NACC];
     int rows;
-    if (w == 0) rows = run_lane_shared<MODEL, D, MASK, false, DEEP, true>(A, g, 0, 0, nullptr, end, acc);
+    if (w == 0) rows = run_lane_shared<MODEL, D, MASK, false, DEEP, true>(A, g, 0, 0, nullptr, end, acc, &GV);      // (only wave 0 walks table rows)
     else rows = run_lane_shared<MODEL, D, MASK, true, DEEP, true>(A, g, 0, w, &rec[w - 1][0][lane], end, acc);
     __syncthreads();                                           // every window's record is in LDS (a wave whose lanes all ended early is here too)
     double worst = 0.0;
@@ -612,16 +632,18 @@ __global__ __launch_bounds__(WG_WAVES * WAVE, 1) void iso_shared_wg_kernel(const
 // One translation unit per model (k_iso_shared_ctcrw.hip, ..._ou.hip, ..._bm.hip): one kernel per (dimension, direction
 // mask, prefetch depth) is ~100 kernels, minutes of compile time each way -- split, they build side by side.
 template <int MODEL, int D, bool DEEP>
-static hipError_t launch_masks(const IsoArgs& a, const ReduceArgs& r, dim3 grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+static hipError_t launch_masks(const IsoArgs& a, const ReduceArgs& r, dim3 grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, const HeadGain* hg) {
     dim3 block(WG_WAVES * WAVE);
+    static const HeadGain no_table = {};                 // (rows == 0: the wg entry stages from a.gain)
+    const HeadGain& gv = hg ? *hg : no_table;
     if (MODEL == M_BM_SSM && (a.part_mask[0] & DIR_P2)) return hipErrorInvalidValue;     // BM_SSM has no second variance parameter
     switch (a.part_mask[0]) {
     // hipExtLaunchKernelGGL stamps ev0 / ev1 with the kernel's own begin / end (what rocprof reports), not with the
     // stream position of separately recorded events
     // (ev0 == NULL: a plain launch -- SSDE_OPT_KERNEL_STAMPS off -- which costs the host and the queue a few microseconds less)
-#define SSDE_LAUNCH_K(K, M) { if (ev0) hipExtLaunchKernelGGL((K<MODEL, D, M, DEEP>), grid, block, 0, s, ev0, ev1, 0, a, r); \
-                              else hipLaunchKernelGGL((K<MODEL, D, M, DEEP>), grid, block, 0, s, a, r); }
-#define SSDE_CASE(M) case M: if (a.wg_form) SSDE_LAUNCH_K(iso_shared_wg_kernel, M) else SSDE_LAUNCH_K(iso_shared_kernel, M) break;
+#define SSDE_LAUNCH_K(K, M, X) { if (ev0) hipExtLaunchKernelGGL((K<MODEL, D, M, DEEP>), grid, block, 0, s, ev0, ev1, 0, a, X); \
+                                 else hipLaunchKernelGGL((K<MODEL, D, M, DEEP>), grid, block, 0, s, a, X); }
+#define SSDE_CASE(M) case M: if (a.wg_form) SSDE_LAUNCH_K(iso_shared_wg_kernel, M, gv) else SSDE_LAUNCH_K(iso_shared_kernel, M, r) break;
         SSDE_CASE(0) SSDE_CASE(1) SSDE_CASE(2) SSDE_CASE(3) SSDE_CASE(4) SSDE_CASE(5) SSDE_CASE(6) SSDE_CASE(7)
 #if SSDE_SHARED_HAS_P2
         SSDE_CASE(8) SSDE_CASE(9) SSDE_CASE(10) SSDE_CASE(11) SSDE_CASE(12) SSDE_CASE(13) SSDE_CASE(14) SSDE_CASE(15)
@@ -635,9 +657,10 @@ static hipError_t launch_masks(const IsoArgs& a, const ReduceArgs& r, dim3 grid,
 
 // d = 1 runs the deep rotation, d = 2 the ping-pong pair (see run_segment)
 template <int MODEL>
-static hipError_t launch_shared_model(int d, const IsoArgs& a, const ReduceArgs& r, dim3 grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, bool) {
-    if (d == 1) return launch_masks<MODEL, 1, true>(a, r, grid, s, ev0, ev1);
-    if (d == 2) return launch_masks<MODEL, 2, false>(a, r, grid, s, ev0, ev1);
+static hipError_t launch_shared_model(int d, const IsoArgs& a, const ReduceArgs& r, dim3 grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, bool,
+                                      const HeadGain* hg) {
+    if (d == 1) return launch_masks<MODEL, 1, true>(a, r, grid, s, ev0, ev1, hg);
+    if (d == 2) return launch_masks<MODEL, 2, false>(a, r, grid, s, ev0, ev1, hg);
     return hipErrorInvalidValue;
 }
 

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ssde_gain_feed.hpp"
 #include "ssde_math.hpp"
 
 namespace ssde {
@@ -234,6 +235,9 @@ struct IsoArgs {
     double quiet_ld;             // log F at the stationary covariance
     double quiet_gld[3];         // ... dF / F per covariance direction
 };
+// iso_shared_wg_kernel takes the gain table by value where iso_shared_kernel takes ReduceArgs (ssde_gain_feed.hpp): what the block has left
+constexpr int HEAD_GAIN_ROWS = head_gain_capacity(sizeof(IsoArgs));
+typedef HeadGainT<HEAD_GAIN_ROWS> HeadGain;
 // One part of a k_iso_colvar.hip launch: the design columns whose coefficient gradients one wave of the workgroups carries
 // (device table, CV_WAVES entries)
 constexpr int CV_CMAX = 32;      // channels of a row the kernel can stage: dt, y, H_array entries (d = 2), DRIFT_KMAX columns
@@ -280,7 +284,9 @@ int iso_block_rows(int model);
 hipError_t launch_nan_blocks(const TileView& tv, int d, int block_rows, unsigned long long* bits, int nwords, hipStream_t s);
 // ev0 / ev1 (may be NULL): stamped with the kernel's own begin / end
 struct ReduceArgs;
-hipError_t launch_iso_shared(int model, int d, const IsoArgs& a, const ReduceArgs& r, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+// hg: the gain table by value (a.wg_form launches with hg->rows > 0; a.gain is then not read), or NULL
+hipError_t launch_iso_shared(int model, int d, const IsoArgs& a, const ReduceArgs& r, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1,
+                             const HeadGain* hg = nullptr);
 // shared-covariance lanes with a streamed row-varying drift (k_iso_drift.hip); partials [n_chunks][4 + d + drift_k][n_groups]
 hipError_t launch_iso_drift(int model, int d, const IsoArgs& a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 int drift_nstate(int model, int d, int k);
@@ -348,6 +354,8 @@ struct ReduceArgs {
     double lag_chk;
 };
 static_assert(sizeof(IsoArgs) + sizeof(ReduceArgs) <= 4096, "iso_shared_kernel and iso_finalize_kernel take both by value: the 4 KB argument block");
+static_assert(HEAD_GAIN_STRIDE == GAIN_ROW, "the packed rows expand to rows of the gain table");
+static_assert(HEAD_GAIN_ROWS >= 16 && sizeof(IsoArgs) + sizeof(HeadGain) <= HEAD_ARG_BLOCK, "iso_shared_wg_kernel takes both by value: the 4 KB argument block");
 hipError_t launch_reduce(const ReduceArgs& a, hipStream_t s);
 
 // ---- ingest (k_ingest.hip): long format -> tiles ------------------------------------------------

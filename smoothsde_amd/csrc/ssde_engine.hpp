@@ -203,6 +203,8 @@ struct ssde_handle {
     double* gain_pinned = nullptr;
     size_t gain_rows_cap = 0;
     int last_gain_rows = 0;
+    int last_gain_feed = 0;        // how the last evaluation's launch got its gain table: 0 the ring and a copy, 1 by value (ssde_last_gain_feed)
+    std::vector<double> gain_scratch;        // a deferred table's rows (build_gain_table / feed_gain_table)
     bool par_ev_pending[PAR_RING] = {false, false, false, false, false, false, false, false};   // slot last used by an asynchronous call
     bool sync_call = false;        // set around the evaluation of a synchronous ssde_eval (single engine, null stream)
 

@@ -28,27 +28,42 @@ WindowFacts window_facts(const ssde_handle* h) {
 // for the regular grid -- it does not depend on the observations -- until it is bitwise
 // stationary, upload the gains, and return the data-independent likelihood terms
 // (D/2 sum log F and its derivatives, weighted by how many tracks reach each row).
-// Stationarity test of the covariance recursion, shared by the gain table and ssde_lagforms_host.  In floating point the recursion
-// ends in a last-bit limit cycle rather than a bitwise fixed point, so "settled" = every component moved by less than 2e-15
-// relative; GAIN_SETTLED_ROWS such rows in a row end the recursion.
-constexpr int GAIN_SETTLED_ROWS = 4;
-inline bool gain_close(double a, double b) { return std::fabs(a - b) <= 2e-15 * (std::fabs(a) + std::fabs(b)) + 1e-300; }
-inline bool ctcrw_cov_settled(const CtcrwCov<15>& C, const CtcrwCov<15>& prev) {
-    bool same = gain_close(C.p11, prev.p11) && gain_close(C.p12, prev.p12) && gain_close(C.p22, prev.p22);
-    for (int j = 0; j < NDIRP && same; j++)
-        same = gain_close(C.d11[j], prev.d11[j]) && gain_close(C.d12[j], prev.d12[j]) && gain_close(C.d22[j], prev.d22[j]);
-    return same;
-}
+// (the stationarity test of the covariance recursion -- gain_close, ctcrw_cov_settled, GAIN_SETTLED_ROWS -- lives in ssde_gain_feed.hpp)
 
-template <int D>
-int build_gain_table(ssde_handle* h, IsoArgs& a, int mask, hipStream_t s, double add[4]) {
-    const int slot = h->par_next;
+// a slot of the ring for this evaluation's table: the ring protects the pinned slot of an ASYNCHRONOUS caller's earlier evaluation
+// (ssde_eval_device); a synchronous ssde_eval has read its result back before the next call: no event traffic on that path
+int gain_ring_slot(ssde_handle* h, int& slot) {
+    slot = h->par_next;
     h->par_next = (h->par_next + 1) % PAR_RING;
-    // the ring protects the pinned slot of an ASYNCHRONOUS caller's earlier evaluation (ssde_eval_device); a
-    // synchronous ssde_eval has read its result back before the next call: no event traffic on that path
     if (h->use_shared && (!h->sync_call || h->par_ev_pending[slot])) { HIPCHK(h, hipEventSynchronize(h->par_ev[slot])); h->par_ev_pending[slot] = false; }
+    return SSDE_OK;
+}
+int gain_ring_copy(ssde_handle* h, IsoArgs& a, int slot, int rows, hipStream_t s) {
     double* host = h->gain_pinned + (size_t)slot * h->gain_rows_cap * GAIN_ROW;
     double* dev = h->gain_ring.p + (size_t)slot * h->gain_rows_cap * GAIN_ROW;
+    if (h->use_shared) {                                    // (otherwise only the stationary constants are wanted)
+        HIPCHK(h, hipMemcpyAsync(dev, host, (size_t)rows * GAIN_ROW * 8, hipMemcpyHostToDevice, s));
+        if (!h->sync_call) { HIPCHK(h, hipEventRecord(h->par_ev[slot], s)); h->par_ev_pending[slot] = true; }
+    }
+    a.gain = dev;
+    return SSDE_OK;
+}
+
+// defer: the launch may take the table by value (the head of the lag-statistics path, iso_shared_wg_kernel) -- the rows go to the
+// handle's scratch, no ring slot is taken, no event touched and nothing copied; a.gain stays NULL until feed_gain_table has seen
+// the geometry.  Otherwise: a ring slot, the pinned rows and the copy, as ever.
+template <int D>
+int build_gain_table(ssde_handle* h, IsoArgs& a, int mask, hipStream_t s, double add[4], bool defer = false) {
+    int slot = -1;
+    double* host;
+    if (defer) {
+        if (h->gain_scratch.size() < h->gain_rows_cap * GAIN_ROW) h->gain_scratch.resize(h->gain_rows_cap * GAIN_ROW);
+        host = h->gain_scratch.data();
+    } else {
+        const int st = gain_ring_slot(h, slot);
+        if (st) return st;
+        host = h->gain_pinned + (size_t)slot * h->gain_rows_cap * GAIN_ROW;
+    }
     const int tmax = h->glen_max;                 // rows 0 .. tmax-1 can be asked for
     // running sums of log F and of its derivatives, row by row (member buffers: no allocation per evaluation)
     std::vector<double>& cum_ld = h->gain_cum[0];
@@ -118,11 +133,8 @@ int build_gain_table(ssde_handle* h, IsoArgs& a, int mask, hipStream_t s, double
         h->stat_ld = cum_ld[last] - cum_ld[last - 1];
         for (int j = 0; j < NDIRP; j++) h->stat_gld[j] = cum_g[j][last] - cum_g[j][last - 1];
     }
-    if (h->use_shared) {                                    // (otherwise only the stationary constants are wanted)
-        HIPCHK(h, hipMemcpyAsync(dev, host, (size_t)rows * GAIN_ROW * 8, hipMemcpyHostToDevice, s));
-        if (!h->sync_call) { HIPCHK(h, hipEventRecord(h->par_ev[slot], s)); h->par_ev_pending[slot] = true; }
-    }
-    a.gain = dev;
+    a.gain = nullptr;
+    if (!defer) { const int st = gain_ring_copy(h, a, slot, rows, s); if (st) return st; }
     a.gain_last = last;
     for (int k = 0; k < GAIN_ROW; k++) a.gain_stat[k] = host[(size_t)last * GAIN_ROW + k];
     fill_stat_consts(h->model, h->d, a);
@@ -141,6 +153,20 @@ int build_gain_table(ssde_handle* h, IsoArgs& a, int mask, hipStream_t s, double
     add[0] = 0.5 * D * s_ld;
     for (int j = 0; j < NDIRP; j++) add[1 + j] = 0.5 * D * s_g[j];
     return SSDE_OK;
+}
+
+// A deferred table (build_gain_table) once the geometry is known: by value in the launch's argument block when the launch is the
+// wg entry and the rows fit (ssde_gain_feed.hpp) -- no copy, no ring slot, no event: the table belongs to its launch, so no evaluation
+// in flight can see another's --, through the ring and the copy otherwise.
+int feed_gain_table(ssde_handle* h, IsoArgs& a, bool wg, hipStream_t s, HeadGain& gv) {
+    const int rows = a.gain_last + 1;
+    gv.rows = 0;
+    if (wg && head_gain_pack(h->gain_scratch.data(), rows, HEAD_GAIN_ROWS, gv.v)) { gv.rows = rows; return SSDE_OK; }
+    int slot;
+    const int st = gain_ring_slot(h, slot);
+    if (st) return st;
+    memcpy(h->gain_pinned + (size_t)slot * h->gain_rows_cap * GAIN_ROW, h->gain_scratch.data(), (size_t)rows * GAIN_ROW * 8);
+    return gain_ring_copy(h, a, slot, rows, s);
 }
 
 // The bulk's forms at this evaluation (ssde_lagforms.hpp): the taps are the impulse responses of the lanes' own stationary step
@@ -418,9 +444,11 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
         a.gain = nullptr;
         for (double& v : add) v = 0.0;
     }
+    // (only the head of the lag-statistics path launches the wg entry: window_geometry, head_latency_plan)
+    const bool gain_deferred = h->use_shared && h->lag_ready && !h->drift && !h->knobs.fused_finalize;
     if (h->use_shared) {
-        int st = (h->d == 1) ? build_gain_table<1>(h, a, h->iso_free_mask, s, add)
-                             : build_gain_table<2>(h, a, h->iso_free_mask, s, add);
+        int st = (h->d == 1) ? build_gain_table<1>(h, a, h->iso_free_mask, s, add, gain_deferred)
+                             : build_gain_table<2>(h, a, h->iso_free_mask, s, add, gain_deferred);
         if (st) return st;
         if (h->knobs.trace) { const double t = tick(); h->trace_us[1] += t - tk0; tk0 = t; }
         a.group_mode = 3;
@@ -463,6 +491,14 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
         a.wg_form = 1;
         if (host_finish) { a.mbx = h->mbx_pinned; a.mbx_seq = ++h->mbx_seq; }
     }
+    HeadGain gv;
+    gv.rows = 0;
+    if (gain_deferred) {
+        const int st = feed_gain_table(h, a, wg, s, gv);
+        if (st) return st;
+        if (h->knobs.trace) { const double t = tick(); h->trace_us[1] += t - tk0; tk0 = t; }
+    }
+    h->last_gain_feed = gv.rows > 0 ? 1 : 0;
     if (h->use_shared) {
         // two independent launches (NaN-free groups on the shared-covariance kernel, NaN-carrying groups on
         // the general kernel): fork onto a side stream so they share the chip, join before the hand-over check
@@ -509,7 +545,8 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
             // the bulk's forms, on the host: the single launch of the fused form needs them; the two-launch form computes them
             // while the head runs (below), for its finalize launch
             if (lag_K > 0 && fused) { const int st = lag_forms_into(h, a, order, lag_K, a.n_chunks, ra); if (st) return st; }
-            HIPCHK(h, launch_iso_shared(h->model, h->d, b, ra, s, h->stamps ? h->ev_k0 : nullptr, h->stamps ? h->ev_k1 : nullptr));
+            HIPCHK(h, launch_iso_shared(h->model, h->d, b, ra, s, h->stamps ? h->ev_k0 : nullptr, h->stamps ? h->ev_k1 : nullptr,
+                                        gv.rows > 0 ? &gv : nullptr));
         }
         h->last_kernel_id = h->drift ? SSDE_KERNEL_ISO_DRIFT : any_dirty ? SSDE_KERNEL_ISO_MIXED : SSDE_KERNEL_ISO_SHARED;
         h->ev_k_valid = h->stamps;
@@ -599,6 +636,16 @@ extern "C" int ssde_reduce_host(const double* sums, const double* group_chk, int
 extern "C" int ssde_last_finish_form(const ssde_handle* h) {
     if (!h) return -1;
     return h->shards.empty() ? h->last_finish_form : h->shards[0]->last_finish_form;
+}
+
+extern "C" int ssde_last_gain_feed(const ssde_handle* h) {
+    if (!h) return -1;
+    return h->shards.empty() ? h->last_gain_feed : h->shards[0]->last_gain_feed;
+}
+
+extern "C" int ssde_last_gain_rows(const ssde_handle* h) {
+    if (!h) return -1;
+    return h->shards.empty() ? h->last_gain_rows : h->shards[0]->last_gain_rows;
 }
 
 extern "C" int ssde_lagforms_host(const double* M, const double* s, double n_bulk, int32_t d, const double* theta, double dt,
