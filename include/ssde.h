@@ -29,6 +29,8 @@
  *                         what speed, distance travelled, time in a region or multiple imputation are computed from
  *   ssde_predict       <- (new) the smoothed state at any time between or after the rows, from the smoother's records: what the
  *                         reference gets by rebuilding the data with NA rows at the wanted times
+ *   ssde_path_stats    <- (new) summaries of those draws reduced on the device: path length, net displacement and weighted time
+ *                         inside up to eight boxes per track and draw, without a draw leaving the device
  *   ssde_penalty       <- smoothing penalty     (nllk_ctcrw.hpp:254-280, nllk_sde.hpp:89-124)
  *   ssde_info          <- InfoADFunObject       (src/init.c:7)
  *   ssde_forget        <- (new) drops the memo of ssde_eval
@@ -369,6 +371,31 @@ int ssde_smooth_draws(ssde_handle *h, const double *par, int32_t n_par_full, uin
  * wavefront groups under SSDE_OPT_SMOOTH_BUDGET_MB, and the result does not depend on the chunking. */
 int ssde_predict(ssde_handle *h, const double *par, int32_t n_par_full, const int64_t *q_row, const double *q_off, int64_t n_query,
                  double *a_pred, double *P_pred);
+
+/* Summaries of posterior state paths at `par`, reduced on the device (definitions: DESIGN.md §3.12).  Draw q is draw number draw0 + q
+ * of the stream `seed`: exactly the path ssde_smooth_draws returns for it.  A track's state rows are the CALLER's rows first + 1 ..
+ * last (a lattice-padded handle samples its padded rows, which take part in no statistic); the position columns are state column 2a
+ * of response column a for a CTCRW and state column a for OU_SSM / BM_SSM.
+ *   stats [n_tracks x n_stat x n_draws], n_stat = 2 + n_regions: element (t, k, q) at t + n_tracks * (k + n_stat * q), t the ID
+ *   segment's ordinal in the caller's data.
+ *     k = 0      path length: the sum over consecutive state rows of the Euclidean distance between their positions (0 for one row)
+ *     k = 1      net displacement: the distance between the positions at the last and the first state row
+ *     k = 2 + r  the sum over state rows j of w_j 1[lo_c <= p_jc < hi_c for every position column c] of region r
+ *   regions [n_regions x 4] row-major: lo_1, hi_1, lo_2, hi_2 (the second pair is not read for n_dim = 1); +-inf bounds make half-planes.
+ *   weight  [n] host memory, indexed by the caller's row, or NULL for w_j = 1.  Weights are not validated: a non-finite weight enters
+ *   the sums it is added to.
+ * NaN in every statistic of every draw of a track without a state row (a one-row track), and in every statistic of a (track, draw)
+ * whose path has a non-finite position on a state row (the negative-P0 / det F <= 0 corner of §3.10).
+ * SSDE_ERR_ARG for NULL par / stats, n_draws < 1, draw0 < 0, draw0 + n_draws >= 2^28, n_regions outside 0 .. SSDE_PATH_MAX_REGIONS,
+ * regions NULL with n_regions > 0, a NaN bound or lo > hi, flags != 0.  SSDE_ERR_MODEL for the direct families and ESEAL_SSM (as
+ * ssde_smooth) and for EVERY handle with n_dim > 2, column pairs and coupled filters alike: a distance needs the position columns in
+ * one lane, and the pairs of a wide response sit in different handles.  Multi-device handles are served (shards own whole tracks).
+ * Leaves the memo, the window state, the TV records, n_evals / n_memo_hits and every later ssde_eval / ssde_smooth / ssde_smooth_draws /
+ * ssde_predict result as they were; its buffers are its own, chunked by whole wavefront groups under SSDE_OPT_SMOOTH_BUDGET_MB, and the
+ * result does not depend on the chunking, on how the draws are cut over calls or on the devices. */
+#define SSDE_PATH_MAX_REGIONS 8
+int ssde_path_stats(ssde_handle *h, const double *par, int32_t n_par_full, uint64_t seed, int64_t draw0, int32_t n_draws,
+                    const double *regions, int32_t n_regions, const double *weight, double *stats, uint32_t flags);
 
 /* Multiply the warm-up overlap of the time windows by `factor` for all later evaluations
  * (factor <= 0: force one sequential window). */

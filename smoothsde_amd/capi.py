@@ -493,6 +493,8 @@ def load_library():
     lib.ssde_smooth_draws.restype = C.c_int
     lib.ssde_predict.argtypes = [C.c_void_p, _dp, C.c_int32, C.POINTER(C.c_int64), _dp, C.c_int64, _dp, _dp]
     lib.ssde_predict.restype = C.c_int
+    lib.ssde_path_stats.argtypes = [C.c_void_p, _dp, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, _dp, C.c_int32, _dp, _dp, C.c_uint32]
+    lib.ssde_path_stats.restype = C.c_int
     lib.ssde_widen_windows.argtypes = [C.c_void_p, C.c_int32]
     lib.ssde_widen_windows.restype = C.c_int
     lib.ssde_relax_windows.argtypes = [C.c_void_p]
@@ -562,13 +564,14 @@ class EngineError(RuntimeError):
     status = None
 
 
+PATH_MAX_REGIONS = 8   # SSDE_PATH_MAX_REGIONS (include/ssde.h)
 DRAWS_DEVICE_OUT = 1   # ssde_smooth_draws flag: `draws` is an HBM pointer on the handle's device (include/ssde.h)
 
 WINDOW_TOL = 1e-11  # largest tolerated relative hand-over disagreement between time windows
 
 EXPORTED_SYMBOLS = ("ssde_create", "ssde_eval", "ssde_eval_device", "ssde_penalty", "ssde_report", "ssde_widen_windows", "ssde_relax_windows",
                     "ssde_info", "ssde_destroy", "ssde_last_error", "ssde_abi_version", "ssde_comm_unique_id", "ssde_comm_init_rank", "ssde_forget", "ssde_laplace_eval", "ssde_last_kernel_ms", "ssde_kernel_ms_history",
-                    "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth", "ssde_smooth_draws", "ssde_predict",
+                    "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth", "ssde_smooth_draws", "ssde_predict", "ssde_path_stats",
                     "ssde_lagstats_host_m", "ssde_lagstats_read_m", "ssde_lagforms_host_m", "ssde_reduce_host", "ssde_last_finish_form", "ssde_last_gain_feed", "ssde_last_gain_rows")
 
 
@@ -960,6 +963,35 @@ class Engine:
         self._check(self.lib.ssde_predict(self._h, par.ctypes.data_as(_dp), self.n_par_full, rows.ctypes.data_as(C.POINTER(C.c_int64)),
                                           offsets.ctypes.data_as(_dp), m, mean.ctypes.data_as(_dp), P.ctypes.data_as(_dp) if cov else None))
         return {"mean": mean, "cov": P}
+
+    def path_stats(self, par, n_draws: int, seed: int = 0, draw0: int = 0, regions=None, weight=None):
+        """Summaries of posterior state paths at `par`, reduced on the device (ssde_path_stats): an array of shape
+        (n_draws, n_tracks, n_stat), n_stat = 2 + n_regions -- path length, net displacement, then per region the sum of `weight`
+        over the track's state rows whose position is inside.  Draw k is draw number draw0 + k of the stream `seed`, the path
+        smooth_draws returns for it.  `regions`: (n_regions, 4) rows of lo_1, hi_1, lo_2, hi_2 (at most PATH_MAX_REGIONS; +-inf
+        allowed) or None; `weight`: one number per row of the data, or None for 1.  NaN for a one-row track and for a (track, draw)
+        with a non-finite position."""
+        par = np.ascontiguousarray(par, dtype=np.float64)
+        if par.shape != (self.n_par_full,):
+            raise ValueError(f"par must have length {self.n_par_full}")
+        if regions is None:
+            reg = np.zeros((0, 4))
+        else:
+            reg = np.ascontiguousarray(regions, dtype=np.float64)
+            if reg.ndim != 2 or reg.shape[1] != 4:
+                raise ValueError("regions must have shape (n_regions, 4): lo_1, hi_1, lo_2, hi_2")
+        w = None
+        if weight is not None:
+            w = np.ascontiguousarray(weight, dtype=np.float64)
+            if w.shape != (self.problem.n,):
+                raise ValueError("weight must hold one number per row of the data")
+        n_stat = 2 + len(reg)
+        n_trk = self.problem.n_seg
+        buf = np.zeros((max(int(n_draws), 0), n_stat, n_trk))                          # element (t, k, q) at t + n_tracks (k + n_stat q)
+        self._check(self.lib.ssde_path_stats(self._h, par.ctypes.data_as(_dp), self.n_par_full, int(seed), int(draw0), int(n_draws),
+                                             reg.ctypes.data_as(_dp) if len(reg) else None, len(reg),
+                                             None if w is None else w.ctypes.data_as(_dp), buf.ctypes.data_as(_dp), 0))
+        return buf.transpose(0, 2, 1)
 
     def close(self):
         if self._h:

@@ -632,6 +632,25 @@ struct DrawArgs {
     double* out;
 };
 hipError_t launch_smooth_draws(const DrawArgs& a, hipStream_t s);
+// ---- summaries of the drawn paths (k_path_stats.hip, ssde_path.hpp) ----
+// The draws of a DrawArgs `d` (its out / draw_stride are not read), reduced in registers to n_stat = 2 + n_regions numbers per (track,
+// draw): statistic k of draw q of the lane's track at stats + lane_trk[l] + n_trk * (k + n_stat * q), q counted within the batch.
+// The regions travel by value (256 B of uniform operands).
+#ifndef SSDE_PATH_MAX_REGIONS
+#define SSDE_PATH_MAX_REGIONS 8
+#endif
+struct PathArgs {
+    DrawArgs d;
+    const int64_t* row_map;      // [n_out]: the caller's row of a lattice row, -1 on a padded row; NULL: the rows ARE the caller's
+    const double* weight;        // [the caller's rows]: w_j, or NULL for 1
+    double* stats;               // [n_trk x n_stat x n_draws]
+    int64_t n_trk;               // the handle's ID segments
+    int n_regions;
+    double regions[SSDE_PATH_MAX_REGIONS * 4];   // lo_1, hi_1, lo_2, hi_2 per region
+};
+hipError_t launch_path_stats(const PathArgs& a, hipStream_t s);
+// map[pos[i]] = i for the caller's rows i < n, -1 on the other lattice rows (np of them)
+hipError_t launch_path_row_map(const int64_t* pos, int64_t n, int64_t np, int64_t* map, hipStream_t s);
 // ---- the state at any time from the records (k_predict.hip, ssde_predict.hpp) ----
 // The records, side rows, groups and lanes of a SmoothArgs `s`.  Lane l wants the steps want_step[want_off[l] .. want_off[l + 1]) (ascending);
 // entry i of that list is slot i, and the walk stores its packet's double k at pk + k * pk_stride + (i - slot0).  The query kernel

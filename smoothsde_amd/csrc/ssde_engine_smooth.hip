@@ -249,6 +249,80 @@ int draws_single(ssde_handle* h, const double* par, uint64_t seed, int64_t draw0
     return SSDE_OK;
 }
 
+// ---- ssde_path_stats ----------------------------------------------------------------------------------------------------------
+// One engine's statistics [n_seg x n_stat x n_draws] into host memory: the draws' walk with the stores replaced by the reduction
+// (k_path_stats.hip).  Records as draws_single produces them: once when there is one chunk, per batch of draws otherwise; a batch is
+// what one launch's second grid dimension takes.  weight: the engine's own rows (host) or NULL; track0: the ID segments of the shards
+// before this one (the deviates' counter only: the statistics are placed by the engine's own ordinals).
+int path_single(ssde_handle* h, const double* par, uint64_t seed, int64_t draw0, int n_draws, const double* regions, int n_regions,
+                const double* weight, double* stats, int64_t track0) {
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(0));
+    RecordRun run;
+    { int st = run.setup(h, par, "ssde_path_stats"); if (st) return st; }
+    const int64_t nt = run.nt, n = h->n, n_trk = h->n_seg;
+    const int n_stat = 2 + n_regions;
+    if ((int64_t)h->lane_seg.n < run.n_lanes) { h->err = "ssde_path_stats: the handle holds no track ordinals for its lanes"; return SSDE_ERR_ARG; }
+    if (n_trk == 0) return SSDE_OK;
+    DevBuf<double> sb, wb;
+    DevBuf<int64_t> map;
+    SmoothBufs guard{{&sb, &wb}, {&map}};
+    // draws per batch: what one launch's second grid dimension takes, and what fits the budget beside the records (whole waves of
+    // DRAW_CH draws; one wave's draws always go)
+    const size_t per_draw = (size_t)n_trk * n_stat;
+    int64_t nb_max = std::min<int64_t>(std::max<int64_t>(run.budget / (int64_t)per_draw, DRAW_CH), (int64_t)DRAW_CH << 15);
+    nb_max -= nb_max % DRAW_CH;
+    const int nb_cap = (int)std::min<int64_t>(nb_max, n_draws);
+    HIPCHK(h, sb.alloc(per_draw * nb_cap));
+    if (weight && n > 0) HIPCHK(h, wb.upload(std::vector<double>(weight, weight + n)));
+    PathArgs a;
+    memset(&a, 0, sizeof(a));
+    if (nt != n) {                                                      // the caller's row OF each lattice row
+        HIPCHK(h, map.alloc((size_t)nt));
+        HIPCHK(h, launch_path_row_map(h->pad_row.p, n, nt, map.p, 0));
+        a.row_map = map.p;
+    }
+    a.d.lane_trk = h->lane_seg.p; a.d.track0 = track0; a.d.seed = seed; a.d.col0 = 0;
+    a.weight = (weight && n > 0) ? wb.p : nullptr;
+    a.stats = sb.p; a.n_trk = n_trk; a.n_regions = n_regions;
+    for (int k = 0; k < 4 * n_regions; k++) a.regions[k] = regions[k];
+    bool have_records = false;
+    for (int k0 = 0; k0 < n_draws; k0 += nb_cap) {
+        const int nb = std::min(nb_cap, n_draws - k0);
+        HIPCHK(h, hipMemset(sb.p, 0xff, per_draw * nb * 8));            // NaN (all bits set) where no lane writes
+        a.d.draw0 = (uint32_t)(draw0 + k0); a.d.n_draws = nb;
+        for (size_t c = 0; c < run.n_chunks(); c++) {
+            if (!have_records || run.n_chunks() > 1) { int st = run.produce(c); if (st) return st; }
+            have_records = true;
+            a.d.s = run.s;
+            HIPCHK(h, launch_path_stats(a, 0));
+        }
+        HIPCHK(h, hipMemcpy(stats + per_draw * k0, sb.p, per_draw * nb * 8, hipMemcpyDeviceToHost));
+    }
+    HIPCHK(h, hipStreamSynchronize(0));
+    return SSDE_OK;
+}
+
+// the track shards' statistics: each shard reads its own slice of the weights, counts its deviates by the GLOBAL track ordinal and
+// lands at its tracks' places in the parent's array
+int path_sharded(ssde_handle* parent, const double* par, uint64_t seed, int64_t draw0, int n_draws, const double* regions,
+                 int n_regions, const double* weight, double* stats) {
+    const int64_t N = parent->n_seg;
+    const int n_stat = 2 + n_regions;
+    std::fill(stats, stats + (size_t)N * n_stat * n_draws, std::numeric_limits<double>::quiet_NaN());
+    int64_t track0 = 0;
+    for (size_t k = 0; k < parent->shards.size(); k++) {
+        ssde_handle* sh = parent->shards[k];
+        const int64_t lo = parent->shard_row0[k], m = sh->n_seg;
+        std::vector<double> t((size_t)m * n_stat * n_draws);
+        int st = path_single(sh, par, seed, draw0, n_draws, regions, n_regions, weight ? weight + lo : nullptr, t.data(), track0);
+        if (st) { parent->err = sh->err; return st; }
+        for (int64_t q = 0; q < (int64_t)n_stat * n_draws; q++) memcpy(stats + (size_t)N * q + track0, t.data() + (size_t)m * q, (size_t)m * 8);
+        track0 += m;
+    }
+    return SSDE_OK;
+}
+
 // ---- ssde_predict -------------------------------------------------------------------------------------------------------------
 // One engine's queries.  Planning on the host: every query goes to the state row (lane, step) that starts its interval in the
 // handle's resident layout, plus a residual offset; the wanted steps become a list per lane (slots) and the queries are ordered by
@@ -489,6 +563,33 @@ int ssde_smooth_draws(ssde_handle* h, const double* par, int32_t n_par_full, uin
         return draws_sharded(h, par, seed, draw0, n_draws, draws, dev_out);
     }
     return draws_single(h, par, seed, draw0, n_draws, draws, dev_out, (int64_t)h->n * h->sdim, 0, 0);
+}
+
+int ssde_path_stats(ssde_handle* h, const double* par, int32_t n_par_full, uint64_t seed, int64_t draw0, int32_t n_draws,
+                    const double* regions, int32_t n_regions, const double* weight, double* stats, uint32_t flags) {
+    if (!h || !par || !stats) { if (h) h->err = "ssde_path_stats: no parameter vector, or no output"; return SSDE_ERR_ARG; }
+    if (n_par_full != h->L.n_full) { h->err = "parameter vector has the wrong length"; return SSDE_ERR_ARG; }
+    if (n_draws < 1 || draw0 < 0 || draw0 + (int64_t)n_draws >= ((int64_t)1 << 28)) {
+        h->err = "ssde_path_stats: n_draws >= 1, draw0 >= 0 and draw0 + n_draws < 2^28 are required";
+        return SSDE_ERR_ARG;
+    }
+    if (n_regions < 0 || n_regions > SSDE_PATH_MAX_REGIONS || (n_regions > 0 && !regions)) {
+        h->err = "ssde_path_stats: 0 <= n_regions <= SSDE_PATH_MAX_REGIONS, with a table of bounds when there are regions";
+        return SSDE_ERR_ARG;
+    }
+    for (int k = 0; k < 2 * n_regions; k++) {
+        const double lo = regions[2 * k], hi = regions[2 * k + 1];
+        if ((k & 1) && h->d == 1) continue;                         // the second pair is not read for one position column
+        if (std::isnan(lo) || std::isnan(hi) || lo > hi) { h->err = "ssde_path_stats: a region bound that is NaN, or lo > hi"; return SSDE_ERR_ARG; }
+    }
+    if (flags != 0) { h->err = "ssde_path_stats: unknown flag"; return SSDE_ERR_ARG; }
+    if (!is_kalman(h->model)) { h->err = "the smoother serves the Kalman families only (the direct families have no state; ESEAL_SSM no REPORT)"; return SSDE_ERR_MODEL; }
+    if (h->d > 2) {
+        h->err = "ssde_path_stats: a response of three or more columns is not served, as column pairs or as one coupled filter (a distance needs the position columns in one lane)";
+        return SSDE_ERR_MODEL;
+    }
+    if (!h->shards.empty()) return path_sharded(h, par, seed, draw0, n_draws, regions, n_regions, weight, stats);
+    return path_single(h, par, seed, draw0, n_draws, regions, n_regions, weight, stats, 0);
 }
 
 int ssde_predict(ssde_handle* h, const double* par, int32_t n_par_full, const int64_t* q_row, const double* q_off, int64_t n_query,

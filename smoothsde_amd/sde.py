@@ -531,6 +531,25 @@ class SDE:
             raise NotImplementedError(f"sample_states: no latent state in the model {self.type_!r}")
         return self.engine_.smooth_draws(self._current_par_full(), n_draws, seed=seed)
 
+    def path_summary(self, n_draws, seed=0, regions=None, weight="dt"):
+        """Summaries of the posterior state paths of a state-space model (CTCRW, OU_SSM, BM_SSM) at the current parameters, reduced
+        on the device (ssde_path_stats): no draw comes home.  {"length": (n_draws, n_tracks) distance travelled
+        along the drawn path, "displacement": (n_draws, n_tracks) distance between its two ends, "in_region": (n_draws, n_tracks,
+        n_regions) weighted rows inside each region}.  `regions`: rows of lo_1, hi_1, lo_2, hi_2 or None.  `weight`: "dt" weighs a
+        row by the time to the track's next row (0 at its last row), so "in_region" is time spent inside; an array (one number per
+        row) is passed through; None counts rows.  The draws are those of sample_states(n_draws, seed)."""
+        if self.type_ not in ("CTCRW", "OU_SSM", "BM_SSM"):
+            raise NotImplementedError(f"path_summary: no latent state in the model {self.type_!r}")
+        if isinstance(weight, str):
+            if weight != "dt":
+                raise ValueError('weight must be "dt", an array or None')
+            ids, t = np.asarray(self.data_["ID"]), np.asarray(self.data_["time"], dtype=np.float64)
+            weight = np.zeros(len(t))
+            same = ids[1:] == ids[:-1]
+            weight[:-1][same] = (t[1:] - t[:-1])[same]
+        st = self.engine_.path_stats(self._current_par_full(), n_draws, seed=seed, regions=regions, weight=weight)
+        return {"length": st[:, :, 0], "displacement": st[:, :, 1], "in_region": st[:, :, 2:]}
+
     def residuals(self):
         """Model residuals, iid N(0, 1) under the model (one column per response variable).
 
