@@ -20,7 +20,7 @@ __global__ __launch_bounds__(WAVE) void dense_kernel(const DenseArgs A) {
     typedef DenseDims<MODEL, D> DM;
     constexpr int SD = DM::SD, Q = DM::Q;
     constexpr bool REPORT = MODE == 1;
-    const int g = blockIdx.x + (MODE == 2 ? A.g0 : 0), b = blockIdx.y, lane = threadIdx.x;
+    const int g = blockIdx.x + (MODE == 2 ? A.rc.g0 : 0), b = blockIdx.y, lane = threadIdx.x;
     const TileView& tv = A.tv;
     const SlotTable* __restrict__ T = A.slots;
     const int C = tv.C;
@@ -91,15 +91,12 @@ __global__ __launch_bounds__(WAVE) void dense_kernel(const DenseArgs A) {
             }
         }
         if constexpr (MODE == 2) {
-            // records of the group at srec_off[g] (chunk-relative), double k of step s at (s * R + k) * 64 + lane
-            double* rp = A.srec + (A.srec_off[g] - A.srec_base) + (int64_t)s0 * SmoothRec<MODEL, D>::R * WAVE + lane;
-            const bool upd = smooth_record_row<MODEL, D>(S, par, H, dt, y, is_na(y[0], A.any_nan), [&](int k) -> double& { return rp[(int64_t)k * WAVE]; });
+            const int64_t goff = rec_group(A.rc, g);
+            const bool upd = smooth_record_row<MODEL, D>(S, par, H, dt, y, is_na(y[0], A.any_nan), rec_row<SmoothRec<MODEL, D>::R>(A.rc, goff, lane, s0));
             if constexpr (D <= 2) {
-                if (A.sside) {                                                   // ssde_predict: the row's linear predictors and interval
-                    constexpr int SW = PredictPk<MODEL, D>::SW;
-                    double* sp = A.sside + (A.srec_off[g] - A.srec_base) / SmoothRec<MODEL, D>::R * SW + (int64_t)s0 * SW * WAVE + lane;
-                    predict_side_row<MODEL, D>(par, dt, is_na(y[0], A.any_nan), upd, [&](int k) -> double& { return sp[(int64_t)k * WAVE]; });
-                }
+                if (A.rc.side)                                                   // ssde_predict: the row's linear predictors and interval
+                    predict_side_row<MODEL, D>(par, dt, is_na(y[0], A.any_nan), upd,
+                                               rec_side_row<SmoothRec<MODEL, D>::R, PredictPk<MODEL, D>::SW>(A.rc, goff, lane, s0));
             }
         }
         dense_step<MODEL, D, N>(S, par, H, dt, y, is_na(y[0], A.any_nan));
@@ -122,8 +119,8 @@ hipError_t launch_dense_wide(const DenseArgs& a, bool want_grad, hipStream_t s);
 
 #define SSDE_L(MODEL, D)                                                                          \
     if (a.model == MODEL && a.d == D) {                                                           \
-        if (a.srec)                                                                               \
-            hipLaunchKernelGGL((dense_kernel<MODEL, D, 0, 2>), dim3(a.srec_groups, 1), block, 0, s, a); \
+        if (a.rc.rec)                                                                             \
+            hipLaunchKernelGGL((dense_kernel<MODEL, D, 0, 2>), dim3(a.rc.n_groups, 1), block, 0, s, a); \
         else if (a.report)                                                                        \
             hipLaunchKernelGGL((dense_kernel<MODEL, D, 0, 1>), dim3(a.tv.n_groups, 1), block, 0, s, a); \
         else if (!want_grad)                                                                      \

@@ -1,11 +1,9 @@
 // k_path_stats.hip -- summaries of posterior state paths for gfx950 (ssde_path_stats; math in ssde_path.hpp over ssde_draws.hpp,
 // definitions DESIGN.md §3.12).
 //
-// path_stats_kernel: the walk of smooth_draws_kernel (k_smooth_draws.hip) -- lane = track, one wave per (group of 64 tracks, chunk
-// of DRAW_CH draws), the records read from the last step to the first in 512-B wave loads, the row's factors formed once per step
-// and applied to the chunk's DRAW_CH paths -- with the n x sdim stores of every draw replaced by path_step: the length, the end
-// positions and the region sums of each (lane, draw) stay in registers, and after the walk the lane stores n_stat numbers per draw at
-// its track's ordinal.  One wave owns each (track, draw): plain stores, no atomics, a deterministic result.  The only per-row reads
+// path_stats_kernel: the walk of smooth_draws_kernel (rec_draw_walk, ssde_records.hpp: lane = track, one wave per (group of 64 tracks,
+// chunk of DRAW_CH draws)) with the n x sdim stores of every draw replaced by path_step: the length, the end positions and the region
+// sums of each (lane, draw) stay in registers, and after the walk the lane stores n_stat numbers per draw at its track's ordinal.  One wave owns each (track, draw): plain stores, no atomics, a deterministic result.  The only per-row reads
 // beside the records are the row's weight and, on a lattice-padded handle, its entry of the lattice row -> caller row map: per-lane
 // addresses, but a lane's successive rows share lines.  64-bit offsets throughout.
 #include "ssde_device.hpp"
@@ -17,58 +15,27 @@ static_assert(PATH_NREG * 4 * sizeof(double) == sizeof(PathArgs::regions), "regi
 
 template <int MODEL, int D>
 __global__ __launch_bounds__(WAVE) void path_stats_kernel(const PathArgs A) {
-    typedef SmoothRec<MODEL, D> RC;
-    typedef DrawFac<MODEL, D> FC;
-    constexpr int SD = RC::SD;
-    const int g = A.d.s.g0 + blockIdx.x, lane = threadIdx.x;
+    constexpr int SD = SmoothRec<MODEL, D>::SD;
+    const RecLane L = rec_lane(A.d.s);
     const int k0 = blockIdx.y * DRAW_CH;
-    const int64_t l = (int64_t)g * WAVE + lane;
-    const bool has = l < A.d.s.n_lanes;
-    const int ns = has ? A.d.s.lane_ns[l] : 0;
-    const int64_t row0 = has ? A.d.s.lane_row0[l] : 0;
-    const int64_t seg = has ? A.d.lane_trk[l] : 0;
-    const uint64_t trk = (uint64_t)(A.d.track0 + seg);
-    int smax = ns;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) smax = max(smax, __shfl_xor(smax, o, 64));
-    smax = __builtin_amdgcn_readfirstlane(smax);
-    const double* base = A.d.s.rec + (A.d.s.rec_off[g] - A.d.s.rec_base) + lane;
-    double al[DRAW_CH][SD];
+    const int64_t seg = L.has ? A.d.lane_trk[L.l] : 0;
     PathAcc<D> acc[DRAW_CH];
 #pragma unroll
-    for (int q = 0; q < DRAW_CH; q++) {
-#pragma unroll
-        for (int c = 0; c < SD; c++) al[q][c] = 0.0;
-        path_init<D>(acc[q]);
-    }
-    DrawNext<SD> nx;
-#pragma unroll
-    for (int r = 0; r < SD; r++) {
-        nx.a[r] = 0.0; nx.id[r] = 0.0;
-#pragma unroll
-        for (int c = 0; c < SD; c++) nx.Lp[r][c] = 0.0;
-    }
+    for (int q = 0; q < DRAW_CH; q++) path_init<D>(acc[q]);
     const int nreg = A.n_regions;
-    for (int s = smax - 1; s >= 0; s--) {
-        if (s >= ns) continue;
-        const double* rp = base + (int64_t)s * RC::R * WAVE;
-        const bool tail = s == ns - 1;
-        double fac[FC::R];
-        draw_factor_row<MODEL, D, SD>([&](int k) -> double { return rp[(int64_t)k * WAVE]; }, tail, nx,
-                                      [&](int k) -> double& { return fac[k]; });
-        const int64_t row = row0 + 1 + s;
-        const int64_t crow = A.row_map ? A.row_map[row] : row;
-        const bool is_row = crow >= 0;
-        const double w = (is_row && A.weight) ? A.weight[crow] : 1.0;
-#pragma unroll
-        for (int q = 0; q < DRAW_CH; q++) {
-            double z[SD];
-            draw_deviates<SD>(A.d.seed, trk, (uint32_t)s, A.d.draw0 + (uint32_t)(k0 + q), A.d.col0, z);
-            draw_step<MODEL, D, SD>([&](int k) -> double { return fac[k]; }, tail, al[q], z);
-            path_step<MODEL, D, SD>(acc[q], al[q], is_row, w, [&](int k) -> double { return A.regions[k]; }, nreg);
-        }
-    }
-    if (ns <= 0) return;                                            // no state row: the preset NaN stays
+    bool is_row = false;
+    double w = 1.0;
+    rec_draw_walk<MODEL, D, DRAW_CH>(
+        L, A.d.seed, (uint64_t)(A.d.track0 + seg), A.d.draw0 + (uint32_t)k0, A.d.col0,
+        [&](int64_t row) {
+            const int64_t crow = A.row_map ? A.row_map[row] : row;
+            is_row = crow >= 0;
+            w = (is_row && A.weight) ? A.weight[crow] : 1.0;
+        },
+        [&](int q, const double (&al)[SD]) {
+            path_step<MODEL, D, SD>(acc[q], al, is_row, w, [&](int k) -> double { return A.regions[k]; }, nreg);
+        });
+    if (L.ns <= 0) return;                                            // no state row: the preset NaN stays
     const int nstat = 2 + nreg;
 #pragma unroll
     for (int q = 0; q < DRAW_CH; q++) {
@@ -96,9 +63,9 @@ hipError_t launch_path_row_map(const int64_t* pos, int64_t n, int64_t np, int64_
 }
 
 hipError_t launch_path_stats(const PathArgs& a, hipStream_t s) {
-    if (a.d.s.n_groups == 0 || a.d.n_draws <= 0) return hipSuccess;
+    if (a.d.s.rc.n_groups == 0 || a.d.n_draws <= 0) return hipSuccess;
     if (a.n_regions < 0 || a.n_regions > PATH_NREG) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)a.d.s.n_groups, (unsigned)((a.d.n_draws + DRAW_CH - 1) / DRAW_CH));
+    const dim3 grid((unsigned)a.d.s.rc.n_groups, (unsigned)((a.d.n_draws + DRAW_CH - 1) / DRAW_CH));
     if (grid.y > 65535u) return hipErrorInvalidValue;
 #define SSDE_PK(MODEL, D) \
     if (a.d.s.model == MODEL && a.d.s.d == D) { hipLaunchKernelGGL((path_stats_kernel<MODEL, D>), grid, dim3(WAVE), 0, s, a); return hipGetLastError(); }

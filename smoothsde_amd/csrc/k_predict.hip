@@ -18,25 +18,16 @@ __global__ __launch_bounds__(WAVE) void predict_walk_kernel(const PredictArgs A)
     typedef SmoothRec<MODEL, D> RC;
     typedef PredictPk<MODEL, D> PK;
     constexpr int SD = RC::SD;
-    const int g = A.s.g0 + blockIdx.x, lane = threadIdx.x;
-    const int64_t l = (int64_t)g * WAVE + lane;
-    const bool has = l < A.s.n_lanes;
-    const int ns = has ? A.s.lane_ns[l] : 0;
-    const int64_t w0 = has ? A.want_off[l] : 0;
-    int64_t cur = has ? A.want_off[l + 1] - 1 : -1;            // the lane's wanted steps ascend: the walk takes them from the end
+    const RecLane L = rec_lane(A.s);
+    const int ns = L.ns;
+    const int64_t w0 = L.has ? A.want_off[L.l] : 0;
+    int64_t cur = L.has ? A.want_off[L.l + 1] - 1 : -1;        // the lane's wanted steps ascend: the walk takes them from the end
     int next = cur >= w0 ? A.want_step[cur] : -1;
     // the wave stops below its lowest wanted step: nothing under it is asked for
-    int smax = ns, smin = cur >= w0 ? A.want_step[w0] : 0x7fffffff;
+    int smin = cur >= w0 ? A.want_step[w0] : 0x7fffffff;
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        smax = max(smax, __shfl_xor(smax, o, 64));
-        smin = min(smin, __shfl_xor(smin, o, 64));
-    }
-    smax = __builtin_amdgcn_readfirstlane(smax);
+    for (int o = 32; o > 0; o >>= 1) smin = min(smin, __shfl_xor(smin, o, 64));
     smin = __builtin_amdgcn_readfirstlane(smin);
-    const int64_t goff = A.s.rec_off[g] - A.s.rec_base;
-    const double* base = A.s.rec + goff + lane;
-    const double* sbase = A.s.side + goff / RC::R * PK::SW + lane;
     double r[SD], N[SD][SD];
 #pragma unroll
     for (int a = 0; a < SD; a++) {
@@ -44,20 +35,18 @@ __global__ __launch_bounds__(WAVE) void predict_walk_kernel(const PredictArgs A)
 #pragma unroll
         for (int b = 0; b < SD; b++) N[a][b] = 0.0;
     }
-    for (int s = smax - 1; s >= smin; s--) {
+    for (int s = L.smax - 1; s >= smin; s--) {
         if (s >= ns) continue;
-        const double* rp = base + (int64_t)s * RC::R * WAVE;
+        const RecRow rec = L.row<RC::R>(s);
         if (s == next) {
-            const double* sp = sbase + (int64_t)s * PK::SW * WAVE;
             double* pp = A.pk + (cur - A.slot0);
-            predict_packet_row<MODEL, D, SD>([&](int k) -> double { return rp[(int64_t)k * WAVE]; },
-                                             [&](int k) -> double { return sp[(int64_t)k * WAVE]; }, r, N, s == ns - 1,
+            predict_packet_row<MODEL, D, SD>(rec, rec_side_row<RC::R, PK::SW>(A.s.rc, L.goff, L.lane, s), r, N, s == ns - 1,
                                              [&](int k) -> double& { return pp[(int64_t)k * A.pk_stride]; });
             cur--;
             next = cur >= w0 ? A.want_step[cur] : -1;
         }
         double am[SD], V[SD][SD];
-        smooth_back_row<MODEL, D, SD>(r, N, s == ns - 1, [&](int k) -> double { return rp[(int64_t)k * WAVE]; }, am, V);
+        smooth_back_row<MODEL, D, SD>(r, N, s == ns - 1, rec, am, V);
     }
 }
 
@@ -100,9 +89,9 @@ int predict_side_doubles(int model, int d) {
 }
 
 hipError_t launch_predict_walk(const PredictArgs& a, hipStream_t s) {
-    if (a.s.n_groups == 0) return hipSuccess;
+    if (a.s.rc.n_groups == 0) return hipSuccess;
 #define SSDE_PW(MODEL, D) \
-    if (a.s.model == MODEL && a.s.d == D) { hipLaunchKernelGGL((predict_walk_kernel<MODEL, D>), dim3(a.s.n_groups), dim3(WAVE), 0, s, a); return hipGetLastError(); }
+    if (a.s.model == MODEL && a.s.d == D) { hipLaunchKernelGGL((predict_walk_kernel<MODEL, D>), dim3(a.s.rc.n_groups), dim3(WAVE), 0, s, a); return hipGetLastError(); }
     SSDE_PALL(SSDE_PW)
 #undef SSDE_PW
     return hipErrorInvalidValue;

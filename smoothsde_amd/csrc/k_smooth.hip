@@ -16,16 +16,7 @@ template <int MODEL, int D>
 __global__ __launch_bounds__(WAVE) void smooth_back_kernel(const SmoothArgs A) {
     typedef SmoothRec<MODEL, D> RC;
     constexpr int SD = RC::SD;
-    const int g = A.g0 + blockIdx.x, lane = threadIdx.x;
-    const int64_t l = (int64_t)g * WAVE + lane;
-    const bool has = l < A.n_lanes;
-    const int ns = has ? A.lane_ns[l] : 0;
-    const int64_t row0 = has ? A.lane_row0[l] : 0;
-    int smax = ns;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) smax = max(smax, __shfl_xor(smax, o, 64));
-    smax = __builtin_amdgcn_readfirstlane(smax);
-    const double* base = A.rec + (A.rec_off[g] - A.rec_base) + lane;
+    const RecLane L = rec_lane(A);
     double r[SD], N[SD][SD];
 #pragma unroll
     for (int a = 0; a < SD; a++) {
@@ -34,12 +25,12 @@ __global__ __launch_bounds__(WAVE) void smooth_back_kernel(const SmoothArgs A) {
         for (int b = 0; b < SD; b++) N[a][b] = 0.0;
     }
     const int64_t n = A.n_out;
-    for (int s = smax - 1; s >= 0; s--) {
-        if (s >= ns) continue;
-        const double* rp = base + (int64_t)s * RC::R * WAVE;
+    for (int s = L.smax - 1; s >= 0; s--) {
+        if (s >= L.ns) continue;
+        const RecRow rec = L.row<RC::R>(s);
         double am[SD], V[SD][SD];
-        smooth_back_row<MODEL, D, SD>(r, N, s == ns - 1, [&](int k) -> double { return rp[(int64_t)k * WAVE]; }, am, V);
-        const int64_t row = row0 + 1 + s;
+        smooth_back_row<MODEL, D, SD>(r, N, s == L.ns - 1, rec, am, V);
+        const int64_t row = L.row0 + 1 + s;
         if (A.am) {
 #pragma unroll
             for (int c = 0; c < SD; c++) A.am[row + (int64_t)c * n] = am[c];
@@ -52,7 +43,7 @@ __global__ __launch_bounds__(WAVE) void smooth_back_kernel(const SmoothArgs A) {
         }
         if (A.em) {
 #pragma unroll
-            for (int i = 0; i < D; i++) A.em[row + (int64_t)i * n] = rp[(int64_t)(RC::E + i) * WAVE];
+            for (int i = 0; i < D; i++) A.em[row + (int64_t)i * n] = rec(RC::E + i);
         }
     }
 }
@@ -65,12 +56,12 @@ __global__ __launch_bounds__(WAVE) void smooth_tv_record_kernel(const TvArgs T, 
     typedef DenseDims<MODEL, D> DM;
     typedef SmoothRec<MODEL, D> RC;
     constexpr int SD = DM::SD, Q = DM::Q;
-    const int g = A.g0 + blockIdx.x, lane = threadIdx.x;
+    const int g = A.rc.g0 + blockIdx.x, lane = threadIdx.x;
     const int64_t trk = (int64_t)g * WAVE + lane;
     if (trk >= T.n_tracks) return;
     const int ns = T.trk_ns[trk];
     const int64_t row0 = T.trk_row0[trk];
-    double* base = A.rec + (A.rec_off[g] - A.rec_base) + lane;
+    const int64_t goff = rec_group(A.rc, g);
     DenseLane<MODEL, D, 0> S;
     double a0[SD];
     for (int c = 0; c < SD; c++) a0[c] = T.a0[trk * SD + c];
@@ -97,20 +88,16 @@ __global__ __launch_bounds__(WAVE) void smooth_tv_record_kernel(const TvArgs T, 
             for (int jj = 0; jj < Q; jj++) par[jj].v += (j == jj) ? t : 0.0;
         }
         const bool na = is_na(y[0], T.any_nan);
-        double* rp = base + (int64_t)s * RC::R * WAVE;
-        const bool upd = smooth_record_row<MODEL, D>(S, par, H, dt, y, na, [&](int k) -> double& { return rp[(int64_t)k * WAVE]; });
-        if (A.side) {                                                            // ssde_predict: the row's linear predictors and interval
-            constexpr int SW = PredictPk<MODEL, D>::SW;
-            double* sp = A.side + (A.rec_off[g] - A.rec_base) / RC::R * SW + (int64_t)s * SW * WAVE + lane;
-            predict_side_row<MODEL, D>(par, dt, na, upd, [&](int k) -> double& { return sp[(int64_t)k * WAVE]; });
-        }
+        const bool upd = smooth_record_row<MODEL, D>(S, par, H, dt, y, na, rec_row<RC::R>(A.rc, goff, lane, s));
+        if (A.rc.side)                                                           // ssde_predict: the row's linear predictors and interval
+            predict_side_row<MODEL, D>(par, dt, na, upd, rec_side_row<RC::R, PredictPk<MODEL, D>::SW>(A.rc, goff, lane, s));
         dense_step<MODEL, D, 0>(S, par, H, dt, y, na);
     }
 }
 #endif
 
 #define SSDE_SB(MODEL, D) \
-    if (a.model == MODEL && a.d == D) { hipLaunchKernelGGL((smooth_back_kernel<MODEL, D>), dim3(a.n_groups), dim3(WAVE), 0, s, a); return hipGetLastError(); }
+    if (a.model == MODEL && a.d == D) { hipLaunchKernelGGL((smooth_back_kernel<MODEL, D>), dim3(a.rc.n_groups), dim3(WAVE), 0, s, a); return hipGetLastError(); }
 #define SSDE_SR(MODEL, D) if (model == MODEL && d == D) return SmoothRec<MODEL, D>::R;
 
 #ifndef SSDE_SMOOTH_WIDE_TU
@@ -125,7 +112,7 @@ int smooth_rec_doubles(int model, int d) {
 }
 
 hipError_t launch_smooth_back(const SmoothArgs& a, hipStream_t s) {
-    if (a.n_groups == 0) return hipSuccess;
+    if (a.rc.n_groups == 0) return hipSuccess;
     SSDE_SB(M_CTCRW, 1) SSDE_SB(M_CTCRW, 2) SSDE_SB(M_CTCRW, 3) SSDE_SB(M_CTCRW, 4)
     SSDE_SB(M_OU_SSM, 1) SSDE_SB(M_OU_SSM, 2) SSDE_SB(M_OU_SSM, 3) SSDE_SB(M_OU_SSM, 4)
     SSDE_SB(M_BM_SSM, 1) SSDE_SB(M_BM_SSM, 2) SSDE_SB(M_BM_SSM, 3) SSDE_SB(M_BM_SSM, 4)
@@ -133,9 +120,9 @@ hipError_t launch_smooth_back(const SmoothArgs& a, hipStream_t s) {
 }
 
 hipError_t launch_smooth_tv_record(const TvArgs& t, const SmoothArgs& a, hipStream_t s) {
-    if (a.n_groups == 0) return hipSuccess;
+    if (a.rc.n_groups == 0) return hipSuccess;
 #define SSDE_TR(MODEL, D) \
-    if (a.model == MODEL && a.d == D) { hipLaunchKernelGGL((smooth_tv_record_kernel<MODEL, D>), dim3(a.n_groups), dim3(WAVE), 0, s, t, a); return hipGetLastError(); }
+    if (a.model == MODEL && a.d == D) { hipLaunchKernelGGL((smooth_tv_record_kernel<MODEL, D>), dim3(a.rc.n_groups), dim3(WAVE), 0, s, t, a); return hipGetLastError(); }
     SSDE_TR(M_CTCRW, 1) SSDE_TR(M_CTCRW, 2) SSDE_TR(M_OU_SSM, 1) SSDE_TR(M_OU_SSM, 2) SSDE_TR(M_BM_SSM, 1) SSDE_TR(M_BM_SSM, 2)
 #undef SSDE_TR
     return hipErrorInvalidValue;

@@ -21,10 +21,12 @@
 
 #include "ssde_gain_feed.hpp"
 #include "ssde_math.hpp"
+#include "ssde_records.hpp"
 
 namespace ssde {
 
 constexpr int WAVE = 64;
+static_assert(WAVE == REC_WAVE, "the records' groups are waves");
 constexpr int WG_WAVES = 4;       // waves per workgroup of the register Kalman kernels: the four waves of a
                                  // workgroup land on the four SIMDs of one CU, which is what balances the SIMDs
                                  // (single-wave workgroups were observed to be packed unevenly); the waves are
@@ -523,12 +525,7 @@ struct DenseArgs {
     int64_t n;
     double last_dt;              // dtimes(n-1), see IngestArgs
     PpDrift pp;                  // pp.nb > 0: the tiles hold covariates, the slots' columns come out of the blocks' tables (REPORT of such a handle)
-    // the smoother's forward records (ssde_smooth, k_smooth.hip): srec != NULL runs groups [g0, g0 + srec_groups) in record mode
-    double* srec;                // group g's records at srec + srec_off[g] - srec_base
-    const int64_t* srec_off;     // [n_groups] in doubles, over all groups
-    int64_t srec_base;           // srec_off[g0]
-    int g0, srec_groups;
-    double* sside;               // ssde_predict: the rows' side rows (SmoothArgs.side), or NULL
+    RecChunk rc;                 // the smoother's forward records (ssde_records.hpp): rc.rec != NULL runs the chunk's groups in record mode
 };
 hipError_t launch_dense(const DenseArgs& a, bool want_grad, hipStream_t s);
 
@@ -593,14 +590,11 @@ struct TvArgs {
 hipError_t launch_tv_weights(const TvArgs& a, hipStream_t s);
 
 // ---- fixed-interval smoother (k_smooth.hip, ssde_smooth.hpp) ----------------------------------------
-// Records of SmoothRec<MODEL, D>::R doubles per state row, one group (64 lanes = tracks) after another; double k of step s of a lane at
-// rec + (rec_off[g] - rec_base) + (s * R + k) * 64 + lane.  Outputs in the long (possibly lattice-padded) layout of n_out rows.
+// The chunk of records `rc` (layout: ssde_records.hpp) and the lanes that wrote them.  Outputs in the long (possibly lattice-padded)
+// layout of n_out rows.
 struct SmoothArgs {
     int model, d;
-    double* rec;
-    const int64_t* rec_off;      // [n_groups]
-    int64_t rec_base;
-    int g0, n_groups;            // this chunk's groups
+    RecChunk rc;
     const int64_t* lane_row0;    // [groups * 64]: the lane's track's first row (its state rows follow)
     const int32_t* lane_ns;      // [groups * 64]: state rows of the lane's track (rows - 1)
     int64_t n_lanes;
@@ -608,10 +602,6 @@ struct SmoothArgs {
     double* Vm;                  // [n_out x sdim x sdim] or NULL
     double* em;                  // [n_out x d] or NULL
     int64_t n_out;
-    // ssde_predict (ssde_predict.hpp): the record pass also writes every state row's linear predictors and interval, Q + 1 doubles in the
-    // records' layout with a row width of its own: double k of step s at side + (rec_off[g] - rec_base) / R * (Q + 1) + (s * (Q + 1) + k) * 64
-    // + lane.  NULL (ssde_smooth, ssde_smooth_draws): nothing is written.
-    double* side;
 };
 int smooth_rec_doubles(int model, int d);
 hipError_t launch_smooth_back(const SmoothArgs& a, hipStream_t s);

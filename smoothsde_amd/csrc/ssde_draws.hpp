@@ -30,6 +30,15 @@ struct DrawNext {
     double a[SD], Lp[SD][SD], id[SD];
 };
 
+// before the track's last row: nothing is handed over (draw_factor_row does not read it when tail)
+template <int SD>
+SSDE_HD void draw_next_init(DrawNext<SD>& nx) {
+    SSDE_DLOOP for (int r = 0; r < SD; r++) {
+        nx.a[r] = 0.0; nx.id[r] = 0.0;
+        SSDE_DLOOP for (int c = 0; c < SD; c++) nx.Lp[r][c] = 0.0;
+    }
+}
+
 // Lower Cholesky factor in state order.  ZERO: a pivot <= 0 gives a zero column (a semidefinite matrix that rounding left slightly
 // negative); otherwise the square root of a negative pivot is NaN and spreads through the factor.
 template <int SD, bool ZERO>

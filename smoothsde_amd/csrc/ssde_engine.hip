@@ -15,6 +15,26 @@ thread_local std::string g_create_error;
 using namespace ssde_engine;
 
 namespace ssde_engine {
+void dense_base_args(const ssde_handle* h, DenseArgs& a) {
+    memset(&a, 0, sizeof(a));
+    a.tv.tiles = h->tiles.p; a.tv.group_off = h->group_off.p; a.tv.group_len = h->group_len.p;
+    a.tv.lane_nsteps = h->lane_nsteps.p; a.tv.a0 = h->a0.p; a.tv.n_groups = h->n_groups; a.tv.C = h->C; a.tv.c_obs = h->c_obs; a.tv.dt_all = h->dt_all;
+    a.model = h->model; a.d = h->d; a.any_nan = h->na_any; a.has_h = h->has_h ? 1 : 0;
+    for (int i = 0; i < 256; i++) a.p0[i] = h->p0_full[i];
+    a.lane_row0 = h->lane_row0.p; a.n = h->n; a.last_dt = h->last_dt;
+}
+
+SlotTable value_slot_table(const ssde_handle* h) {
+    SlotTable st;
+    memset(&st, 0, sizeof(st));
+    st.n_slots = (int)h->slots.size(); st.q = h->q;
+    for (size_t k = 0; k < h->slots.size(); k++) {
+        st.par_j[k] = (int16_t)h->slots[k].par_j; st.col[k] = (int16_t)h->slots[k].col;
+        st.pidx[k] = (int16_t)h->slots[k].pidx; st.is_free[k] = 0;
+    }
+    return st;
+}
+
 int fail(ssde_handle* h, int code, const std::string& msg) {
     if (h) h->err = msg;
     g_create_error = msg;
@@ -152,14 +172,9 @@ int eval_device(ssde_handle* h, const double* par, int order, double* out_dev, h
         int st = push_par(h, par, s, &pdev);
         if (st) return st;
         DenseArgs a;
-        memset(&a, 0, sizeof(a));
-        a.tv.tiles = h->tiles.p; a.tv.group_off = h->group_off.p; a.tv.group_len = h->group_len.p;
-        a.tv.lane_nsteps = h->lane_nsteps.p; a.tv.a0 = h->a0.p; a.tv.n_groups = h->n_groups; a.tv.C = h->C; a.tv.c_obs = h->c_obs; a.tv.dt_all = h->dt_all;
-        a.model = h->model; a.d = h->d; a.any_nan = h->na_any; a.has_h = h->has_h ? 1 : 0;
+        dense_base_args(h, a);
         a.slots = h->slot_table.p; a.par = pdev; a.n_slots = (int)h->slots.size();
-        for (int i = 0; i < 256; i++) a.p0[i] = h->p0_full[i];
         a.n_dirblocks = h->n_dirblocks; a.dirs = h->dirs.p; a.partials = h->partials.p;
-        a.report = nullptr; a.lane_row0 = h->lane_row0.p; a.n = h->n; a.last_dt = h->last_dt;
         if (h->stamps) HIPCHK(h, hipEventRecord(h->ev_k0, s));
         HIPCHK(h, launch_dense(a, order >= 1, s));
         h->last_kernel_id = SSDE_KERNEL_DENSE;
@@ -678,24 +693,13 @@ int ssde_report(ssde_handle* h, const double* par, int32_t n_par_full, double* a
     HIPCHK(h, rep.alloc((size_t)nt * h->sdim));
     HIPCHK(h, hipMemset(rep.p, 0, (size_t)nt * h->sdim * 8));
     HIPCHK(h, pbuf.upload(std::vector<double>(par, par + h->L.n_full)));
-    SlotTable st;
-    memset(&st, 0, sizeof(st));
-    st.n_slots = (int)h->slots.size(); st.q = h->q;
-    for (size_t k = 0; k < h->slots.size(); k++) {
-        st.par_j[k] = (int16_t)h->slots[k].par_j; st.col[k] = (int16_t)h->slots[k].col;
-        st.pidx[k] = (int16_t)h->slots[k].pidx; st.is_free[k] = 0;
-    }
+    const SlotTable st = value_slot_table(h);
     HIPCHK(h, stb.upload(std::vector<SlotTable>(1, st)));
     DenseArgs a;
-    memset(&a, 0, sizeof(a));
-    a.tv.tiles = h->tiles.p; a.tv.group_off = h->group_off.p; a.tv.group_len = h->group_len.p;
-    a.tv.lane_nsteps = h->lane_nsteps.p; a.tv.a0 = h->a0.p; a.tv.n_groups = h->n_groups; a.tv.C = h->C; a.tv.c_obs = h->c_obs; a.tv.dt_all = h->dt_all;
-    a.model = h->model; a.d = h->d; a.any_nan = h->na_any; a.has_h = h->has_h ? 1 : 0;
+    dense_base_args(h, a);
     a.slots = stb.p; a.par = pbuf.p; a.n_slots = st.n_slots;
-    for (int i = 0; i < 256; i++) a.p0[i] = h->p0_full[i];
-    a.n_dirblocks = 1; a.dirs = nullptr; a.partials = nullptr;
-    a.pp = h->pp_drift;
-    a.report = rep.p; a.lane_row0 = h->lane_row0.p; a.n = nt; a.last_dt = h->last_dt;
+    a.n_dirblocks = 1; a.pp = h->pp_drift;
+    a.report = rep.p; a.n = nt;
     HIPCHK(h, launch_dense(a, false, 0));
     if (h->n_pad > 0) {                                          // the caller's rows out of the lattice's
         DevBuf<double> rows;

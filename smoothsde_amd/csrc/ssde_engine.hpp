@@ -394,6 +394,10 @@ int push_par(ssde_handle* h, const double* par, hipStream_t s, const double** de
 
 // ---- lane = gradient direction path (ssde_engine_tv.hip) ------------------------------------------------------------
 void tv_base_args(const ssde_handle* h, TvArgs& a);
+// the general kernel's arguments a handle fixes (tiles, model, P0, rows: everything but slots, parameters, directions and outputs),
+// and the handle's slots as a value-only table (ssde_engine.hip)
+void dense_base_args(const ssde_handle* h, DenseArgs& a);
+SlotTable value_slot_table(const ssde_handle* h);
 int build_tv(const ssde_desc* d, ssde_handle* h, const std::vector<int64_t>& starts, bool on_dev);
 int tv_plan(ssde_handle* h, double hobs, hipStream_t s);
 int eval_tv(ssde_handle* h, const double* par, int order, double* out_dev, hipStream_t s);

@@ -10,40 +10,52 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <functional>
 #include <limits>
-#include <numeric>
+#include <tuple>
 
 #include "ssde_engine.hpp"
 #include "ssde_predict.hpp"
+#include "ssde_smooth_plan.hpp"
 
 using namespace ssde_engine;
+using namespace ssde_plan;
 
 namespace {
 
-struct SmoothBufs {
-    std::vector<DevBuf<double>*> d;
-    std::vector<DevBuf<int64_t>*> i;
-    ~SmoothBufs() { for (auto* b : d) b->release(); for (auto* b : i) b->release(); }
+// releases a call's buffers on every way out
+template <class... B>
+struct Release {
+    std::tuple<B&...> bufs;
+    explicit Release(B&... b) : bufs(b...) {}
+    ~Release() { std::apply([](auto&... b) { (b.release(), ...); }, bufs); }
 };
 
-// chunk the groups [0, G) so that each chunk's records fit `budget` doubles (at least one group per chunk)
-std::vector<int> chunk_groups(const std::vector<int64_t>& goff, int64_t budget) {
-    const int G = (int)goff.size() - 1;
-    std::vector<int> cut(1, 0);
-    int g0 = 0;
-    for (int g = 0; g < G; g++)
-        if (g > g0 && goff[g + 1] - goff[g0] > budget) { cut.push_back(g); g0 = g; }
-    cut.push_back(G);
-    return cut;
+// what the entry points check alike (the strings are part of the interface)
+int refuse(ssde_handle* h, int code, const std::string& msg) { h->err = msg; return code; }      // (the handle's message only)
+int check_par_len(ssde_handle* h, int32_t n_par_full) {
+    return n_par_full == h->L.n_full ? SSDE_OK : refuse(h, SSDE_ERR_ARG, "parameter vector has the wrong length");
+}
+int check_kalman(ssde_handle* h) {
+    return is_kalman(h->model) ? SSDE_OK : refuse(h, SSDE_ERR_MODEL, "the smoother serves the Kalman families only (the direct families have no state; ESEAL_SSM no REPORT)");
+}
+int check_not_coupled_wide(ssde_handle* h, const char* who) {
+    return h->d <= 2 ? SSDE_OK : refuse(h, SSDE_ERR_MODEL, std::string(who) + ": a response of three or more columns that runs as ONE coupled filter is not served (uncoupled wide responses run as column pairs and are)");
 }
 
-// The record-producing half of a smoother call, shared by ssde_smooth and ssde_smooth_draws: the parameter vector, the groups' record
-// offsets, the chunk plan under the budget, the record buffer and the forward launch's arguments.  produce(c) fills the buffer with
-// chunk c's records and leaves `s` addressing them.
+// a quarter of the free memory, in doubles: the budget where SSDE_OPT_SMOOTH_BUDGET_MB sets none
+int free_budget(ssde_handle* h, int64_t& budget) {
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
+    budget = (int64_t)(free_b / 4 / 8);
+    return SSDE_OK;
+}
+
+// The record-producing half of a smoother call, shared by the four calls: the parameter vector, the groups' record offsets, the
+// chunk plan under the budget, the record buffer and the forward launch's arguments.  produce(c) fills the buffer with chunk c's
+// records and leaves `s` addressing them.
 struct RecordRun {
     ssde_handle* h = nullptr;
-    bool tv = false;
+    bool tv = false, have_records = false;
     int R = 0;
     int64_t nt = 0, n_lanes = 0, budget = 0;
     int SW = 0;                        // > 0 (set before setup): the record pass also writes side rows of SW doubles (ssde_predict)
@@ -55,9 +67,10 @@ struct RecordRun {
     SmoothArgs s;
     TvArgs ta;
     DenseArgs da;
-    SlotTable stab;
     ~RecordRun() { rec.release(); pbuf.release(); side.release(); offb.release(); stb.release(); }
     size_t n_chunks() const { return cut.size() - 1; }
+    // rows of the layout the kernels write
+    static int64_t rows(const ssde_handle* h) { return (h->path != PATH_TV && h->n_pad > 0) ? h->n_pad : h->n; }
 
     int setup(ssde_handle* h_, const double* par, const char* who) {
         h = h_;
@@ -65,7 +78,7 @@ struct RecordRun {
         R = smooth_rec_doubles(h->model, d);
         if (R <= 0) { h->err = std::string(who) + ": no smoother for this response width"; return SSDE_ERR_MODEL; }
         tv = h->path == PATH_TV;
-        nt = (!tv && h->n_pad > 0) ? h->n_pad : h->n;        // rows of the layout the kernels write
+        nt = rows(h);
         HIPCHK(h, pbuf.upload(std::vector<double>(par, par + h->L.n_full)));
 
         // the groups' record offsets (doubles; 64-bit throughout)
@@ -89,11 +102,7 @@ struct RecordRun {
         for (int g = 0; g < G; g++) goff[g + 1] = goff[g] + (int64_t)glen[g] * R * WAVE;
         HIPCHK(h, offb.upload(goff));
         if (h->smooth_budget_mb > 0) budget = h->smooth_budget_mb * (int64_t)(1 << 20) / 8;
-        else {
-            size_t free_b = 0, total_b = 0;
-            HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
-            budget = (int64_t)(free_b / 4 / 8);
-        }
+        else if (int st = free_budget(h, budget)) return st;
         if (SW > 0) budget = budget / (R + SW) * R;                // the side rows share the budget
         cut = chunk_groups(goff, budget);
         int64_t biggest = 0;
@@ -102,8 +111,8 @@ struct RecordRun {
         if (SW > 0) HIPCHK(h, side.alloc((size_t)std::max<int64_t>(biggest / R * SW, 1)));
 
         memset(&s, 0, sizeof(s));
-        s.model = h->model; s.d = d; s.rec = rec.p; s.rec_off = offb.p;
-        s.n_out = nt; s.n_lanes = n_lanes; s.side = side.p;
+        s.model = h->model; s.d = d; s.rc.rec = rec.p; s.rc.side = side.p; s.rc.rec_off = offb.p;
+        s.n_out = nt; s.n_lanes = n_lanes;
         if (tv) {
             tv_base_args(h, ta);
             ta.par = pbuf.p;
@@ -111,38 +120,32 @@ struct RecordRun {
             ta.h = sig * sig;
             s.lane_row0 = h->tv_row0.p; s.lane_ns = h->tv_ns.p;
         } else {
-            memset(&stab, 0, sizeof(stab));
-            stab.n_slots = (int)h->slots.size(); stab.q = h->q;
-            for (size_t k = 0; k < h->slots.size(); k++) {
-                stab.par_j[k] = (int16_t)h->slots[k].par_j; stab.col[k] = (int16_t)h->slots[k].col;
-                stab.pidx[k] = (int16_t)h->slots[k].pidx; stab.is_free[k] = 0;
-            }
+            const SlotTable stab = value_slot_table(h);
             HIPCHK(h, stb.upload(std::vector<SlotTable>(1, stab)));
-            memset(&da, 0, sizeof(da));
-            da.tv.tiles = h->tiles.p; da.tv.group_off = h->group_off.p; da.tv.group_len = h->group_len.p;
-            da.tv.lane_nsteps = h->lane_nsteps.p; da.tv.a0 = h->a0.p; da.tv.n_groups = h->n_groups; da.tv.C = h->C; da.tv.c_obs = h->c_obs;
-            da.tv.dt_all = h->dt_all;
-            da.model = h->model; da.d = d; da.any_nan = h->na_any; da.has_h = h->has_h ? 1 : 0;
+            dense_base_args(h, da);
             da.slots = stb.p; da.par = pbuf.p; da.n_slots = stab.n_slots;
-            for (int i = 0; i < 256; i++) da.p0[i] = h->p0_full[i];
-            da.n_dirblocks = 1; da.pp = h->pp_drift;
-            da.lane_row0 = h->lane_row0.p; da.n = nt; da.last_dt = h->last_dt;
-            da.srec = rec.p; da.srec_off = offb.p; da.sside = side.p;
+            da.n_dirblocks = 1; da.pp = h->pp_drift; da.n = nt;
             s.lane_row0 = h->lane_row0.p; s.lane_ns = h->lane_nsteps.p;
         }
         return SSDE_OK;
     }
 
     int produce(size_t c) {
-        const int g0 = cut[c], ng = cut[c + 1] - cut[c];
-        s.g0 = g0; s.n_groups = ng; s.rec_base = goff[g0];
+        s.rc.g0 = cut[c]; s.rc.n_groups = cut[c + 1] - cut[c]; s.rc.rec_base = goff[cut[c]];
         if (tv) {
             HIPCHK(h, launch_smooth_tv_record(ta, s, 0));
         } else {
-            da.g0 = g0; da.srec_groups = ng; da.srec_base = goff[g0];
+            da.rc = s.rc;
             HIPCHK(h, launch_dense(da, false, 0));
         }
         return SSDE_OK;
+    }
+
+    // chunk c's records for one batch of a call that draws: produced once when there is one chunk, per batch otherwise
+    int produce_for_batch(size_t c) {
+        if (have_records && n_chunks() == 1) return SSDE_OK;
+        have_records = true;
+        return produce(c);
     }
 };
 
@@ -150,16 +153,15 @@ int smooth_single(ssde_handle* h, const double* par, double* a_smooth, double* P
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(0));
     const int sd = h->sdim, d = h->d;
-    if (smooth_rec_doubles(h->model, d) <= 0) { h->err = "ssde_smooth: no smoother for this response width"; return SSDE_ERR_MODEL; }
-    const int64_t nt = (h->path != PATH_TV && h->n_pad > 0) ? h->n_pad : h->n;
+    const int64_t nt = RecordRun::rows(h);
     DevBuf<double> am, Vm, em;
-    SmoothBufs guard{{&am, &Vm, &em}, {}};
-    // the outputs, NaN (all bits set) where no state row writes
+    Release guard(am, Vm, em);
+    // the outputs, NaN (all bits set) where no state row writes; before the run's set-up, whose default budget is what they leave free
     if (a_smooth) { HIPCHK(h, am.alloc((size_t)nt * sd)); HIPCHK(h, hipMemset(am.p, 0xff, (size_t)nt * sd * 8)); }
     if (P_smooth) { HIPCHK(h, Vm.alloc((size_t)nt * sd * sd)); HIPCHK(h, hipMemset(Vm.p, 0xff, (size_t)nt * sd * sd * 8)); }
     if (resid) { HIPCHK(h, em.alloc((size_t)nt * d)); HIPCHK(h, hipMemset(em.p, 0xff, (size_t)nt * d * 8)); }
     RecordRun run;
-    { int st = run.setup(h, par, "ssde_smooth"); if (st) return st; }
+    if (int st = run.setup(h, par, "ssde_smooth")) return st;
     run.s.am = am.p; run.s.Vm = Vm.p; run.s.em = em.p;
     for (size_t c = 0; c < run.n_chunks(); c++) {
         int st = run.produce(c);
@@ -171,7 +173,7 @@ int smooth_single(ssde_handle* h, const double* par, double* a_smooth, double* P
         if (!dst) return SSDE_OK;
         if (nt != h->n) {
             DevBuf<double> rows;
-            SmoothBufs g2{{&rows}, {}};
+            Release g2(rows);
             HIPCHK(h, rows.alloc((size_t)h->n * ncol));
             HIPCHK(h, launch_lattice_gather(h->pad_row.p, src.p, h->n, nt, ncol, rows.p, 0));
             HIPCHK(h, hipMemcpy(dst, rows.p, (size_t)h->n * ncol * 8, hipMemcpyDeviceToHost));
@@ -195,44 +197,34 @@ int draws_single(ssde_handle* h, const double* par, uint64_t seed, int64_t draw0
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(0));
     const int sd = h->sdim;
-    if (h->d > 2) {
-        h->err = "ssde_smooth_draws: a response of three or more columns that runs as ONE coupled filter is not served (uncoupled wide responses run as column pairs and are)";
-        return SSDE_ERR_MODEL;
-    }
+    if (int st = check_not_coupled_wide(h, "ssde_smooth_draws")) return st;
     RecordRun run;
-    { int st = run.setup(h, par, "ssde_smooth_draws"); if (st) return st; }
+    if (int st = run.setup(h, par, "ssde_smooth_draws")) return st;
     const int64_t nt = run.nt, n = h->n;
     if ((int64_t)h->lane_seg.n < run.n_lanes) { h->err = "ssde_smooth_draws: the handle holds no track ordinals for its lanes"; return SSDE_ERR_ARG; }
     DevBuf<double> batch, rows;
-    SmoothBufs guard{{&batch, &rows}, {}};
-    // Draws per batch: what fits beside the records (the budget again; a draw always goes).  A device output on the caller's own rows is
-    // written in place; otherwise a batch is staged (and, on a lattice-padded handle, gathered to the caller's rows) before it leaves.
+    Release guard(batch, rows);
+    // Draws per batch: what fits beside the records (the free memory asked for again; a draw always goes).  A device output on the
+    // caller's own rows is written in place; otherwise a batch is staged (and, on a lattice-padded handle, gathered to the caller's
+    // rows) before it leaves.
     const bool in_place = dev_out && nt == n;
-    const int64_t per_draw = std::max<int64_t>(nt * sd, 1);
     int64_t budget = run.budget;
-    if (h->smooth_budget_mb <= 0) {
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
-        budget = (int64_t)(free_b / 4 / 8);
-    }
-    const int64_t nb_max = std::min<int64_t>(std::max<int64_t>(budget / per_draw, 1), (int64_t)DRAW_CH << 15);
-    const int nb_cap = (int)std::min<int64_t>(nb_max, n_draws);
+    if (h->smooth_budget_mb <= 0) if (int st = free_budget(h, budget)) return st;
+    const int nb_cap = batch_cap(budget, nt * sd, 1, DRAW_CH, n_draws);
     if (!in_place) HIPCHK(h, batch.alloc((size_t)nt * sd * nb_cap));
     if (nt != n) HIPCHK(h, rows.alloc((size_t)n * sd * nb_cap));
     DrawArgs a;
     memset(&a, 0, sizeof(a));
     a.lane_trk = h->lane_seg.p; a.track0 = track0; a.seed = seed; a.col0 = col0;
     a.draw_stride = in_place ? stride : nt * sd;
-    bool have_records = false;
     for (int k0 = 0; k0 < n_draws; k0 += nb_cap) {
         const int nb = std::min(nb_cap, n_draws - k0);
-        double* dst = in_place ? draws + (size_t)k0 * stride : batch.p;
+        a.out = in_place ? draws + (size_t)k0 * stride : batch.p;
         // NaN (all bits set) where no state row writes
-        if (nt * sd > 0) HIPCHK(h, hipMemset2D(dst, (size_t)a.draw_stride * 8, 0xff, (size_t)nt * sd * 8, (size_t)nb));
-        a.draw0 = (uint32_t)(draw0 + k0); a.n_draws = nb; a.out = dst;
+        if (nt * sd > 0) HIPCHK(h, hipMemset2D(a.out, (size_t)a.draw_stride * 8, 0xff, (size_t)nt * sd * 8, (size_t)nb));
+        a.draw0 = (uint32_t)(draw0 + k0); a.n_draws = nb;
         for (size_t c = 0; c < run.n_chunks(); c++) {
-            if (!have_records || run.n_chunks() > 1) { int st = run.produce(c); if (st) return st; }
-            have_records = true;
+            if (int st = run.produce_for_batch(c)) return st;
             a.s = run.s;
             HIPCHK(h, launch_smooth_draws(a, 0));
         }
@@ -251,28 +243,25 @@ int draws_single(ssde_handle* h, const double* par, uint64_t seed, int64_t draw0
 
 // ---- ssde_path_stats ----------------------------------------------------------------------------------------------------------
 // One engine's statistics [n_seg x n_stat x n_draws] into host memory: the draws' walk with the stores replaced by the reduction
-// (k_path_stats.hip).  Records as draws_single produces them: once when there is one chunk, per batch of draws otherwise; a batch is
-// what one launch's second grid dimension takes.  weight: the engine's own rows (host) or NULL; track0: the ID segments of the shards
-// before this one (the deviates' counter only: the statistics are placed by the engine's own ordinals).
+// (k_path_stats.hip), batched as draws_single's; a batch is what one launch's second grid dimension takes.  weight: the engine's own
+// rows (host) or NULL; track0: the ID segments of the shards before this one (the deviates' counter only: the statistics are placed
+// by the engine's own ordinals).
 int path_single(ssde_handle* h, const double* par, uint64_t seed, int64_t draw0, int n_draws, const double* regions, int n_regions,
                 const double* weight, double* stats, int64_t track0) {
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(0));
     RecordRun run;
-    { int st = run.setup(h, par, "ssde_path_stats"); if (st) return st; }
+    if (int st = run.setup(h, par, "ssde_path_stats")) return st;
     const int64_t nt = run.nt, n = h->n, n_trk = h->n_seg;
     const int n_stat = 2 + n_regions;
     if ((int64_t)h->lane_seg.n < run.n_lanes) { h->err = "ssde_path_stats: the handle holds no track ordinals for its lanes"; return SSDE_ERR_ARG; }
     if (n_trk == 0) return SSDE_OK;
     DevBuf<double> sb, wb;
     DevBuf<int64_t> map;
-    SmoothBufs guard{{&sb, &wb}, {&map}};
-    // draws per batch: what one launch's second grid dimension takes, and what fits the budget beside the records (whole waves of
-    // DRAW_CH draws; one wave's draws always go)
+    Release guard(sb, wb, map);
+    // draws per batch: what fits the run's budget beside the records, in whole waves of DRAW_CH draws (one wave's draws always go)
     const size_t per_draw = (size_t)n_trk * n_stat;
-    int64_t nb_max = std::min<int64_t>(std::max<int64_t>(run.budget / (int64_t)per_draw, DRAW_CH), (int64_t)DRAW_CH << 15);
-    nb_max -= nb_max % DRAW_CH;
-    const int nb_cap = (int)std::min<int64_t>(nb_max, n_draws);
+    const int nb_cap = batch_cap(run.budget, (int64_t)per_draw, DRAW_CH, DRAW_CH, n_draws);
     HIPCHK(h, sb.alloc(per_draw * nb_cap));
     if (weight && n > 0) HIPCHK(h, wb.upload(std::vector<double>(weight, weight + n)));
     PathArgs a;
@@ -286,14 +275,12 @@ int path_single(ssde_handle* h, const double* par, uint64_t seed, int64_t draw0,
     a.weight = (weight && n > 0) ? wb.p : nullptr;
     a.stats = sb.p; a.n_trk = n_trk; a.n_regions = n_regions;
     for (int k = 0; k < 4 * n_regions; k++) a.regions[k] = regions[k];
-    bool have_records = false;
     for (int k0 = 0; k0 < n_draws; k0 += nb_cap) {
         const int nb = std::min(nb_cap, n_draws - k0);
         HIPCHK(h, hipMemset(sb.p, 0xff, per_draw * nb * 8));            // NaN (all bits set) where no lane writes
         a.d.draw0 = (uint32_t)(draw0 + k0); a.d.n_draws = nb;
         for (size_t c = 0; c < run.n_chunks(); c++) {
-            if (!have_records || run.n_chunks() > 1) { int st = run.produce(c); if (st) return st; }
-            have_records = true;
+            if (int st = run.produce_for_batch(c)) return st;
             a.d.s = run.s;
             HIPCHK(h, launch_path_stats(a, 0));
         }
@@ -324,104 +311,48 @@ int path_sharded(ssde_handle* parent, const double* par, uint64_t seed, int64_t 
 }
 
 // ---- ssde_predict -------------------------------------------------------------------------------------------------------------
-// One engine's queries.  Planning on the host: every query goes to the state row (lane, step) that starts its interval in the
-// handle's resident layout, plus a residual offset; the wanted steps become a list per lane (slots) and the queries are ordered by
-// slot.  Then, chunk by chunk: the record pass with side rows, the walk that fills the chunk's packets, the query kernel.
+// One engine's queries.  plan_queries (ssde_smooth_plan.hpp) places them on the host; then, chunk by chunk: the record pass with side
+// rows, the walk that fills the chunk's packets, the query kernel.
 int predict_single(ssde_handle* h, const double* par, const int64_t* q_row, const double* q_off, int64_t nq, double* a_pred,
                    double* P_pred) {
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(0));
     const int sd = h->sdim;
-    if (h->d > 2) {
-        h->err = "ssde_predict: a response of three or more columns that runs as ONE coupled filter is not served (uncoupled wide responses run as column pairs and are)";
-        return SSDE_ERR_MODEL;
-    }
+    if (int st = check_not_coupled_wide(h, "ssde_predict")) return st;
     RecordRun run;
     run.SW = predict_side_doubles(h->model, h->d);
     const int PKD = predict_packet_doubles(h->model, h->d);
     if (run.SW <= 0 || PKD <= 0) { h->err = "ssde_predict: no kernels for this model and width"; return SSDE_ERR_MODEL; }
-    { int st = run.setup(h, par, "ssde_predict"); if (st) return st; }
+    if (int st = run.setup(h, par, "ssde_predict")) return st;
     const int64_t nl = run.n_lanes, n = h->n;
-    const bool lattice = run.nt != n;
 
-    // the lanes' tracks in the resident layout: first row and state rows, sorted by first row
-    std::vector<int64_t> row0((size_t)nl);
+    // the lanes' tracks in the resident layout, and on a lattice-padded handle the lattice row of every caller row
+    std::vector<int64_t> row0((size_t)nl), prow;
     std::vector<int32_t> lns((size_t)nl);
     if (nl) {
         HIPCHK(h, hipMemcpy(row0.data(), run.s.lane_row0, (size_t)nl * 8, hipMemcpyDeviceToHost));
         HIPCHK(h, hipMemcpy(lns.data(), run.s.lane_ns, (size_t)nl * 4, hipMemcpyDeviceToHost));
     }
-    std::vector<int64_t> by_row;
-    for (int64_t l = 0; l < nl; l++) if (lns[l] > 0) by_row.push_back(l);
-    std::sort(by_row.begin(), by_row.end(), [&](int64_t a, int64_t b) { return row0[a] < row0[b]; });
-    std::vector<int64_t> start(by_row.size());
-    for (size_t k = 0; k < by_row.size(); k++) start[k] = row0[by_row[k]];
-    std::vector<int64_t> prow;
-    if (lattice) {
+    if (run.nt != n) {
         prow.resize((size_t)n);
         HIPCHK(h, hipMemcpy(prow.data(), h->pad_row.p, (size_t)n * 8, hipMemcpyDeviceToHost));
     }
-
-    // queries -> (lane, step, residual); key = lane * 2^31 + step orders them by slot
-    std::vector<int64_t> key((size_t)nq, -1);
-    std::vector<double> res((size_t)nq, 0.0);
-    for (int64_t k = 0; k < nq; k++) {
-        const int64_t p = lattice ? prow[q_row[k]] : q_row[k];
-        const size_t t = std::upper_bound(start.begin(), start.end(), p) - start.begin();
-        if (t == 0) continue;
-        const int64_t l = by_row[t - 1], r0 = row0[l], ns = lns[l];
-        if (p > r0 + ns) continue;                                  // (a one-row track: no lane holds it)
-        int64_t st = p - r0 - 1;
-        if (st < 0) continue;                                       // a track's first row carries no state
-        double off = q_off[k];
-        if (lattice && st < ns - 1) {
-            // a caller's interval may span several lattice steps: the whole steps inside `off` move the row, the rest is the residual
-            const double step = h->pad_step;
-            int64_t w = (int64_t)std::floor(off / step + PREDICT_DT_RTOL);
-            double rest = off - (double)w * step;
-            if (rest < 0.0) rest = 0.0;
-            const int64_t pn = prow[q_row[k] + 1];                  // the caller's next row (same track: row j is not its last)
-            if (p + w > pn || (p + w == pn && rest > PREDICT_DT_RTOL * step)) continue;   // past the next fix: NaN
-            if (p + w == pn) rest = 0.0;
-            st += w; off = rest;
-        }
-        key[k] = (l << 31) | st;
-        res[k] = off;
-    }
-    std::vector<int64_t> order;
-    for (int64_t k = 0; k < nq; k++) if (key[k] >= 0) order.push_back(k);
-    std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return key[a] < key[b]; });
-    const int64_t nv = (int64_t)order.size();
-    std::vector<int64_t> want_off((size_t)nl + 1, 0), q_slot((size_t)nv);
-    std::vector<int32_t> want_step;
-    std::vector<double> off_sorted((size_t)nv);
-    for (int64_t i = 0; i < nv; i++) {
-        const int64_t kk = key[order[i]];
-        if (i == 0 || kk != key[order[i - 1]]) {
-            want_step.push_back((int32_t)(kk & 0x7fffffff));
-            want_off[(size_t)(kk >> 31) + 1]++;
-        }
-        q_slot[i] = (int64_t)want_step.size() - 1;
-        off_sorted[i] = res[order[i]];
-    }
-    for (int64_t l = 0; l < nl; l++) want_off[l + 1] += want_off[l];
+    const QueryPlan P = plan_queries(row0, lns, run.nt != n ? prow.data() : nullptr, h->pad_step, q_row, q_off, nq);
 
     // the outputs, NaN (all bits set) where no query writes
     DevBuf<double> am, Vm, pk, offd;
     DevBuf<int64_t> wo, ord, qs;
     DevBuf<int32_t> ws;
-    struct Guard { DevBuf<int32_t>* w; ~Guard() { w->release(); } } g32{&ws};
-    SmoothBufs guard{{&am, &Vm, &pk, &offd}, {&wo, &ord, &qs}};
+    Release guard(am, Vm, pk, offd, wo, ord, qs, ws);
     HIPCHK(h, am.alloc((size_t)nq * sd)); HIPCHK(h, hipMemset(am.p, 0xff, (size_t)nq * sd * 8));
     if (P_pred) { HIPCHK(h, Vm.alloc((size_t)nq * sd * sd)); HIPCHK(h, hipMemset(Vm.p, 0xff, (size_t)nq * sd * sd * 8)); }
-    if (nv > 0) {
-        HIPCHK(h, wo.upload(want_off)); HIPCHK(h, ws.upload(want_step));
-        HIPCHK(h, ord.upload(order)); HIPCHK(h, qs.upload(q_slot)); HIPCHK(h, offd.upload(off_sorted));
-        // the chunks' slot ranges (a chunk's lanes hold consecutive slots) and the queries of each
+    if (!P.order.empty()) {
+        HIPCHK(h, wo.upload(P.want_off)); HIPCHK(h, ws.upload(P.want_step));
+        HIPCHK(h, ord.upload(P.order)); HIPCHK(h, qs.upload(P.q_slot)); HIPCHK(h, offd.upload(P.off));
         int64_t most = 0;
         for (size_t c = 0; c < run.n_chunks(); c++) {
-            const int64_t l0 = std::min<int64_t>((int64_t)run.cut[c] * WAVE, nl), l1 = std::min<int64_t>((int64_t)run.cut[c + 1] * WAVE, nl);
-            most = std::max(most, want_off[l1] - want_off[l0]);
+            const QueryRange r = chunk_queries(P, run.cut[c], run.cut[c + 1], WAVE);
+            most = std::max(most, r.s1 - r.s0);
         }
         HIPCHK(h, pk.alloc((size_t)most * PKD));
         PredictArgs a;
@@ -429,15 +360,12 @@ int predict_single(ssde_handle* h, const double* par, const int64_t* q_row, cons
         a.want_off = wo.p; a.want_step = ws.p; a.pk = pk.p; a.order = ord.p; a.q_slot = qs.p; a.q_off = offd.p;
         a.n_query = nq; a.a_pred = am.p; a.P_pred = Vm.p;
         for (size_t c = 0; c < run.n_chunks(); c++) {
-            const int64_t l0 = std::min<int64_t>((int64_t)run.cut[c] * WAVE, nl), l1 = std::min<int64_t>((int64_t)run.cut[c + 1] * WAVE, nl);
-            const int64_t s0 = want_off[l0], s1 = want_off[l1];
-            if (s1 == s0) continue;                                 // no query on this chunk's tracks
+            const QueryRange r = chunk_queries(P, run.cut[c], run.cut[c + 1], WAVE);
+            if (r.s1 == r.s0) continue;                             // no query on this chunk's tracks
             int st = run.produce(c);
             if (st) return st;
             a.s = run.s;
-            a.slot0 = s0; a.pk_stride = s1 - s0;
-            a.q0 = std::lower_bound(q_slot.begin(), q_slot.end(), s0) - q_slot.begin();
-            a.q1 = std::lower_bound(q_slot.begin(), q_slot.end(), s1) - q_slot.begin();
+            a.slot0 = r.s0; a.pk_stride = r.s1 - r.s0; a.q0 = r.q0; a.q1 = r.q1;
             HIPCHK(h, launch_predict_walk(a, 0));
             HIPCHK(h, launch_predict_query(a, 0));
         }
@@ -550,13 +478,13 @@ extern "C" {
 int ssde_smooth_draws(ssde_handle* h, const double* par, int32_t n_par_full, uint64_t seed, int64_t draw0, int32_t n_draws,
                       double* draws, uint32_t flags) {
     if (!h || !par || !draws) { if (h) h->err = "ssde_smooth_draws: no parameter vector, or no output"; return SSDE_ERR_ARG; }
-    if (n_par_full != h->L.n_full) { h->err = "parameter vector has the wrong length"; return SSDE_ERR_ARG; }
+    if (int st = check_par_len(h, n_par_full)) return st;
     if (n_draws < 1 || draw0 < 0 || draw0 + (int64_t)n_draws >= ((int64_t)1 << 28)) {
         h->err = "ssde_smooth_draws: n_draws >= 1, draw0 >= 0 and draw0 + n_draws < 2^28 are required";
         return SSDE_ERR_ARG;
     }
     if (flags & ~(uint32_t)SSDE_DRAWS_DEVICE_OUT) { h->err = "ssde_smooth_draws: unknown flag"; return SSDE_ERR_ARG; }
-    if (!is_kalman(h->model)) { h->err = "the smoother serves the Kalman families only (the direct families have no state; ESEAL_SSM no REPORT)"; return SSDE_ERR_MODEL; }
+    if (int st = check_kalman(h)) return st;
     const bool dev_out = (flags & SSDE_DRAWS_DEVICE_OUT) != 0;
     if (!h->shards.empty()) {
         if (dev_out && h->n_track_shards > 1) { h->err = "ssde_smooth_draws: SSDE_DRAWS_DEVICE_OUT needs a single-device handle"; return SSDE_ERR_ARG; }
@@ -568,7 +496,7 @@ int ssde_smooth_draws(ssde_handle* h, const double* par, int32_t n_par_full, uin
 int ssde_path_stats(ssde_handle* h, const double* par, int32_t n_par_full, uint64_t seed, int64_t draw0, int32_t n_draws,
                     const double* regions, int32_t n_regions, const double* weight, double* stats, uint32_t flags) {
     if (!h || !par || !stats) { if (h) h->err = "ssde_path_stats: no parameter vector, or no output"; return SSDE_ERR_ARG; }
-    if (n_par_full != h->L.n_full) { h->err = "parameter vector has the wrong length"; return SSDE_ERR_ARG; }
+    if (int st = check_par_len(h, n_par_full)) return st;
     if (n_draws < 1 || draw0 < 0 || draw0 + (int64_t)n_draws >= ((int64_t)1 << 28)) {
         h->err = "ssde_path_stats: n_draws >= 1, draw0 >= 0 and draw0 + n_draws < 2^28 are required";
         return SSDE_ERR_ARG;
@@ -583,7 +511,7 @@ int ssde_path_stats(ssde_handle* h, const double* par, int32_t n_par_full, uint6
         if (std::isnan(lo) || std::isnan(hi) || lo > hi) { h->err = "ssde_path_stats: a region bound that is NaN, or lo > hi"; return SSDE_ERR_ARG; }
     }
     if (flags != 0) { h->err = "ssde_path_stats: unknown flag"; return SSDE_ERR_ARG; }
-    if (!is_kalman(h->model)) { h->err = "the smoother serves the Kalman families only (the direct families have no state; ESEAL_SSM no REPORT)"; return SSDE_ERR_MODEL; }
+    if (int st = check_kalman(h)) return st;
     if (h->d > 2) {
         h->err = "ssde_path_stats: a response of three or more columns is not served, as column pairs or as one coupled filter (a distance needs the position columns in one lane)";
         return SSDE_ERR_MODEL;
@@ -595,21 +523,21 @@ int ssde_path_stats(ssde_handle* h, const double* par, int32_t n_par_full, uint6
 int ssde_predict(ssde_handle* h, const double* par, int32_t n_par_full, const int64_t* q_row, const double* q_off, int64_t n_query,
                  double* a_pred, double* P_pred) {
     if (!h || !par || !q_row || !q_off || !a_pred) { if (h) h->err = "ssde_predict: no parameter vector, no queries, or no output"; return SSDE_ERR_ARG; }
-    if (n_par_full != h->L.n_full) { h->err = "parameter vector has the wrong length"; return SSDE_ERR_ARG; }
+    if (int st = check_par_len(h, n_par_full)) return st;
     if (n_query < 1) { h->err = "ssde_predict: n_query >= 1 is required"; return SSDE_ERR_ARG; }
     for (int64_t k = 0; k < n_query; k++) {
         if (q_row[k] < 0 || q_row[k] >= h->n) { h->err = "ssde_predict: a query row outside [0, n)"; return SSDE_ERR_ARG; }
         if (!std::isfinite(q_off[k]) || q_off[k] < 0.0) { h->err = "ssde_predict: a query offset that is negative or not finite"; return SSDE_ERR_ARG; }
     }
-    if (!is_kalman(h->model)) { h->err = "the smoother serves the Kalman families only (the direct families have no state; ESEAL_SSM no REPORT)"; return SSDE_ERR_MODEL; }
+    if (int st = check_kalman(h)) return st;
     if (!h->shards.empty()) return predict_sharded(h, par, q_row, q_off, n_query, a_pred, P_pred);
     return predict_single(h, par, q_row, q_off, n_query, a_pred, P_pred);
 }
 
 int ssde_smooth(ssde_handle* h, const double* par, int32_t n_par_full, double* a_smooth, double* P_smooth, double* resid) {
     if (!h || !par || (!a_smooth && !P_smooth && !resid)) { if (h) h->err = "ssde_smooth: no parameter vector, or no output asked for"; return SSDE_ERR_ARG; }
-    if (n_par_full != h->L.n_full) { h->err = "parameter vector has the wrong length"; return SSDE_ERR_ARG; }
-    if (!is_kalman(h->model)) { h->err = "the smoother serves the Kalman families only (the direct families have no state; ESEAL_SSM no REPORT)"; return SSDE_ERR_MODEL; }
+    if (int st = check_par_len(h, n_par_full)) return st;
+    if (int st = check_kalman(h)) return st;
     if (!h->shards.empty()) return smooth_sharded(h, par, a_smooth, P_smooth, resid);
     return smooth_single(h, par, a_smooth, P_smooth, resid);
 }

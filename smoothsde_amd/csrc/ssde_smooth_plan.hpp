@@ -1,0 +1,115 @@
+// ssde_smooth_plan.hpp -- the host-side plans of the calls that consume the smoother's records (ssde_engine_smooth.hip): how the
+// groups are cut into chunks under the budget, how many draws go into one batch, and where every query of ssde_predict lands.
+// Plain C++17, no HIP: the engine uploads and launches what these return, tests/hostsim/hostsim_predict.cpp exports them to
+// tests/test_smooth_plan_host.py.
+#ifndef SSDE_SMOOTH_PLAN_HPP
+#define SSDE_SMOOTH_PLAN_HPP
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <vector>
+
+#include "ssde_predict.hpp"
+
+namespace ssde_plan {
+
+// chunk the groups [0, G) so that each chunk's records fit `budget` doubles (at least one group per chunk); goff: the groups'
+// record offsets, G + 1 of them
+inline std::vector<int> chunk_groups(const std::vector<int64_t>& goff, int64_t budget) {
+    const int G = (int)goff.size() - 1;
+    std::vector<int> cut(1, 0);
+    int g0 = 0;
+    for (int g = 0; g < G; g++)
+        if (g > g0 && goff[g + 1] - goff[g0] > budget) { cut.push_back(g); g0 = g; }
+    cut.push_back(G);
+    return cut;
+}
+
+// Draws per batch: what fits `budget` doubles at per_draw doubles a draw, in whole multiples of `unit` (one unit always goes), at
+// most what one launch's second grid dimension takes (ch draws per wave), and no more than the call asks for.  ssde_smooth_draws
+// takes any number of draws (unit 1), ssde_path_stats whole waves (unit ch).
+inline int batch_cap(int64_t budget, int64_t per_draw, int unit, int ch, int n_draws) {
+    int64_t nb = std::min<int64_t>(std::max<int64_t>(budget / std::max<int64_t>(per_draw, 1), unit), (int64_t)ch << 15);
+    return (int)std::min<int64_t>(nb - nb % unit, n_draws);
+}
+
+// ---- ssde_predict's queries --------------------------------------------------------------------------------------
+// Every query goes to the state row (lane, step) that starts its interval in the handle's resident layout, plus a residual offset.
+// The wanted steps become one ascending list per lane (slots: want_step[want_off[l] .. want_off[l + 1])) and the planned queries
+// are ordered by slot: order[i] is the caller's index of the i-th, q_slot[i] its slot, off[i] its residual.  A query without a state
+// (a track's first row, a one-row track, past the next fix of a lattice handle) is not planned.
+struct QueryPlan {
+    std::vector<int64_t> order, q_slot, want_off;
+    std::vector<int32_t> want_step;
+    std::vector<double> off;
+};
+
+// row0 / ns: the lanes' first row and state rows in the resident layout (any order; ns <= 0: no track); pad_row: the lattice row of
+// every caller row and pad_step the lattice step, or NULL when the rows ARE the caller's
+inline QueryPlan plan_queries(const std::vector<int64_t>& row0, const std::vector<int32_t>& ns, const int64_t* pad_row, double pad_step,
+                              const int64_t* q_row, const double* q_off, int64_t nq) {
+    const int64_t nl = (int64_t)row0.size();
+    std::vector<int64_t> by_row;
+    for (int64_t l = 0; l < nl; l++) if (ns[l] > 0) by_row.push_back(l);
+    std::sort(by_row.begin(), by_row.end(), [&](int64_t a, int64_t b) { return row0[a] < row0[b]; });
+    std::vector<int64_t> start(by_row.size());
+    for (size_t k = 0; k < by_row.size(); k++) start[k] = row0[by_row[k]];
+
+    // queries -> (lane, step, residual); key = lane * 2^31 + step orders them by slot
+    std::vector<int64_t> key((size_t)nq, -1);
+    std::vector<double> res((size_t)nq, 0.0);
+    for (int64_t k = 0; k < nq; k++) {
+        const int64_t p = pad_row ? pad_row[q_row[k]] : q_row[k];
+        const size_t t = std::upper_bound(start.begin(), start.end(), p) - start.begin();
+        if (t == 0) continue;
+        const int64_t l = by_row[t - 1], r0 = row0[l], n = ns[l];
+        if (p > r0 + n) continue;                                   // (a one-row track: no lane holds it)
+        int64_t st = p - r0 - 1;
+        if (st < 0) continue;                                       // a track's first row carries no state
+        double off = q_off[k];
+        if (pad_row && st < n - 1) {
+            // a caller's interval may span several lattice steps: the whole steps inside `off` move the row, the rest is the residual
+            int64_t w = (int64_t)std::floor(off / pad_step + ssde::PREDICT_DT_RTOL);
+            double rest = off - (double)w * pad_step;
+            if (rest < 0.0) rest = 0.0;
+            const int64_t pn = pad_row[q_row[k] + 1];               // the caller's next row (same track: row j is not its last)
+            if (p + w > pn || (p + w == pn && rest > ssde::PREDICT_DT_RTOL * pad_step)) continue;   // past the next fix: NaN
+            if (p + w == pn) rest = 0.0;
+            st += w; off = rest;
+        }
+        key[k] = (l << 31) | st;
+        res[k] = off;
+    }
+    QueryPlan P;
+    for (int64_t k = 0; k < nq; k++) if (key[k] >= 0) P.order.push_back(k);
+    std::stable_sort(P.order.begin(), P.order.end(), [&](int64_t a, int64_t b) { return key[a] < key[b]; });
+    const int64_t nv = (int64_t)P.order.size();
+    P.want_off.assign((size_t)nl + 1, 0);
+    P.q_slot.resize((size_t)nv);
+    P.off.resize((size_t)nv);
+    for (int64_t i = 0; i < nv; i++) {
+        const int64_t kk = key[P.order[i]];
+        if (i == 0 || kk != key[P.order[i - 1]]) {
+            P.want_step.push_back((int32_t)(kk & 0x7fffffff));
+            P.want_off[(size_t)(kk >> 31) + 1]++;
+        }
+        P.q_slot[i] = (int64_t)P.want_step.size() - 1;
+        P.off[i] = res[P.order[i]];
+    }
+    for (int64_t l = 0; l < nl; l++) P.want_off[l + 1] += P.want_off[l];
+    return P;
+}
+
+// the slots [s0, s1) of the chunk of groups [g_lo, g_hi) (a chunk's lanes hold consecutive slots) and its queries [q0, q1)
+struct QueryRange { int64_t s0, s1, q0, q1; };
+inline QueryRange chunk_queries(const QueryPlan& P, int g_lo, int g_hi, int wave) {
+    const int64_t nl = (int64_t)P.want_off.size() - 1;
+    const int64_t l0 = std::min<int64_t>((int64_t)g_lo * wave, nl), l1 = std::min<int64_t>((int64_t)g_hi * wave, nl);
+    const int64_t s0 = P.want_off[l0], s1 = P.want_off[l1];
+    return QueryRange{s0, s1, std::lower_bound(P.q_slot.begin(), P.q_slot.end(), s0) - P.q_slot.begin(),
+                      std::lower_bound(P.q_slot.begin(), P.q_slot.end(), s1) - P.q_slot.begin()};
+}
+
+}  // namespace ssde_plan
+#endif

@@ -17,6 +17,7 @@
 #include "../../smoothsde_amd/csrc/ssde_smooth.hpp"
 #include "../../smoothsde_amd/csrc/ssde_knobs.hpp"
 #include "../../smoothsde_amd/csrc/ssde_windows.hpp"
+#include "hostsim_records.hpp"
 #include <sstream>
 #include <vector>
 
@@ -237,35 +238,16 @@ void run_adj_full(int any_nan, int64_t n, int64_t n_tracks, const int64_t* row0,
 
 // fixed-interval smoother (ssde_smooth.hpp over ssde_dense.hpp): each track the way one lane of dense_kernel's record mode /
 // smooth_tv_record_kernel and then smooth_back_kernel walk it -- a plain record per state row, then the backward recursion.
-// parmat: n x q row-major linear predictors; harr: n x d x d (row-major per row) or NULL (h I); p0f: SD x SD column-major;
-// a0: n_tracks x SD.  mean (n x SD), cov (n x SD x SD), resid (n x d), row-major, written on state rows only.
+// The problem as hostsim_records.hpp has it.  mean (n x SD), cov (n x SD x SD), resid (n x d), row-major, written on state rows only.
 template <int MODEL, int D>
-void run_smooth(int any_nan, int64_t n, int64_t n_tracks, const int64_t* row0, const int64_t* nrows, const double* times,
-                const double* obs, const double* parmat, const double* harr, double h, const double* p0f, const double* a0,
-                double* mean, double* cov, double* resid) {
-    typedef DenseDims<MODEL, D> DM;
+void run_smooth(const TwinProblem& pb, double* mean, double* cov, double* resid) {
     typedef SmoothRec<MODEL, D> RC;
-    constexpr int SD = DM::SD, Q = DM::Q, R = RC::R;
-    for (int64_t m = 0; m < n_tracks; m++) {
-        const int64_t ns = nrows[m] - 1;
+    constexpr int SD = RC::SD, R = RC::R;
+    const int64_t* row0 = pb.row0;
+    std::vector<double> recs;
+    for (int64_t m = 0; m < pb.n_tracks; m++) {
+        const int64_t ns = twin_record_track<MODEL, D>(pb, m, recs);
         if (ns <= 0) continue;
-        DenseLane<MODEL, D, 0> L;
-        L.init(a0 + m * SD, p0f);
-        std::vector<double> recs((size_t)ns * R);
-        for (int64_t s = 0; s < ns; s++) {
-            const int64_t i = row0[m] + 1 + s;
-            const double dt = (i + 1 < n) ? times[i + 1] - times[i] : 1.0;
-            double y[D];
-            for (int c = 0; c < D; c++) y[c] = obs[i + c * n];
-            DualN<0> H[D][D], par[Q];
-            for (int p = 0; p < D; p++)
-                for (int q = 0; q < D; q++) H[p][q] = DualN<0>(harr ? harr[(i * D + p) * D + q] : (p == q ? h : 0.0));
-            for (int j = 0; j < Q; j++) par[j] = DualN<0>(parmat[i * Q + j]);
-            const bool na = is_na(y[0], any_nan);
-            double* rp = &recs[(size_t)s * R];
-            smooth_record_row<MODEL, D>(L, par, H, dt, y, na, [&](int k) -> double& { return rp[k]; });
-            dense_step<MODEL, D, 0>(L, par, H, dt, y, na);
-        }
         double r[SD], N[SD][SD];
         for (int a = 0; a < SD; a++) { r[a] = 0.0; for (int b = 0; b < SD; b++) N[a][b] = 0.0; }
         for (int64_t s = ns - 1; s >= 0; s--) {
@@ -286,13 +268,9 @@ void run_smooth(int any_nan, int64_t n, int64_t n_tracks, const int64_t* row0, c
 
 extern "C" {
 
-int hostsim_smooth(int model, int d, int any_nan, int64_t n, int64_t n_tracks, const int64_t* row0, const int64_t* nrows,
-                   const double* times, const double* obs, const double* parmat, const double* harr, double h, const double* p0f,
-                   const double* a0, double* mean, double* cov, double* resid) {
-#define SM(MODEL, D) if (model == MODEL && d == D) { run_smooth<MODEL, D>(any_nan, n, n_tracks, row0, nrows, times, obs, parmat, harr, h, p0f, a0, mean, cov, resid); return 0; }
-#define SM8(MODEL) SM(MODEL, 1) SM(MODEL, 2) SM(MODEL, 3) SM(MODEL, 4) SM(MODEL, 5) SM(MODEL, 6) SM(MODEL, 7) SM(MODEL, 8)
-    SM8(M_CTCRW) SM8(M_OU_SSM) SM8(M_BM_SSM)
-#undef SM8
+int hostsim_smooth(int model, int d, TWIN_PARAMS, double* mean, double* cov, double* resid) {
+#define SM(MODEL, D) if (model == MODEL && d == D) { run_smooth<MODEL, D>(TWIN_ARGS, mean, cov, resid); return 0; }
+    TWIN_D12(SM) TWIN_D38(SM)
 #undef SM
     return 1;
 }

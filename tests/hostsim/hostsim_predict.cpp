@@ -3,54 +3,32 @@
 // Compiles smoothsde_amd/csrc/ssde_predict.hpp (the lane math of k_predict.hip) over ssde_smooth.hpp / ssde_dense.hpp with g++ and
 // walks each track the way one lane of the kernels does: smooth_record_row + predict_side_row -> dense_step per state row, then from
 // the last record to the first predict_packet_row (before the row is processed) and smooth_back_row; predict_query_row answers the
-// queries from the packets.  tests/test_predict_hostsim.py compares it with tests/predict_ref.py.
-#include <cmath>
-#include <cstdint>
-#include <vector>
+// queries from the packets.  tests/test_predict_hostsim.py compares it with tests/predict_ref.py.  It also exports the host-side
+// plans of smoothsde_amd/csrc/ssde_smooth_plan.hpp to tests/test_smooth_plan_host.py.
+#include <cstring>
 
-#include "../../smoothsde_amd/csrc/ssde_predict.hpp"
+#include "../../smoothsde_amd/csrc/ssde_smooth_plan.hpp"
+#include "hostsim_records.hpp"
 
 using namespace ssde;
 
 namespace {
 
-// parmat: n x q row-major linear predictors; harr: n x d x d (row-major per row) or NULL (h I); p0f: SD x SD column-major;
-// a0: n_tracks x SD.  Queries (q_row, q_off); a_pred (nq x SD) and P_pred (nq x SD x SD), row-major, are written where a state exists.
+// the problem as hostsim_records.hpp has it.  Queries (q_row, q_off); a_pred (nq x SD) and P_pred (nq x SD x SD), row-major, are
+// written where a state exists.
 template <int MODEL, int D>
-void run_predict(int any_nan, int64_t n, int64_t n_tracks, const int64_t* row0, const int64_t* nrows, const double* times,
-                 const double* obs, const double* parmat, const double* harr, double h, const double* p0f, const double* a0,
-                 int64_t nq, const int64_t* q_row, const double* q_off, double* a_pred, double* P_pred) {
-    typedef DenseDims<MODEL, D> DM;
+void run_predict(const TwinProblem& pb, int64_t nq, const int64_t* q_row, const double* q_off, double* a_pred, double* P_pred) {
     typedef SmoothRec<MODEL, D> RC;
     typedef PredictPk<MODEL, D> PK;
-    constexpr int SD = DM::SD, Q = DM::Q, R = RC::R, SW = PK::SW, SZ = PK::SZ;
-    std::vector<double> packets((size_t)n * SZ, 0.0);
-    std::vector<char> has((size_t)n, 0);
-    for (int64_t m = 0; m < n_tracks; m++) {
-        const int64_t ns = nrows[m] - 1;
+    constexpr int SD = RC::SD, R = RC::R, SW = PK::SW, SZ = PK::SZ;
+    std::vector<double> packets((size_t)pb.n * SZ, 0.0), recs, side;
+    std::vector<char> has((size_t)pb.n, 0);
+    for (int64_t m = 0; m < pb.n_tracks; m++) {
+        const int64_t ns = twin_record_track<MODEL, D>(pb, m, recs, &side);
         if (ns <= 0) continue;
-        DenseLane<MODEL, D, 0> L;
-        L.init(a0 + m * SD, p0f);
-        std::vector<double> recs((size_t)ns * R), side((size_t)ns * SW);
-        for (int64_t s = 0; s < ns; s++) {
-            const int64_t i = row0[m] + 1 + s;
-            const double dt = (i + 1 < n) ? times[i + 1] - times[i] : 1.0;
-            double y[D];
-            for (int c = 0; c < D; c++) y[c] = obs[i + c * n];
-            DualN<0> H[D][D], par[Q];
-            for (int p = 0; p < D; p++)
-                for (int q = 0; q < D; q++) H[p][q] = DualN<0>(harr ? harr[(i * D + p) * D + q] : (p == q ? h : 0.0));
-            for (int j = 0; j < Q; j++) par[j] = DualN<0>(parmat[i * Q + j]);
-            const bool na = is_na(y[0], any_nan);
-            double* rp = &recs[(size_t)s * R];
-            double* sp = &side[(size_t)s * SW];
-            const bool upd = smooth_record_row<MODEL, D>(L, par, H, dt, y, na, [&](int k) -> double& { return rp[k]; });
-            predict_side_row<MODEL, D>(par, dt, na, upd, [&](int k) -> double& { return sp[k]; });
-            dense_step<MODEL, D, 0>(L, par, H, dt, y, na);
-        }
         double r[SD] = {}, N[SD][SD] = {};
         for (int64_t s = ns - 1; s >= 0; s--) {
-            const int64_t i = row0[m] + 1 + s;
+            const int64_t i = pb.row0[m] + 1 + s;
             const double* rp = &recs[(size_t)s * R];
             const double* sp = &side[(size_t)s * SW];
             double* pp = &packets[(size_t)i * SZ];
@@ -74,24 +52,52 @@ void run_predict(int any_nan, int64_t n, int64_t n_tracks, const int64_t* row0, 
     }
 }
 
+template <class T>
+void copy_out(const std::vector<T>& v, T* dst) { if (!v.empty()) memcpy(dst, v.data(), v.size() * sizeof(T)); }
+
 }  // namespace
 
 extern "C" {
 
-int hostsim_predict(int model, int d, int any_nan, int64_t n, int64_t n_tracks, const int64_t* row0, const int64_t* nrows,
-                    const double* times, const double* obs, const double* parmat, const double* harr, double h, const double* p0f,
-                    const double* a0, int64_t nq, const int64_t* q_row, const double* q_off, double* a_pred, double* P_pred) {
-#define PR(MODEL, D) if (model == MODEL && d == D) { run_predict<MODEL, D>(any_nan, n, n_tracks, row0, nrows, times, obs, parmat, harr, h, p0f, a0, nq, q_row, q_off, a_pred, P_pred); return 0; }
-    PR(M_CTCRW, 1) PR(M_CTCRW, 2) PR(M_OU_SSM, 1) PR(M_OU_SSM, 2) PR(M_BM_SSM, 1) PR(M_BM_SSM, 2)
+int hostsim_predict(int model, int d, TWIN_PARAMS, int64_t nq, const int64_t* q_row, const double* q_off, double* a_pred, double* P_pred) {
+#define PR(MODEL, D) if (model == MODEL && d == D) { run_predict<MODEL, D>(TWIN_ARGS, nq, q_row, q_off, a_pred, P_pred); return 0; }
+    TWIN_D12(PR)
 #undef PR
     return 1;
 }
 
 int hostsim_predict_packet_doubles(int model, int d) {
 #define PD(MODEL, D) if (model == MODEL && d == D) return PredictPk<MODEL, D>::SZ;
-    PD(M_CTCRW, 1) PD(M_CTCRW, 2) PD(M_OU_SSM, 1) PD(M_OU_SSM, 2) PD(M_BM_SSM, 1) PD(M_BM_SSM, 2)
+    TWIN_D12(PD)
 #undef PD
     return 0;
 }
+
+// ---- the plans of ssde_smooth_plan.hpp ------------------------------------------------------------------------------------------
+// plan_queries over nl lanes and nq queries (pad_row NULL: the rows are the caller's).  order, q_slot, off: room for nq; want_off:
+// nl + 1; want_step: nq.  cuts: n_cuts group boundaries (ascending, wave lanes a group); ranges: (n_cuts - 1) x 4 = s0, s1, q0, q1 of
+// every chunk.  counts = planned queries, slots.
+void hostsim_plan_queries(int64_t nl, const int64_t* row0, const int32_t* ns, const int64_t* pad_row, double pad_step, int64_t nq,
+                          const int64_t* q_row, const double* q_off, int n_cuts, const int32_t* cuts, int wave, int64_t* counts,
+                          int64_t* order, int64_t* q_slot, double* off, int64_t* want_off, int32_t* want_step, int64_t* ranges) {
+    const ssde_plan::QueryPlan P = ssde_plan::plan_queries(std::vector<int64_t>(row0, row0 + nl), std::vector<int32_t>(ns, ns + nl),
+                                                           pad_row, pad_step, q_row, q_off, nq);
+    counts[0] = (int64_t)P.order.size(); counts[1] = (int64_t)P.want_step.size();
+    copy_out(P.order, order); copy_out(P.q_slot, q_slot); copy_out(P.off, off);
+    copy_out(P.want_off, want_off); copy_out(P.want_step, want_step);
+    for (int c = 0; c + 1 < n_cuts; c++) {
+        const ssde_plan::QueryRange r = ssde_plan::chunk_queries(P, cuts[c], cuts[c + 1], wave);
+        ranges[4 * c] = r.s0; ranges[4 * c + 1] = r.s1; ranges[4 * c + 2] = r.q0; ranges[4 * c + 3] = r.q1;
+    }
+}
+
+// chunk_groups over goff (n_groups + 1 offsets): cuts gets at most n_groups + 1 entries, returns how many
+int hostsim_chunk_groups(int n_groups, const int64_t* goff, int64_t budget, int32_t* cuts) {
+    const std::vector<int> cut = ssde_plan::chunk_groups(std::vector<int64_t>(goff, goff + n_groups + 1), budget);
+    for (size_t k = 0; k < cut.size(); k++) cuts[k] = cut[k];
+    return (int)cut.size();
+}
+
+int hostsim_batch_cap(int64_t budget, int64_t per_draw, int unit, int ch, int n_draws) { return ssde_plan::batch_cap(budget, per_draw, unit, ch, n_draws); }
 
 }  // extern "C"

@@ -9,15 +9,66 @@ _DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostsim")
 _LIB = None
 _dp = C.POINTER(C.c_double)
 _lp = C.POINTER(C.c_int64)
+# the twins' common arguments (tests/hostsim/hostsim_records.hpp: TWIN_PARAMS), after model and d
+TWIN_ARGTYPES = [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _lp, _lp, _dp, _dp, _dp, _dp, C.c_double, _dp, _dp]
+
+
+_LIBS = {}
+
+
+def load_lib(name, protos=None):
+    """tests/hostsim/<name>, after `make` there (which compiles nothing in a built tree), loaded once; protos: {function: (restype,
+    argtypes)}"""
+    if name not in _LIBS:
+        alt = os.environ.get("SSDE_ORACLE_LIBDIR") if name == "libhostsim.so" else None      # tools/sanitize_cpu.sh: the sanitizer build
+        if not alt:
+            subprocess.run(["make", "-s", "-C", _DIR, name], check=True)
+        lib = C.CDLL(os.path.join(alt or _DIR, name))
+        for f, (res, args) in (protos or {}).items():
+            getattr(lib, f).restype, getattr(lib, f).argtypes = res, args
+        _LIBS[name] = lib
+    return _LIBS[name]
+
+
+def ptr(a, t=None):
+    """the ctypes pointer of an array (None stays NULL)"""
+    return None if a is None else a.ctypes.data_as(t or (_lp if a.dtype == np.int64 else _dp))
+
+
+def twin_args(pb, par):
+    """A problem as the twins take it: (arguments in TWIN_ARGTYPES' order, the arrays they point to -- keep them alive over the
+    call).  The linear predictors are formed here (refimpl.linear_predictor), a0 and P0 default as the engine's create path sets
+    them."""
+    import torch
+    from refimpl import linear_predictor
+    from smoothsde_amd.capi import MODEL_CODES
+    d, sd, n = pb.n_dim, pb.sdim, pb.n
+    par = np.asarray(par, dtype=np.float64)
+    parmat = np.ascontiguousarray(linear_predictor(pb, torch.as_tensor(par)).detach().numpy())          # n x q
+    row0 = np.ascontiguousarray(pb.seg_start, dtype=np.int64)
+    nrows = np.diff(np.append(pb.seg_start, n)).astype(np.int64)
+    z = (lambda a: 2 * a) if pb.model == "CTCRW" else (lambda a: a)
+    if pb.P0 is None:
+        P0 = np.diag([1.0, 10.0] * d) if pb.model == "CTCRW" else 10.0 * np.eye(d)
+    else:
+        P0 = np.asarray(pb.P0, dtype=np.float64)
+    p0f = np.ascontiguousarray(P0.ravel(order="F"))
+    if pb.a0 is None:
+        a0 = np.zeros((pb.n_seg, sd))
+        for a in range(d):
+            a0[:, z(a)] = pb.obs[row0, a]
+    else:
+        a0 = np.ascontiguousarray(pb.a0, dtype=np.float64)
+    harr = None if pb.H is None else np.ascontiguousarray(np.moveaxis(np.asarray(pb.H, dtype=np.float64), 2, 0))   # n x d x d
+    keep = (parmat, row0, nrows, p0f, a0, harr)
+    return [MODEL_CODES[pb.model], d, int(pb.na_mode == 1), n, pb.n_seg, ptr(row0), ptr(nrows), ptr(pb.times), ptr(pb.obs),
+            ptr(parmat), ptr(harr), float(np.exp(par[0]) ** 2), ptr(p0f), ptr(a0)], keep
 
 
 def load():
     global _LIB
     if _LIB is None:
-        alt = os.environ.get("SSDE_ORACLE_LIBDIR")           # tools/sanitize_cpu.sh: the sanitizer build
-        if not alt:
-            subprocess.run(["make", "-s", "-C", _DIR], check=True)
-        lib = C.CDLL(os.path.join(alt or _DIR, "libhostsim.so"))
+        lib = load_lib("libhostsim.so")
         lib.hostsim_kalman_iso.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _lp, _lp,
                                            _dp, _dp, _dp, _dp, _dp]
         lib.hostsim_kalman_iso.restype = C.c_int
@@ -33,8 +84,7 @@ def load():
         lib.hostsim_kalman_adj_full.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int64, _lp, _lp, _dp, _dp, _dp,
                                                 C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp]
         lib.hostsim_kalman_adj_full.restype = C.c_int
-        lib.hostsim_smooth.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _lp, _lp, _dp, _dp, _dp, _dp, C.c_double,
-                                       _dp, _dp, _dp, _dp, _dp]
+        lib.hostsim_smooth.argtypes = TWIN_ARGTYPES + [_dp, _dp, _dp]
         lib.hostsim_smooth.restype = C.c_int
         lib.hostsim_knobs.argtypes = [C.c_int, C.c_char_p, C.c_int]
         lib.hostsim_knobs.restype = C.c_int
@@ -169,38 +219,35 @@ class WindowPolicy:
 def smooth(pb, par):
     """The fixed-interval smoother by the lane math of csrc/ssde_smooth.hpp over csrc/ssde_dense.hpp (smooth_record_row ->
     dense_step per state row, then smooth_back_row over the records), one track after the other: what smooth_ref returns,
-    {"mean": n x sdim, "cov": n x sdim x sdim, "resid": n x d}, NaN where no state / no update exists.  The linear predictors
-    are formed here (refimpl.linear_predictor), a0 and P0 default as the engine's create path sets them."""
-    import torch
-    from refimpl import linear_predictor
-    from smoothsde_amd.capi import MODEL_CODES
-    lib = load()
+    {"mean": n x sdim, "cov": n x sdim x sdim, "resid": n x d}, NaN where no state / no update exists."""
+    args, keep = twin_args(pb, par)
     d, sd, n = pb.n_dim, pb.sdim, pb.n
-    par = np.asarray(par, dtype=np.float64)
-    parmat = np.ascontiguousarray(linear_predictor(pb, torch.as_tensor(par)).detach().numpy())          # n x q
-    row0 = np.ascontiguousarray(pb.seg_start, dtype=np.int64)
-    nrows = np.diff(np.append(pb.seg_start, n)).astype(np.int64)
-    z = (lambda a: 2 * a) if pb.model == "CTCRW" else (lambda a: a)
-    if pb.P0 is None:
-        P0 = np.diag([1.0, 10.0] * d) if pb.model == "CTCRW" else 10.0 * np.eye(d)
-    else:
-        P0 = np.asarray(pb.P0, dtype=np.float64)
-    p0f = np.ascontiguousarray(P0.ravel(order="F"))
-    if pb.a0 is None:
-        a0 = np.zeros((pb.n_seg, sd))
-        for a in range(d):
-            a0[:, z(a)] = pb.obs[row0, a]
-    else:
-        a0 = np.ascontiguousarray(pb.a0, dtype=np.float64)
-    harr = None if pb.H is None else np.ascontiguousarray(np.moveaxis(np.asarray(pb.H, dtype=np.float64), 2, 0))   # n x d x d
     mean, cov, res = np.full((n, sd), np.nan), np.full((n, sd, sd), np.nan), np.full((n, d), np.nan)
-    st = lib.hostsim_smooth(MODEL_CODES[pb.model], d, int(pb.na_mode == 1), n, pb.n_seg, row0.ctypes.data_as(_lp),
-                            nrows.ctypes.data_as(_lp), pb.times.ctypes.data_as(_dp), pb.obs.ctypes.data_as(_dp),
-                            parmat.ctypes.data_as(_dp), None if harr is None else harr.ctypes.data_as(_dp),
-                            float(np.exp(par[0]) ** 2), p0f.ctypes.data_as(_dp), a0.ctypes.data_as(_dp),
-                            mean.ctypes.data_as(_dp), cov.ctypes.data_as(_dp), res.ctypes.data_as(_dp))
+    st = load().hostsim_smooth(*args, ptr(mean), ptr(cov), ptr(res))
     assert st == 0
     return {"mean": mean, "cov": cov, "resid": res}
+
+
+def _parmat_blocks(pb, par):
+    """the linear predictors (n x q, column-major) and, per coefficient, (parameter j, index in par, design column)"""
+    n, q = pb.n, pb.q
+    parmat = np.zeros((n, q), order="F")
+    blocks = []
+    for j in range(q):
+        for src, off, nc in ((pb.X_fe[j], pb.off_fe + pb.fe_off[j], pb.ncol_fe[j]),
+                             (pb.X_re[j], pb.off_re + pb.re_off[j], pb.ncol_re[j])):
+            for c in range(nc):
+                col = np.ones(n) if src is None else src[:, c]
+                parmat[:, j] += col * par[off + c]
+                blocks.append((j, off + c, col))
+    return parmat, blocks
+
+
+def _p0_iso(pb):
+    """P0 of the isotropic lanes: one dimension's block (p11, p12, p22), or the scalar models' variance"""
+    if pb.model == "CTCRW":
+        return np.array([1.0, 0.0, 10.0]) if pb.P0 is None else np.array([pb.P0[0, 0], pb.P0[0, 1], pb.P0[1, 1]])
+    return np.array([10.0, 0, 0]) if pb.P0 is None else np.array([pb.P0[0, 0], 0, 0])
 
 
 def kalman_adj_full(pb, par):
@@ -211,15 +258,7 @@ def kalman_adj_full(pb, par):
     d, q, n = pb.n_dim, pb.q, pb.n
     assert d == 2
     par = np.asarray(par, dtype=np.float64)
-    parmat = np.zeros((n, q), order="F")
-    blocks = []
-    for j in range(q):
-        for src, off, nc in ((pb.X_fe[j], pb.off_fe + pb.fe_off[j], pb.ncol_fe[j]),
-                             (pb.X_re[j], pb.off_re + pb.re_off[j], pb.ncol_re[j])):
-            for c in range(nc):
-                col = np.ones(n) if src is None else src[:, c]
-                parmat[:, j] += col * par[off + c]
-                blocks.append((j, off + c, col))
+    parmat, blocks = _parmat_blocks(pb, par)
     row0 = np.ascontiguousarray(pb.seg_start, dtype=np.int64)
     nrows = np.diff(np.append(pb.seg_start, n)).astype(np.int64)
     sd = 4 if pb.model == "CTCRW" else 2
@@ -252,21 +291,10 @@ def kalman_adj(pb, par):
     lib = load()
     d, q, n = pb.n_dim, pb.q, pb.n
     par = np.asarray(par, dtype=np.float64)
-    parmat = np.zeros((n, q), order="F")
-    blocks = []
-    for j in range(q):
-        for src, off, nc in ((pb.X_fe[j], pb.off_fe + pb.fe_off[j], pb.ncol_fe[j]),
-                             (pb.X_re[j], pb.off_re + pb.re_off[j], pb.ncol_re[j])):
-            for c in range(nc):
-                col = np.ones(n) if src is None else src[:, c]
-                parmat[:, j] += col * par[off + c]
-                blocks.append((j, off + c, col))
+    parmat, blocks = _parmat_blocks(pb, par)
     row0 = np.ascontiguousarray(pb.seg_start, dtype=np.int64)
     nrows = np.diff(np.append(pb.seg_start, n)).astype(np.int64)
-    if pb.model == "CTCRW":
-        p0 = np.array([1.0, 0.0, 10.0]) if pb.P0 is None else np.array([pb.P0[0, 0], pb.P0[0, 1], pb.P0[1, 1]])
-    else:
-        p0 = np.array([10.0, 0, 0]) if pb.P0 is None else np.array([pb.P0[0, 0], 0, 0])
+    p0 = _p0_iso(pb)
     a0 = None if pb.a0 is None else np.ascontiguousarray(pb.a0)
     out = np.zeros(2)
     G = np.zeros((n, q), order="F")
@@ -303,10 +331,7 @@ def kalman_tv(pb, par):
     wmat = np.ascontiguousarray(np.column_stack(wcols))
     row0 = np.ascontiguousarray(pb.seg_start, dtype=np.int64)
     nrows = np.diff(np.append(pb.seg_start, n)).astype(np.int64)
-    if pb.model == "CTCRW":
-        p0 = np.array([1.0, 0.0, 10.0]) if pb.P0 is None else np.array([pb.P0[0, 0], pb.P0[0, 1], pb.P0[1, 1]])
-    else:
-        p0 = np.array([10.0, 0, 0]) if pb.P0 is None else np.array([pb.P0[0, 0], 0, 0])
+    p0 = _p0_iso(pb)
     a0 = None if pb.a0 is None else np.ascontiguousarray(pb.a0)
     ki, di = np.asarray(kinds, dtype=np.int32), np.asarray(dims, dtype=np.int32)
     out = np.zeros(1 + nd)
@@ -331,10 +356,7 @@ def kalman_iso(pb, par, mask):
     nrows = np.diff(np.append(pb.seg_start, pb.n)).astype(np.int64)
     theta = np.zeros(3 + d)
     theta[:len(par)] = par
-    if pb.model == "CTCRW":
-        p0 = np.array([1.0, 0.0, 10.0]) if pb.P0 is None else np.array([pb.P0[0, 0], pb.P0[0, 1], pb.P0[1, 1]])
-    else:
-        p0 = np.array([10.0, 0, 0]) if pb.P0 is None else np.array([pb.P0[0, 0], 0, 0])
+    p0 = _p0_iso(pb)
     out = np.zeros(4 + d)
     st = lib.hostsim_kalman_iso(MODEL_CODES[pb.model], d, mask, int(pb.na_mode == 1), pb.n, pb.n_seg,
                                 row0.ctypes.data_as(_lp), nrows.ctypes.data_as(_lp),

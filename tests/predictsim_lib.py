@@ -1,43 +1,22 @@
-"""ctypes loader of the test-only host build of ssde_predict's lane math (tests/hostsim/hostsim_predict.cpp): compiles it itself,
-with the flags of tests/hostsim/Makefile, into a library of its own next to libhostsim.so."""
+"""ctypes loader of the test-only host build of ssde_predict's lane math and of the smoother calls' host-side plans
+(tests/hostsim/hostsim_predict.cpp, a library of its own next to libhostsim.so, built by tests/hostsim/Makefile)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostsim")
-_CSRC = os.path.join(os.path.dirname(_DIR), os.pardir, "smoothsde_amd", "csrc")
-_SRC = os.path.join(_DIR, "hostsim_predict.cpp")
-_SO = os.path.join(_DIR, "libhostsim_predict.so")
-_DEPS = [_SRC] + [os.path.join(_CSRC, f) for f in ("ssde_predict.hpp", "ssde_smooth.hpp", "ssde_dense.hpp", "ssde_math.hpp")]
-_LIB = None
-_dp = C.POINTER(C.c_double)
-_lp = C.POINTER(C.c_int64)
+from hostsim_lib import TWIN_ARGTYPES, _dp, _lp, load_lib, ptr, twin_args
 
-
-def build():
-    """g++ -> tests/hostsim/libhostsim_predict.so when it is missing or older than its sources"""
-    if os.path.exists(_SO) and all(os.path.getmtime(_SO) >= os.path.getmtime(f) for f in _DEPS):
-        return _SO
-    cxx = os.environ.get("CXX", "g++")
-    tmp = _SO + f".{os.getpid()}.tmp"
-    subprocess.run([cxx, "-O2", "-std=c++17", "-fPIC", "-Wall", "-Wextra", "-shared", "-o", tmp, _SRC], check=True)
-    os.replace(tmp, _SO)
-    return _SO
+_ip = C.POINTER(C.c_int32)
 
 
 def load():
-    global _LIB
-    if _LIB is None:
-        lib = C.CDLL(build())
-        lib.hostsim_predict.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _lp, _lp, _dp, _dp, _dp, _dp, C.c_double,
-                                        _dp, _dp, C.c_int64, _lp, _dp, _dp, _dp]
-        lib.hostsim_predict.restype = C.c_int
-        lib.hostsim_predict_packet_doubles.argtypes = [C.c_int, C.c_int]
-        lib.hostsim_predict_packet_doubles.restype = C.c_int
-        _LIB = lib
-    return _LIB
+    return load_lib("libhostsim_predict.so", {
+        "hostsim_predict": (C.c_int, TWIN_ARGTYPES + [C.c_int64, _lp, _dp, _dp, _dp]),
+        "hostsim_predict_packet_doubles": (C.c_int, [C.c_int, C.c_int]),
+        "hostsim_plan_queries": (None, [C.c_int64, _lp, _ip, _lp, C.c_double, C.c_int64, _lp, _dp, C.c_int, _ip, C.c_int, _lp, _lp, _lp, _dp,
+                                        _lp, _ip, _lp]),
+        "hostsim_chunk_groups": (C.c_int, [C.c_int, _lp, C.c_int64, _ip]),
+        "hostsim_batch_cap": (C.c_int, [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int])})
 
 
 def packet_doubles(model, d):
@@ -47,37 +26,43 @@ def packet_doubles(model, d):
 
 def predict(pb, par, rows, offs):
     """The queries by the lane math of csrc/ssde_predict.hpp (record + side row -> packet -> query, one track after the other): what
-    predict_ref returns.  The linear predictors, a0 and P0 as drawsim_lib.draws forms them."""
-    import torch
-    from refimpl import linear_predictor
-    from smoothsde_amd.capi import MODEL_CODES
-    lib = load()
-    d, sd, n = pb.n_dim, pb.sdim, pb.n
-    par = np.asarray(par, dtype=np.float64)
-    parmat = np.ascontiguousarray(linear_predictor(pb, torch.as_tensor(par)).detach().numpy())          # n x q
-    row0 = np.ascontiguousarray(pb.seg_start, dtype=np.int64)
-    nrows = np.diff(np.append(pb.seg_start, n)).astype(np.int64)
-    z = (lambda a: 2 * a) if pb.model == "CTCRW" else (lambda a: a)
-    if pb.P0 is None:
-        P0 = np.diag([1.0, 10.0] * d) if pb.model == "CTCRW" else 10.0 * np.eye(d)
-    else:
-        P0 = np.asarray(pb.P0, dtype=np.float64)
-    p0f = np.ascontiguousarray(P0.ravel(order="F"))
-    if pb.a0 is None:
-        a0 = np.zeros((pb.n_seg, sd))
-        for a in range(d):
-            a0[:, z(a)] = pb.obs[row0, a]
-    else:
-        a0 = np.ascontiguousarray(pb.a0, dtype=np.float64)
-    harr = None if pb.H is None else np.ascontiguousarray(np.moveaxis(np.asarray(pb.H, dtype=np.float64), 2, 0))   # n x d x d
+    predict_ref returns.  The linear predictors, a0 and P0 as hostsim_lib.twin_args forms them."""
+    args, keep = twin_args(pb, par)
     rows = np.ascontiguousarray(rows, dtype=np.int64).ravel()
     offs = np.ascontiguousarray(offs, dtype=np.float64).ravel()
-    m = len(rows)
+    m, sd = len(rows), pb.sdim
     mean = np.full((m, sd), np.nan); cov = np.full((m, sd, sd), np.nan)
-    st = lib.hostsim_predict(MODEL_CODES[pb.model], d, int(pb.na_mode == 1), n, pb.n_seg, row0.ctypes.data_as(_lp),
-                             nrows.ctypes.data_as(_lp), pb.times.ctypes.data_as(_dp), pb.obs.ctypes.data_as(_dp),
-                             parmat.ctypes.data_as(_dp), None if harr is None else harr.ctypes.data_as(_dp),
-                             float(np.exp(par[0]) ** 2), p0f.ctypes.data_as(_dp), a0.ctypes.data_as(_dp), m, rows.ctypes.data_as(_lp),
-                             offs.ctypes.data_as(_dp), mean.ctypes.data_as(_dp), cov.ctypes.data_as(_dp))
+    st = load().hostsim_predict(*args, m, ptr(rows), ptr(offs), ptr(mean), ptr(cov))
     assert st == 0
     return {"mean": mean, "cov": cov}
+
+
+# ---- the host-side plans (csrc/ssde_smooth_plan.hpp) ----------------------------------------------------------------------------
+def plan_queries(row0, ns, q_row, q_off, pad_row=None, pad_step=0.0, cuts=(), wave=64):
+    """plan_queries over the lanes (row0, ns), and chunk_queries for the chunks between the group boundaries `cuts`: order, q_slot,
+    off (the sorted residuals), want_off, want_step, ranges (one row s0, s1, q0, q1 per chunk)."""
+    row0 = np.ascontiguousarray(row0, dtype=np.int64); ns = np.ascontiguousarray(ns, dtype=np.int32)
+    q_row = np.ascontiguousarray(q_row, dtype=np.int64); q_off = np.ascontiguousarray(q_off, dtype=np.float64)
+    pad = None if pad_row is None else np.ascontiguousarray(pad_row, dtype=np.int64)
+    cuts = np.ascontiguousarray(cuts, dtype=np.int32)
+    nl, nq = len(row0), len(q_row)
+    counts = np.zeros(2, dtype=np.int64)
+    order, q_slot, off = np.zeros(nq, dtype=np.int64), np.zeros(nq, dtype=np.int64), np.zeros(nq)
+    want_off, want_step = np.zeros(nl + 1, dtype=np.int64), np.zeros(nq, dtype=np.int32)
+    ranges = np.zeros((max(len(cuts) - 1, 0), 4), dtype=np.int64)
+    load().hostsim_plan_queries(nl, ptr(row0), ptr(ns, _ip), ptr(pad), float(pad_step), nq, ptr(q_row), ptr(q_off), len(cuts),
+                                ptr(cuts, _ip), wave, ptr(counts), ptr(order), ptr(q_slot), ptr(off), ptr(want_off),
+                                ptr(want_step, _ip), ptr(ranges))
+    nv, n_slots = int(counts[0]), int(counts[1])
+    return dict(order=order[:nv], q_slot=q_slot[:nv], off=off[:nv], want_off=want_off, want_step=want_step[:n_slots], ranges=ranges)
+
+
+def chunk_groups(goff, budget):
+    goff = np.ascontiguousarray(goff, dtype=np.int64)
+    cuts = np.zeros(len(goff), dtype=np.int32)
+    k = load().hostsim_chunk_groups(len(goff) - 1, ptr(goff), int(budget), ptr(cuts, _ip))
+    return cuts[:k]
+
+
+def batch_cap(budget, per_draw, unit, ch, n_draws):
+    return load().hostsim_batch_cap(int(budget), int(per_draw), unit, ch, n_draws)
