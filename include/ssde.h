@@ -31,6 +31,8 @@
  *                         reference gets by rebuilding the data with NA rows at the wanted times
  *   ssde_path_stats    <- (new) summaries of those draws reduced on the device: path length, net displacement and weighted time
  *                         inside up to eight boxes per track and draw, without a draw leaving the device
+ *   ssde_path_occupancy <- (new) the weighted time those draws spend in every cell of a regular grid, pooled over draws and over
+ *                         groups of tracks: a utilisation distribution, summed on the device as integers and so bitwise reproducible
  *   ssde_penalty       <- smoothing penalty     (nllk_ctcrw.hpp:254-280, nllk_sde.hpp:89-124)
  *   ssde_info          <- InfoADFunObject       (src/init.c:7)
  *   ssde_forget        <- (new) drops the memo of ssde_eval
@@ -396,6 +398,43 @@ int ssde_predict(ssde_handle *h, const double *par, int32_t n_par_full, const in
 #define SSDE_PATH_MAX_REGIONS 8
 int ssde_path_stats(ssde_handle *h, const double *par, int32_t n_par_full, uint64_t seed, int64_t draw0, int32_t n_draws,
                     const double *regions, int32_t n_regions, const double *weight, double *stats, uint32_t flags);
+
+/* Occupancy grids of posterior state paths at `par`, summed on the device (definitions: DESIGN.md §3.13).  Draws, state rows and
+ * position columns are exactly those of ssde_path_stats: draw q is draw number draw0 + q of the stream `seed`, the path
+ * ssde_smooth_draws returns; a lattice-padded handle samples its padded rows, which take part in nothing.
+ *   grid     the cell of a position p is ix = floor((p_1 - x0) / dx), iy = floor((p_2 - y0) / dy) (IEEE divisions); it is inside the
+ *            grid when 0 <= ix < nx and 0 <= iy < ny.  For n_dim = 1, ny must be 1 and y0, dy are neither read nor validated.  A
+ *            non-finite coordinate is outside.
+ *   occ      [nx x ny x n_groups], element (ix, iy, g) at ix + nx * (iy + ny * g): the sum of w_j over the n_draws draws, the tracks t
+ *            with group[t] == g and their state rows j whose position lies in the cell.
+ *   outside  [n_groups] or NULL: the same sum over the state rows that fall in no cell, so that per group the sum of occ plus outside
+ *            is exactly n_draws times the sum of w_j over the group's state rows.
+ *   group    [n_tracks] host memory, indexed by the ID segment's ordinal; -1: the track takes part in nothing.  NULL: every track is in
+ *            group 0 (n_groups must be 1).
+ *   weight   [n] host memory, indexed by the caller's row, or NULL for w_j = 1.  Validated: every entry finite and >= 0.
+ * The sums are taken in fixed point.  With wmax the largest weight (1 for NULL), frexp(wmax) = (m, k) and b the bit length of
+ * n * n_draws (n the rows of the whole handle's data), the quantum is 2^e, e = max(k + b - 52, -1074); w_j enters as the integer
+ * nearbyint(ldexp(w_j, -e)) (ties to even), the integers are summed as unsigned 64-bit numbers, and an output is
+ * ldexp((double)sum, e): every possible sum is below 2^52, so that conversion is exact.  wmax == 0 gives 0 everywhere.  Hence
+ *   1. the result is bitwise independent of SSDE_OPT_SMOOTH_BUDGET_MB, of the devices, of the kernel form and of repeated calls;
+ *   2. draw ranges add up bitwise over calls whenever the weights are whole numbers of both calls' quanta (NULL weights, dyadic dt);
+ *   3. otherwise draw ranges add up to within hits * 2^(e - 1) per cell, e the coarser call's.
+ * flags: SSDE_OCC_FORCE_GLOBAL runs every wavefront group in the global form (each lane adds straight into HBM) instead of the
+ * LDS-tile form; the numbers are the same.  ssde_last_occupancy_form tells which ran.
+ * SSDE_ERR_ARG for NULL h / par / grid / occ; n_draws < 1, draw0 < 0, draw0 + n_draws >= 2^28; nx or ny outside 1 ... 4096; ny != 1
+ * for n_dim = 1; dx (and dy for n_dim = 2) not finite or <= 0, x0 / y0 not finite; n_groups < 1 or nx * ny * n_groups > 2^28; group ==
+ * NULL with n_groups != 1, a group entry outside -1 ... n_groups - 1; a weight that is negative or not finite; an unknown flag.
+ * SSDE_ERR_MODEL exactly where ssde_path_stats gives it.  Every check runs before anything touches the device.  Multi-device handles
+ * are served.  Leaves the memo, the window state, the TV records, n_evals / n_memo_hits and every later ssde_eval / ssde_smooth /
+ * ssde_smooth_draws / ssde_predict / ssde_path_stats result as they were. */
+typedef struct ssde_occ_grid { double x0, dx, y0, dy; int32_t nx, ny; } ssde_occ_grid;
+#define SSDE_OCC_FORCE_GLOBAL 1u
+int ssde_path_occupancy(ssde_handle *h, const double *par, int32_t n_par_full, uint64_t seed, int64_t draw0, int32_t n_draws,
+                        const ssde_occ_grid *grid, const double *weight, const int32_t *group, int32_t n_groups,
+                        double *occ, double *outside, uint32_t flags);
+/* The kernel forms of the handle's last ssde_path_occupancy: 0 none yet, 1 every wavefront group ran the LDS-tile form, 2 every group
+ * the global form, 3 both ran.  A multi-device parent reports its first shard.  NULL gives -1. */
+int ssde_last_occupancy_form(const ssde_handle *h);
 
 /* Multiply the warm-up overlap of the time windows by `factor` for all later evaluations
  * (factor <= 0: force one sequential window). */

@@ -63,6 +63,11 @@ class SsdeLaplaceOpts(C.Structure):
                 ("max_newton", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SsdeOccGrid(C.Structure):
+    """ssde_occ_grid (include/ssde.h): the regular grid of ssde_path_occupancy"""
+    _fields_ = [("x0", C.c_double), ("dx", C.c_double), ("y0", C.c_double), ("dy", C.c_double), ("nx", C.c_int32), ("ny", C.c_int32)]
+
+
 class SsdeSimDesc(C.Structure):
     _fields_ = [("abi_version", C.c_int32), ("model", C.c_int32), ("n_dim", C.c_int32), ("n_steps", C.c_int32),
                 ("track0", C.c_int64), ("n_tracks", C.c_int64), ("row0", C.c_void_p), ("n_rows", C.c_int64),
@@ -495,6 +500,11 @@ def load_library():
     lib.ssde_predict.restype = C.c_int
     lib.ssde_path_stats.argtypes = [C.c_void_p, _dp, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, _dp, C.c_int32, _dp, _dp, C.c_uint32]
     lib.ssde_path_stats.restype = C.c_int
+    lib.ssde_path_occupancy.argtypes = [C.c_void_p, _dp, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.POINTER(SsdeOccGrid), _dp,
+                                        C.POINTER(C.c_int32), C.c_int32, _dp, _dp, C.c_uint32]
+    lib.ssde_path_occupancy.restype = C.c_int
+    lib.ssde_last_occupancy_form.argtypes = [C.c_void_p]
+    lib.ssde_last_occupancy_form.restype = C.c_int
     lib.ssde_widen_windows.argtypes = [C.c_void_p, C.c_int32]
     lib.ssde_widen_windows.restype = C.c_int
     lib.ssde_relax_windows.argtypes = [C.c_void_p]
@@ -566,12 +576,13 @@ class EngineError(RuntimeError):
 
 PATH_MAX_REGIONS = 8   # SSDE_PATH_MAX_REGIONS (include/ssde.h)
 DRAWS_DEVICE_OUT = 1   # ssde_smooth_draws flag: `draws` is an HBM pointer on the handle's device (include/ssde.h)
+OCC_FORCE_GLOBAL = 1   # ssde_path_occupancy flag: every wavefront group runs the global form (SSDE_OCC_FORCE_GLOBAL)
 
 WINDOW_TOL = 1e-11  # largest tolerated relative hand-over disagreement between time windows
 
 EXPORTED_SYMBOLS = ("ssde_create", "ssde_eval", "ssde_eval_device", "ssde_penalty", "ssde_report", "ssde_widen_windows", "ssde_relax_windows",
                     "ssde_info", "ssde_destroy", "ssde_last_error", "ssde_abi_version", "ssde_comm_unique_id", "ssde_comm_init_rank", "ssde_forget", "ssde_laplace_eval", "ssde_last_kernel_ms", "ssde_kernel_ms_history",
-                    "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth", "ssde_smooth_draws", "ssde_predict", "ssde_path_stats",
+                    "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth", "ssde_smooth_draws", "ssde_predict", "ssde_path_stats", "ssde_path_occupancy", "ssde_last_occupancy_form",
                     "ssde_lagstats_host_m", "ssde_lagstats_read_m", "ssde_lagforms_host_m", "ssde_reduce_host", "ssde_last_finish_form", "ssde_last_gain_feed", "ssde_last_gain_rows")
 
 
@@ -992,6 +1003,48 @@ class Engine:
                                              reg.ctypes.data_as(_dp) if len(reg) else None, len(reg),
                                              None if w is None else w.ctypes.data_as(_dp), buf.ctypes.data_as(_dp), 0))
         return buf.transpose(0, 2, 1)
+
+    def path_occupancy(self, par, n_draws: int, grid, seed: int = 0, draw0: int = 0, weight=None, group=None, n_groups=None,
+                       force_global: bool = False):
+        """The weighted time posterior state paths at `par` spend in every cell of a regular grid, summed on the device
+        (ssde_path_occupancy): (occ, outside) with occ of shape (n_groups, ny, nx) and outside of shape (n_groups,),
+        the weight that fell in no cell.  `grid`: a dict (or anything indexable by name) with x0, dx, nx and, for two position
+        columns, y0, dy, ny; the cell of a position is floor((p - x0) / dx), floor((p - y0) / dy).  Draw k is draw number draw0 + k of
+        the stream `seed`, the path smooth_draws returns.  `weight`: one finite number >= 0 per row of the data, or None for 1;
+        `group`: one label per track in -1 ... n_groups - 1 (-1: the track is left out), or None for one pooled grid; `n_groups`
+        defaults to max(group) + 1.  The sums are integers of a fixed quantum: the same bits whatever the chunking, the devices
+        or the kernel form (`force_global` picks the form that adds straight into HBM)."""
+        par = np.ascontiguousarray(par, dtype=np.float64)
+        if par.shape != (self.n_par_full,):
+            raise ValueError(f"par must have length {self.n_par_full}")
+        g = SsdeOccGrid(float(grid["x0"]), float(grid["dx"]), float(grid.get("y0", 0.0)), float(grid.get("dy", 1.0)),
+                        int(grid["nx"]), int(grid.get("ny", 1)))
+        w = None
+        if weight is not None:
+            w = np.ascontiguousarray(weight, dtype=np.float64)
+            if w.shape != (self.problem.n,):
+                raise ValueError("weight must hold one number per row of the data")
+        grp = None
+        if group is not None:
+            grp = np.ascontiguousarray(group, dtype=np.int32)
+            if grp.shape != (self.problem.n_seg,):
+                raise ValueError("group must hold one label per track")
+            if n_groups is None:
+                n_groups = int(grp.max(initial=0)) + 1
+        ng = 1 if n_groups is None else int(n_groups)
+        occ = np.zeros((max(ng, 0), max(g.ny, 0), max(g.nx, 0)))                        # element (ix, iy, g) at ix + nx (iy + ny g)
+        outside = np.zeros(max(ng, 0))
+        self._check(self.lib.ssde_path_occupancy(self._h, par.ctypes.data_as(_dp), self.n_par_full, int(seed), int(draw0), int(n_draws),
+                                                 C.byref(g), None if w is None else w.ctypes.data_as(_dp),
+                                                 None if grp is None else grp.ctypes.data_as(C.POINTER(C.c_int32)), ng,
+                                                 occ.ctypes.data_as(_dp), outside.ctypes.data_as(_dp),
+                                                 OCC_FORCE_GLOBAL if force_global else 0))
+        return occ, outside
+
+    def last_occupancy_form(self) -> int:
+        """The kernel forms of the last path_occupancy (ssde_last_occupancy_form): 0 none yet, 1 the LDS-tile form in every wavefront
+        group, 2 the global form in every group, 3 both."""
+        return int(self.lib.ssde_last_occupancy_form(self._h))
 
     def close(self):
         if self._h:

@@ -21,6 +21,7 @@
 
 #include "ssde_gain_feed.hpp"
 #include "ssde_math.hpp"
+#include "ssde_occ.hpp"
 #include "ssde_records.hpp"
 
 namespace ssde {
@@ -641,6 +642,27 @@ struct PathArgs {
 hipError_t launch_path_stats(const PathArgs& a, hipStream_t s);
 // map[pos[i]] = i for the caller's rows i < n, -1 on the other lattice rows (np of them)
 hipError_t launch_path_row_map(const int64_t* pos, int64_t n, int64_t np, int64_t* map, hipStream_t s);
+// ---- occupancy grids of the drawn paths (k_path_occ.hip, ssde_occ.hpp) ----
+// The draws of a DrawArgs `d` (its out / draw_stride are not read), each state row's quantised weight added to the cell of its drawn
+// position: cell c of output grid o at acc + c + nx * ny * o, the weight outside every cell at acc_out + o.  OCC_NW waves share a
+// workgroup and an LDS tile of at most OCC_TILE_CELLS cells in the tile form: 64 KiB, two workgroups in a CU's 160 KiB, which is the
+// two waves per SIMD the registers allow.
+constexpr int OCC_NW = 4;
+constexpr int OCC_TILE_CELLS = 8192;
+constexpr int OCC_GROUP_MIXED = -2;
+struct OccArgs {
+    DrawArgs d;
+    OccGrid grid;
+    const int64_t* row_map;      // as PathArgs
+    const uint64_t* wq;          // [the caller's rows]: w_j in quanta, or NULL: every row weighs `unit`
+    uint64_t unit;
+    const int32_t* lane_grp;     // [groups * 64]: the lane's output grid, -1: the lane takes part in nothing
+    const int32_t* grp_of;       // [groups]: the output grid all lanes of the group share (-1: none takes part): the tile form; or
+                                 // OCC_GROUP_MIXED: the global form
+    unsigned long long* acc;     // [nx * ny * n_out_groups], zeroed once per call
+    unsigned long long* acc_out; // [n_out_groups]
+};
+hipError_t launch_path_occ(const OccArgs& a, bool tile, hipStream_t s);
 // ---- the state at any time from the records (k_predict.hip, ssde_predict.hpp) ----
 // The records, side rows, groups and lanes of a SmoothArgs `s`.  Lane l wants the steps want_step[want_off[l] .. want_off[l + 1]) (ascending);
 // entry i of that list is slot i, and the walk stores its packet's double k at pk + k * pk_stride + (i - slot0).  The query kernel

@@ -1,6 +1,7 @@
 // ssde_engine_smooth.hip -- ssde_smooth: the fixed-interval smoother of the Kalman families, and
 // ssde_smooth_draws: joint posterior draws of the state path from the same records, and ssde_predict: the smoothed
-// state between and after the rows from them.
+// state between and after the rows from them, and ssde_path_stats / ssde_path_occupancy: reductions of the drawn paths
+// on the device.
 //
 // A forward pass in record mode (dense_kernel MODE 2 on the tiled routes, smooth_tv_record_kernel on PATH_TV) writes every state
 // row's record, smooth_back_kernel walks them back and writes the smoothed mean, covariance and whitened innovation in the long
@@ -14,6 +15,7 @@
 #include <tuple>
 
 #include "ssde_engine.hpp"
+#include "ssde_occ.hpp"
 #include "ssde_predict.hpp"
 #include "ssde_smooth_plan.hpp"
 
@@ -310,6 +312,103 @@ int path_sharded(ssde_handle* parent, const double* par, uint64_t seed, int64_t 
     return SSDE_OK;
 }
 
+// ---- ssde_path_occupancy ------------------------------------------------------------------------------------------------------
+// One engine's occupancy counts, ADDED to `counts` [nx * ny * n_groups, then n_groups for the weight outside] in host memory, in
+// quanta of 2^e: the draws' walk with the stores replaced by integer adds (k_path_occ.hip).  weight / group: the engine's own rows /
+// tracks (host) or NULL; track0 as path_single's.  The counts are integers, so chunks, batches and shards add up exactly.
+int occ_single(ssde_handle* h, const double* par, uint64_t seed, int64_t draw0, int n_draws, const ssde_occ_grid& grid,
+               const double* weight, const int32_t* group, int n_groups, int e, bool force_global, std::vector<uint64_t>& counts,
+               int64_t track0) {
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(0));
+    RecordRun run;
+    if (int st = run.setup(h, par, "ssde_path_occupancy")) return st;
+    const int64_t nt = run.nt, n = h->n, nl = run.n_lanes;
+    const int64_t ncell = (int64_t)grid.nx * grid.ny;
+    if ((int64_t)h->lane_seg.n < nl) { h->err = "ssde_path_occupancy: the handle holds no track ordinals for its lanes"; return SSDE_ERR_ARG; }
+    h->last_occ_form = 0;
+    if (h->n_seg == 0 || nl == 0) return SSDE_OK;
+    // every lane's output grid, and from them every wavefront group's form
+    std::vector<int64_t> lseg((size_t)nl);
+    std::vector<int32_t> lns((size_t)nl), lgrp((size_t)nl, -1);
+    HIPCHK(h, hipMemcpy(lseg.data(), h->lane_seg.p, (size_t)nl * 8, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(lns.data(), run.s.lane_ns, (size_t)nl * 4, hipMemcpyDeviceToHost));
+    for (int64_t l = 0; l < nl; l++)
+        if (lns[l] > 0 && lseg[l] >= 0 && lseg[l] < h->n_seg) lgrp[l] = group ? group[lseg[l]] : 0;
+    const std::vector<int32_t> grp_of = plan_occ_groups(lgrp, WAVE, ncell, OCC_TILE_CELLS, force_global, OCC_GROUP_MIXED);
+    DevBuf<uint64_t> wb;
+    DevBuf<unsigned long long> acc;
+    DevBuf<int32_t> lg, go;
+    DevBuf<int64_t> map;
+    Release guard(wb, acc, lg, go, map);
+    OccArgs a;
+    memset(&a, 0, sizeof(a));
+    if (weight && n > 0) {                                              // quantised and uploaded piece by piece: no second [n] array on the host
+        const int64_t piece = (int64_t)1 << 20;
+        std::vector<uint64_t> wq((size_t)std::min(n, piece));
+        HIPCHK(h, wb.alloc((size_t)n));
+        for (int64_t i0 = 0; i0 < n; i0 += piece) {
+            const int64_t m = std::min(piece, n - i0);
+            occ_quantise_all(weight + i0, m, e, wq.data());
+            HIPCHK(h, hipMemcpy(wb.p + i0, wq.data(), (size_t)m * 8, hipMemcpyHostToDevice));
+        }
+        a.wq = wb.p;
+    }
+    a.unit = occ_quantise(1.0, e);
+    HIPCHK(h, lg.upload(lgrp));
+    HIPCHK(h, go.upload(grp_of));
+    const size_t n_acc = (size_t)ncell * n_groups + (size_t)n_groups;
+    HIPCHK(h, acc.alloc(n_acc));
+    HIPCHK(h, hipMemset(acc.p, 0, n_acc * 8));
+    if (nt != n) {                                                      // the caller's row OF each lattice row
+        HIPCHK(h, map.alloc((size_t)nt));
+        HIPCHK(h, launch_path_row_map(h->pad_row.p, n, nt, map.p, 0));
+        a.row_map = map.p;
+    }
+    a.d.lane_trk = h->lane_seg.p; a.d.track0 = track0; a.d.seed = seed; a.d.col0 = 0;
+    a.grid.x0 = grid.x0; a.grid.dx = grid.dx; a.grid.y0 = grid.y0; a.grid.dy = grid.dy; a.grid.nx = grid.nx; a.grid.ny = grid.ny;
+    a.lane_grp = lg.p; a.grp_of = go.p; a.acc = acc.p; a.acc_out = acc.p + (size_t)ncell * n_groups;
+    const int nb_cap = occ_batch_cap(OCC_NW, DRAW_CH, n_draws);
+    int forms = 0;
+    for (int k0 = 0; k0 < n_draws; k0 += nb_cap) {
+        a.d.draw0 = (uint32_t)(draw0 + k0); a.d.n_draws = std::min(nb_cap, n_draws - k0);
+        for (size_t c = 0; c < run.n_chunks(); c++) {
+            if (int st = run.produce_for_batch(c)) return st;
+            a.d.s = run.s;
+            bool tile = false, global = false;
+            for (int g = run.cut[c]; g < run.cut[c + 1]; g++) {              // (a group none of whose lanes takes part runs neither form)
+                if (grp_of[g] == OCC_GROUP_MIXED) global = true;
+                else if (grp_of[g] >= 0) tile = true;
+            }
+            if (tile) HIPCHK(h, launch_path_occ(a, true, 0));
+            if (global) HIPCHK(h, launch_path_occ(a, false, 0));
+            forms |= (tile ? 1 : 0) | (global ? 2 : 0);
+        }
+    }
+    std::vector<uint64_t> got(n_acc);
+    HIPCHK(h, hipMemcpy(got.data(), acc.p, n_acc * 8, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipStreamSynchronize(0));
+    for (size_t i = 0; i < n_acc; i++) counts[i] += got[i];
+    h->last_occ_form = forms;
+    return SSDE_OK;
+}
+
+// the track shards' counts: each shard reads its own slice of the weights and of the groups, counts its deviates by the GLOBAL track
+// ordinal and adds into the same integers; the quantum is the parent's
+int occ_sharded(ssde_handle* parent, const double* par, uint64_t seed, int64_t draw0, int n_draws, const ssde_occ_grid& grid,
+                const double* weight, const int32_t* group, int n_groups, int e, bool force_global, std::vector<uint64_t>& counts) {
+    int64_t track0 = 0;
+    for (size_t k = 0; k < parent->shards.size(); k++) {
+        ssde_handle* sh = parent->shards[k];
+        const int64_t lo = parent->shard_row0[k];
+        int st = occ_single(sh, par, seed, draw0, n_draws, grid, weight ? weight + lo : nullptr, group ? group + track0 : nullptr, n_groups,
+                            e, force_global, counts, track0);
+        if (st) { parent->err = sh->err; return st; }
+        track0 += sh->n_seg;
+    }
+    return SSDE_OK;
+}
+
 // ---- ssde_predict -------------------------------------------------------------------------------------------------------------
 // One engine's queries.  plan_queries (ssde_smooth_plan.hpp) places them on the host; then, chunk by chunk: the record pass with side
 // rows, the walk that fills the chunk's packets, the query kernel.
@@ -518,6 +617,61 @@ int ssde_path_stats(ssde_handle* h, const double* par, int32_t n_par_full, uint6
     }
     if (!h->shards.empty()) return path_sharded(h, par, seed, draw0, n_draws, regions, n_regions, weight, stats);
     return path_single(h, par, seed, draw0, n_draws, regions, n_regions, weight, stats, 0);
+}
+
+int ssde_path_occupancy(ssde_handle* h, const double* par, int32_t n_par_full, uint64_t seed, int64_t draw0, int32_t n_draws,
+                        const ssde_occ_grid* grid, const double* weight, const int32_t* group, int32_t n_groups, double* occ,
+                        double* outside, uint32_t flags) {
+    if (!h || !par || !grid || !occ) { if (h) h->err = "ssde_path_occupancy: no parameter vector, no grid, or no output"; return SSDE_ERR_ARG; }
+    if (int st = check_par_len(h, n_par_full)) return st;
+    if (n_draws < 1 || draw0 < 0 || draw0 + (int64_t)n_draws >= ((int64_t)1 << 28)) {
+        h->err = "ssde_path_occupancy: n_draws >= 1, draw0 >= 0 and draw0 + n_draws < 2^28 are required";
+        return SSDE_ERR_ARG;
+    }
+    if (flags & ~(uint32_t)SSDE_OCC_FORCE_GLOBAL) { h->err = "ssde_path_occupancy: unknown flag"; return SSDE_ERR_ARG; }
+    if (grid->nx < 1 || grid->nx > 4096 || grid->ny < 1 || grid->ny > 4096) { h->err = "ssde_path_occupancy: nx and ny must be 1 ... 4096"; return SSDE_ERR_ARG; }
+    if (n_groups < 1 || (int64_t)grid->nx * grid->ny * (int64_t)n_groups > ((int64_t)1 << 28)) {
+        h->err = "ssde_path_occupancy: n_groups >= 1 and nx * ny * n_groups <= 2^28 are required";
+        return SSDE_ERR_ARG;
+    }
+    if (!group && n_groups != 1) { h->err = "ssde_path_occupancy: without a group table there is one group"; return SSDE_ERR_ARG; }
+    if (int st = check_kalman(h)) return st;
+    if (h->d > 2) {
+        h->err = "ssde_path_occupancy: a response of three or more columns is not served, as column pairs or as one coupled filter (a cell needs the position columns in one lane)";
+        return SSDE_ERR_MODEL;
+    }
+    if (h->d == 1 && grid->ny != 1) { h->err = "ssde_path_occupancy: one position column takes ny = 1"; return SSDE_ERR_ARG; }
+    if (!std::isfinite(grid->x0) || !std::isfinite(grid->dx) || grid->dx <= 0.0 ||
+        (h->d == 2 && (!std::isfinite(grid->y0) || !std::isfinite(grid->dy) || grid->dy <= 0.0))) {
+        h->err = "ssde_path_occupancy: the grid's origin must be finite and its steps finite and positive";
+        return SSDE_ERR_ARG;
+    }
+    for (int64_t t = 0; group && t < h->n_seg; t++)
+        if (group[t] < -1 || group[t] >= n_groups) { h->err = "ssde_path_occupancy: a group outside -1 ... n_groups - 1"; return SSDE_ERR_ARG; }
+    double wmax = weight ? 0.0 : 1.0;
+    for (int64_t i = 0; weight && i < h->n; i++) {
+        if (!(weight[i] >= 0.0 && weight[i] <= std::numeric_limits<double>::max())) {      // negative, NaN or inf
+            h->err = "ssde_path_occupancy: a weight that is negative or not finite";
+            return SSDE_ERR_ARG;
+        }
+        wmax = std::max(wmax, weight[i]);
+    }
+    // the quantum of the whole handle's call; the counts of every engine, chunk and batch add up as integers
+    const int e = occ_quantum_exp(wmax, h->n, n_draws);
+    const bool force_global = (flags & SSDE_OCC_FORCE_GLOBAL) != 0;
+    const size_t n_cells = (size_t)grid->nx * grid->ny * n_groups;
+    std::vector<uint64_t> counts(n_cells + (size_t)n_groups, 0);
+    const int st = h->shards.empty() ? occ_single(h, par, seed, draw0, n_draws, *grid, weight, group, n_groups, e, force_global, counts, 0)
+                                     : occ_sharded(h, par, seed, draw0, n_draws, *grid, weight, group, n_groups, e, force_global, counts);
+    if (st) return st;
+    for (size_t i = 0; i < n_cells; i++) occ[i] = ldexp((double)counts[i], e);
+    for (int g = 0; outside && g < n_groups; g++) outside[g] = ldexp((double)counts[n_cells + g], e);
+    return SSDE_OK;
+}
+
+int ssde_last_occupancy_form(const ssde_handle* h) {
+    if (!h) return -1;
+    return h->shards.empty() ? h->last_occ_form : h->shards[0]->last_occ_form;
 }
 
 int ssde_predict(ssde_handle* h, const double* par, int32_t n_par_full, const int64_t* q_row, const double* q_off, int64_t n_query,

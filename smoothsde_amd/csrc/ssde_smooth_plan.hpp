@@ -1,5 +1,6 @@
 // ssde_smooth_plan.hpp -- the host-side plans of the calls that consume the smoother's records (ssde_engine_smooth.hip): how the
-// groups are cut into chunks under the budget, how many draws go into one batch, and where every query of ssde_predict lands.
+// groups are cut into chunks under the budget, how many draws go into one batch, which form every wavefront group of
+// ssde_path_occupancy runs, and where every query of ssde_predict lands.
 // Plain C++17, no HIP: the engine uploads and launches what these return, tests/hostsim/hostsim_predict.cpp exports them to
 // tests/test_smooth_plan_host.py.
 #ifndef SSDE_SMOOTH_PLAN_HPP
@@ -8,6 +9,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <limits>
 #include <vector>
 
 #include "ssde_predict.hpp"
@@ -32,6 +34,34 @@ inline std::vector<int> chunk_groups(const std::vector<int64_t>& goff, int64_t b
 inline int batch_cap(int64_t budget, int64_t per_draw, int unit, int ch, int n_draws) {
     int64_t nb = std::min<int64_t>(std::max<int64_t>(budget / std::max<int64_t>(per_draw, 1), unit), (int64_t)ch << 15);
     return (int)std::min<int64_t>(nb - nb % unit, n_draws);
+}
+
+// ---- ssde_path_occupancy -----------------------------------------------------------------------------------------
+// Draws per batch: the call keeps nothing per draw, so the only bound is one launch's second grid dimension -- batch_cap's, at ch
+// draws per wave -- in whole workgroups of nw * ch draws, and no more than the call asks for.
+inline int occ_batch_cap(int nw, int ch, int n_draws) {
+    return batch_cap(std::numeric_limits<int64_t>::max(), 1, nw * ch, ch, n_draws);
+}
+
+// The form of every wavefront group: lane_grp[l] is lane l's output grid (-1: the lane takes part in nothing; n_lanes of them, `wave`
+// a group).  A group whose lanes all feed ONE grid (or none) runs the tile form and gets that grid (-1: none) -- unless the grid's
+// cells pass tile_cells or the caller forces the global form; every other group gets `mixed`: the global form.
+inline std::vector<int32_t> plan_occ_groups(const std::vector<int32_t>& lane_grp, int wave, int64_t n_cells, int64_t tile_cells,
+                                            bool force_global, int32_t mixed) {
+    const int64_t nl = (int64_t)lane_grp.size();
+    std::vector<int32_t> grp_of((size_t)((nl + wave - 1) / wave), mixed);
+    if (force_global || n_cells > tile_cells) return grp_of;
+    for (size_t g = 0; g < grp_of.size(); g++) {
+        int32_t one = -1;
+        bool same = true;
+        for (int64_t l = (int64_t)g * wave; l < std::min<int64_t>((int64_t)(g + 1) * wave, nl); l++) {
+            if (lane_grp[l] < 0) continue;
+            if (one < 0) one = lane_grp[l];
+            same = same && lane_grp[l] == one;
+        }
+        if (same) grp_of[g] = one;
+    }
+    return grp_of;
 }
 
 // ---- ssde_predict's queries --------------------------------------------------------------------------------------

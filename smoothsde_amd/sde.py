@@ -543,12 +543,70 @@ class SDE:
         if isinstance(weight, str):
             if weight != "dt":
                 raise ValueError('weight must be "dt", an array or None')
-            ids, t = np.asarray(self.data_["ID"]), np.asarray(self.data_["time"], dtype=np.float64)
-            weight = np.zeros(len(t))
-            same = ids[1:] == ids[:-1]
-            weight[:-1][same] = (t[1:] - t[:-1])[same]
+            weight = self._dt_weights()
         st = self.engine_.path_stats(self._current_par_full(), n_draws, seed=seed, regions=regions, weight=weight)
         return {"length": st[:, :, 0], "displacement": st[:, :, 1], "in_region": st[:, :, 2:]}
+
+    def _dt_weights(self):
+        """the time from a row to its track's next row, 0 at a track's last row"""
+        ids, t = np.asarray(self.data_["ID"]), np.asarray(self.data_["time"], dtype=np.float64)
+        weight = np.zeros(len(t))
+        same = ids[1:] == ids[:-1]
+        weight[:-1][same] = (t[1:] - t[:-1])[same]
+        return weight
+
+    def utilisation(self, n_draws, seed=0, cells=(64, 64), extent=None, by=None, weight="dt"):
+        """The utilisation distribution of a state-space model (CTCRW, OU_SSM, BM_SSM) at the current parameters: the share of the
+        weighted time that the posterior state paths spend in every cell of a regular grid, summed on the device
+        (ssde_path_occupancy).  `cells`: (nx, ny) (an integer, or ny = 1, for one response column); `extent`:
+        (x_lo, x_hi, y_lo, y_hi), or None for the bounding box of the observed positions widened by 5 % on each side; `by`: None
+        pools every track, "ID" gives one grid per track, an integer array one group label per track (-1: left out); `weight`
+        as path_summary's.  {"x_edges": (nx + 1,), "y_edges": (ny + 1,), "density": (n_groups, ny, nx), "outside": (n_groups,)}:
+        the sums divided per group by n_draws times the group's total weight, so density and outside together sum to 1 (NaN
+        for a group without weight).  The draws are those of sample_states(n_draws, seed)."""
+        if self.type_ not in ("CTCRW", "OU_SSM", "BM_SSM"):
+            raise NotImplementedError(f"utilisation: no latent state in the model {self.type_!r}")
+        pb = self.problem_
+        d = pb.n_dim
+        if d > 2:
+            raise NotImplementedError("utilisation: one or two response columns")
+        nx, ny = (int(cells), 1) if np.isscalar(cells) else (int(cells[0]), int(cells[1]) if d == 2 and len(cells) > 1 else 1)
+        if extent is None:
+            Z = np.asarray(self.obs(), dtype=np.float64).reshape(len(pb.times), -1)
+            lo, hi = np.nanmin(Z, axis=0), np.nanmax(Z, axis=0)
+            pad = 0.05 * np.where(hi > lo, hi - lo, 1.0)
+            ext = np.column_stack([lo - pad, hi + pad])
+        else:
+            ext = np.asarray(extent, dtype=np.float64).reshape(-1, 2)
+        grid = {"x0": ext[0, 0], "dx": (ext[0, 1] - ext[0, 0]) / nx, "nx": nx}
+        if d == 2:
+            grid.update(y0=ext[1, 0], dy=(ext[1, 1] - ext[1, 0]) / ny, ny=ny)
+        if isinstance(weight, str):
+            if weight != "dt":
+                raise ValueError('weight must be "dt", an array or None')
+            weight = self._dt_weights()
+        n_seg = pb.n_seg
+        if by is None:
+            group = None
+        elif isinstance(by, str):
+            if by != "ID":
+                raise ValueError('by must be None, "ID" or one integer label per track')
+            group = np.arange(n_seg, dtype=np.int32)
+        else:
+            group = np.ascontiguousarray(by, dtype=np.int32)
+        occ, outside = self.engine_.path_occupancy(self._current_par_full(), n_draws, grid, seed=seed, weight=weight, group=group)
+        # the total weight of every group's state rows (a track's first row carries no state)
+        start = np.asarray(pb.seg_start, dtype=np.int64)
+        w = np.ones(len(pb.times)) if weight is None else np.array(weight, dtype=np.float64)
+        w[start] = 0.0
+        per_track = np.add.reduceat(w, start)
+        labels = np.zeros(n_seg, dtype=np.int64) if group is None else group.astype(np.int64)
+        total = np.bincount(labels[labels >= 0], weights=per_track[labels >= 0], minlength=len(outside)) * n_draws
+        with np.errstate(invalid="ignore", divide="ignore"):
+            density, out = occ / total[:, None, None], outside / total
+        return {"x_edges": grid["x0"] + grid["dx"] * np.arange(nx + 1),
+                "y_edges": (grid["y0"] + grid["dy"] * np.arange(ny + 1)) if d == 2 else np.array([-np.inf, np.inf]),
+                "density": density, "outside": out}
 
     def residuals(self):
         """Model residuals, iid N(0, 1) under the model (one column per response variable).
