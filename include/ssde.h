@@ -33,6 +33,8 @@
  *                         inside up to eight boxes per track and draw, without a draw leaving the device
  *   ssde_path_occupancy <- (new) the weighted time those draws spend in every cell of a regular grid, pooled over draws and over
  *                         groups of tracks: a utilisation distribution, summed on the device as integers and so bitwise reproducible
+ *   ssde_predict_draws <- (new) those draws' states at any time between or after the rows: the same paths as ssde_smooth_draws,
+ *                         refined by Gaussian bridges inside the intervals and simulated past a track's last row, without NA rows
  *   ssde_penalty       <- smoothing penalty     (nllk_ctcrw.hpp:254-280, nllk_sde.hpp:89-124)
  *   ssde_info          <- InfoADFunObject       (src/init.c:7)
  *   ssde_forget        <- (new) drops the memo of ssde_eval
@@ -373,6 +375,25 @@ int ssde_smooth_draws(ssde_handle *h, const double *par, int32_t n_par_full, uin
  * wavefront groups under SSDE_OPT_SMOOTH_BUDGET_MB, and the result does not depend on the chunking. */
 int ssde_predict(ssde_handle *h, const double *par, int32_t n_par_full, const int64_t *q_row, const double *q_off, int64_t n_query,
                  double *a_pred, double *P_pred);
+
+/* Joint posterior draws of the state at any time at `par` (definitions: DESIGN.md §3.14).  Queries are ssde_predict's: query k is
+ * (q_row[k], q_off[k]), a caller's row (0-based) and an offset >= 0 past its time stamp; they may come in any order, repeat and share
+ * intervals.  Draw q is draw number draw0 + q of the stream `seed` and it is THE SAME PATH ssde_smooth_draws, ssde_path_stats and
+ * ssde_path_occupancy use for that seed and draw number: the states at the rows are theirs (offset 0 returns the row's draw and an
+ * offset equal to the interval the next row's, bitwise), and the call adds the states between them -- a Gaussian bridge between the
+ * draw's states at the two rows around the query, with row q_row[k]'s covariates -- and after a track's last row.
+ *   draws_at [n_query x sdim x n_draws]: element (k, c, q) at k + n_query * (c + sdim * q); columns as in a_pred.
+ * The offsets of one interval must go into ONE call to be jointly distributed: an answer is a pure function of the seed, the track,
+ * the row, the draw number and the SET of distinct offsets of its interval in this call (each offset is drawn given the one below
+ * it).  It does not depend on the order of the queries, their duplicates, the other intervals' queries, SSDE_OPT_SMOOTH_BUDGET_MB,
+ * how the draws are batched or cut over calls, the devices or the column pairs.
+ * NaN in every column of a query, with status SSDE_OK, exactly where ssde_predict gives NaN, and wherever the draw itself is NaN at an
+ * end the answer depends on.  SSDE_ERR_ARG as for ssde_predict's query arguments and ssde_smooth_draws' draw arguments, for
+ * flags != 0, and for a handle with 2^32 or more tracks or an interval with 2^32 or more distinct offsets; SSDE_ERR_MODEL exactly where
+ * ssde_smooth_draws gives it.  Multi-device handles, column pairs, lattice-padded handles and row-varying parameters are served.
+ * Leaves the memo, the window state, the TV records, n_evals / n_memo_hits and every later result of the other calls as they were. */
+int ssde_predict_draws(ssde_handle *h, const double *par, int32_t n_par_full, const int64_t *q_row, const double *q_off, int64_t n_query,
+                       uint64_t seed, int64_t draw0, int32_t n_draws, double *draws_at, uint32_t flags);
 
 /* Summaries of posterior state paths at `par`, reduced on the device (definitions: DESIGN.md §3.12).  Draw q is draw number draw0 + q
  * of the stream `seed`: exactly the path ssde_smooth_draws returns for it.  A track's state rows are the CALLER's rows first + 1 ..

@@ -498,6 +498,9 @@ def load_library():
     lib.ssde_smooth_draws.restype = C.c_int
     lib.ssde_predict.argtypes = [C.c_void_p, _dp, C.c_int32, C.POINTER(C.c_int64), _dp, C.c_int64, _dp, _dp]
     lib.ssde_predict.restype = C.c_int
+    lib.ssde_predict_draws.argtypes = [C.c_void_p, _dp, C.c_int32, C.POINTER(C.c_int64), _dp, C.c_int64, C.c_uint64, C.c_int64, C.c_int32,
+                                       _dp, C.c_uint32]
+    lib.ssde_predict_draws.restype = C.c_int
     lib.ssde_path_stats.argtypes = [C.c_void_p, _dp, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, _dp, C.c_int32, _dp, _dp, C.c_uint32]
     lib.ssde_path_stats.restype = C.c_int
     lib.ssde_path_occupancy.argtypes = [C.c_void_p, _dp, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.POINTER(SsdeOccGrid), _dp,
@@ -582,7 +585,7 @@ WINDOW_TOL = 1e-11  # largest tolerated relative hand-over disagreement between 
 
 EXPORTED_SYMBOLS = ("ssde_create", "ssde_eval", "ssde_eval_device", "ssde_penalty", "ssde_report", "ssde_widen_windows", "ssde_relax_windows",
                     "ssde_info", "ssde_destroy", "ssde_last_error", "ssde_abi_version", "ssde_comm_unique_id", "ssde_comm_init_rank", "ssde_forget", "ssde_laplace_eval", "ssde_last_kernel_ms", "ssde_kernel_ms_history",
-                    "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth", "ssde_smooth_draws", "ssde_predict", "ssde_path_stats", "ssde_path_occupancy", "ssde_last_occupancy_form",
+                    "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth", "ssde_smooth_draws", "ssde_predict", "ssde_predict_draws", "ssde_path_stats", "ssde_path_occupancy", "ssde_last_occupancy_form",
                     "ssde_lagstats_host_m", "ssde_lagstats_read_m", "ssde_lagforms_host_m", "ssde_reduce_host", "ssde_last_finish_form", "ssde_last_gain_feed", "ssde_last_gain_rows")
 
 
@@ -974,6 +977,25 @@ class Engine:
         self._check(self.lib.ssde_predict(self._h, par.ctypes.data_as(_dp), self.n_par_full, rows.ctypes.data_as(C.POINTER(C.c_int64)),
                                           offsets.ctypes.data_as(_dp), m, mean.ctypes.data_as(_dp), P.ctypes.data_as(_dp) if cov else None))
         return {"mean": mean, "cov": P}
+
+    def predict_draws(self, par, rows, offsets, n_draws: int, seed: int = 0, draw0: int = 0):
+        """Joint posterior draws of the state at any time at `par` (ssde_predict_draws): an array of shape
+        (n_draws, n_query, sdim).  Queries as predict's; draw k is draw number draw0 + k of the stream `seed`, the path smooth_draws
+        returns for it, refined inside the intervals and continued past a track's last row.  The offsets of one interval must go
+        into one call to be jointly distributed.  NaN where predict gives NaN."""
+        par = np.ascontiguousarray(par, dtype=np.float64)
+        if par.shape != (self.n_par_full,):
+            raise ValueError(f"par must have length {self.n_par_full}")
+        rows = np.ascontiguousarray(rows, dtype=np.int64).ravel()
+        offsets = np.ascontiguousarray(offsets, dtype=np.float64).ravel()
+        if rows.shape != offsets.shape:
+            raise ValueError("rows and offsets must have the same length")
+        m, sd = len(rows), self.problem.sdim
+        buf = np.zeros((max(int(n_draws), 0), sd, m))                                  # element (k, c, q) at k + m (c + sdim q)
+        self._check(self.lib.ssde_predict_draws(self._h, par.ctypes.data_as(_dp), self.n_par_full, rows.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                offsets.ctypes.data_as(_dp), m, int(seed), int(draw0), int(n_draws),
+                                                buf.ctypes.data_as(_dp), 0))
+        return buf.transpose(0, 2, 1)
 
     def path_stats(self, par, n_draws: int, seed: int = 0, draw0: int = 0, regions=None, weight=None):
         """Summaries of posterior state paths at `par`, reduced on the device (ssde_path_stats): an array of shape

@@ -685,6 +685,29 @@ int predict_packet_doubles(int model, int d);
 int predict_side_doubles(int model, int d);
 hipError_t launch_predict_walk(const PredictArgs& a, hipStream_t s);
 hipError_t launch_predict_query(const PredictArgs& a, hipStream_t s);
+// ---- joint draws of the state at any time (k_predict_draws.hip, ssde_bridge.hpp) ----
+// The draws of a DrawArgs `d` (its out / draw_stride are not read) and the wanted steps of a PredictArgs.  The walk stores, for draw q
+// of the batch and slot i, double k of the ends at ends + (q * 2 sdim + k) * pk_stride + (i - slot0) and double k of the slot's side
+// packet at sidepk + k * pk_stride + (i - slot0).  The query kernel's lane (slot i, draw q) chains the slot's distinct offsets
+// off_val[off_ptr[i] .. off_ptr[i + 1]) and writes answer g (an index into off_val) to the caller's queries q_dest[q_ptr[g] ..
+// q_ptr[g + 1]): element (k, c, q) of out [n_query x sdim x n_draws of the batch] at k + n_query * (c + sdim * q).
+struct PredictDrawArgs {
+    DrawArgs d;
+    const int64_t* want_off;     // [n_lanes + 1]
+    const int32_t* want_step;    // [n_slots]
+    double* ends;
+    double* sidepk;
+    int64_t slot0, pk_stride;    // the chunk's first slot and its slots
+    const int64_t* slot_lane;    // [n_slots]: the slot's lane (its track ordinal: d.lane_trk)
+    const int64_t* off_ptr;      // [n_slots + 1]
+    const double* off_val;       // [n_distinct]
+    const int64_t* q_ptr;        // [n_distinct + 1]
+    const int64_t* q_dest;       // [n_valid]
+    int64_t n_query;
+    double* out;
+};
+hipError_t launch_predict_draws_walk(const PredictDrawArgs& a, hipStream_t s);
+hipError_t launch_predict_draws_query(const PredictDrawArgs& a, hipStream_t s);
 hipError_t launch_tv_a0(const TvArgs& a, const double* a0_src, const int64_t* trk_seg, int64_t n_seg, int sdim,
                         double* a0_dst, hipStream_t s);
 hipError_t launch_tv_prepare(const TvArgs& a, hipStream_t s);

@@ -1,7 +1,7 @@
 // ssde_engine_smooth.hip -- ssde_smooth: the fixed-interval smoother of the Kalman families, and
 // ssde_smooth_draws: joint posterior draws of the state path from the same records, and ssde_predict: the smoothed
 // state between and after the rows from them, and ssde_path_stats / ssde_path_occupancy: reductions of the drawn paths
-// on the device.
+// on the device, and ssde_predict_draws: the drawn paths refined between and after the rows.
 //
 // A forward pass in record mode (dense_kernel MODE 2 on the tiled routes, smooth_tv_record_kernel on PATH_TV) writes every state
 // row's record, smooth_back_kernel walks them back and writes the smoothed mean, covariance and whitened innovation in the long
@@ -508,6 +508,117 @@ int predict_sharded(ssde_handle* parent, const double* par, const int64_t* q_row
     return SSDE_OK;
 }
 
+// ---- ssde_predict_draws -------------------------------------------------------------------------------------------------------
+// One engine's queries for n_draws draws into host memory [nq x sdim x n_draws].  predict_single's plan and chunks (the record pass
+// with side rows, chunks without a query skipped) under draws_single's batches: per batch and chunk the walk that stores the ends of
+// the wanted intervals, then the query kernel.  track0 / col0 as draws_single's.
+int predict_draws_single(ssde_handle* h, const double* par, const int64_t* q_row, const double* q_off, int64_t nq, uint64_t seed,
+                         int64_t draw0, int n_draws, double* draws_at, int64_t track0, int col0) {
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(0));
+    const int sd = h->sdim;
+    if (int st = check_not_coupled_wide(h, "ssde_predict_draws")) return st;
+    RecordRun run;
+    run.SW = predict_side_doubles(h->model, h->d);
+    if (run.SW <= 0) { h->err = "ssde_predict_draws: no kernels for this model and width"; return SSDE_ERR_MODEL; }
+    if (int st = run.setup(h, par, "ssde_predict_draws")) return st;
+    const int64_t nl = run.n_lanes, n = h->n;
+    if ((int64_t)h->lane_seg.n < nl) { h->err = "ssde_predict_draws: the handle holds no track ordinals for its lanes"; return SSDE_ERR_ARG; }
+
+    std::vector<int64_t> row0((size_t)nl), prow;
+    std::vector<int32_t> lns((size_t)nl);
+    if (nl) {
+        HIPCHK(h, hipMemcpy(row0.data(), run.s.lane_row0, (size_t)nl * 8, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(lns.data(), run.s.lane_ns, (size_t)nl * 4, hipMemcpyDeviceToHost));
+    }
+    if (run.nt != n) {
+        prow.resize((size_t)n);
+        HIPCHK(h, hipMemcpy(prow.data(), h->pad_row.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    }
+    const QueryPlan P = plan_queries(row0, lns, run.nt != n ? prow.data() : nullptr, h->pad_step, q_row, q_off, nq);
+    const SlotOffsets S = plan_slot_offsets(P);
+    if (S.most >= ((int64_t)1 << 32)) { h->err = "ssde_predict_draws: an interval with 2^32 or more distinct offsets"; return SSDE_ERR_ARG; }
+    const size_t per_draw = (size_t)nq * sd;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    if (P.order.empty()) { std::fill(draws_at, draws_at + per_draw * n_draws, nan); return SSDE_OK; }
+
+    const int64_t n_slots = (int64_t)P.want_step.size();
+    std::vector<int64_t> slot_lane((size_t)n_slots);
+    for (int64_t l = 0; l < nl; l++)
+        for (int64_t i = P.want_off[l]; i < P.want_off[l + 1]; i++) slot_lane[(size_t)i] = l;
+    int64_t most = 0;
+    for (size_t c = 0; c < run.n_chunks(); c++) {
+        const QueryRange r = chunk_queries(P, run.cut[c], run.cut[c + 1], WAVE);
+        most = std::max(most, r.s1 - r.s0);
+    }
+    DevBuf<double> out, ends, sidepk, offv;
+    DevBuf<int64_t> wo, sl, op, qp, qd;
+    DevBuf<int32_t> ws;
+    Release guard(out, ends, sidepk, offv, wo, sl, op, qp, qd, ws);
+    HIPCHK(h, wo.upload(P.want_off)); HIPCHK(h, ws.upload(P.want_step)); HIPCHK(h, sl.upload(slot_lane));
+    HIPCHK(h, op.upload(S.off_ptr)); HIPCHK(h, offv.upload(S.off_val)); HIPCHK(h, qp.upload(S.q_ptr)); HIPCHK(h, qd.upload(S.q_dest));
+    // draws per batch: what fits beside the records and side rows (the free memory asked for again, as draws_single does)
+    int64_t budget = run.budget;
+    if (h->smooth_budget_mb <= 0) if (int st = free_budget(h, budget)) return st;
+    const int nb_cap = predict_draws_batch_cap(budget, most, sd, nq, DRAW_CH, n_draws);
+    HIPCHK(h, out.alloc(per_draw * nb_cap));
+    HIPCHK(h, ends.alloc((size_t)most * 2 * sd * nb_cap));
+    HIPCHK(h, sidepk.alloc((size_t)most * run.SW));
+    PredictDrawArgs a;
+    memset(&a, 0, sizeof(a));
+    a.d.lane_trk = h->lane_seg.p; a.d.track0 = track0; a.d.seed = seed; a.d.col0 = col0;
+    a.want_off = wo.p; a.want_step = ws.p; a.ends = ends.p; a.sidepk = sidepk.p; a.slot_lane = sl.p;
+    a.off_ptr = op.p; a.off_val = offv.p; a.q_ptr = qp.p; a.q_dest = qd.p; a.n_query = nq; a.out = out.p;
+    for (int k0 = 0; k0 < n_draws; k0 += nb_cap) {
+        const int nb = std::min(nb_cap, n_draws - k0);
+        HIPCHK(h, hipMemset(out.p, 0xff, per_draw * nb * 8));             // NaN (all bits set) where no query writes
+        a.d.draw0 = (uint32_t)(draw0 + k0); a.d.n_draws = nb;
+        for (size_t c = 0; c < run.n_chunks(); c++) {
+            const QueryRange r = chunk_queries(P, run.cut[c], run.cut[c + 1], WAVE);
+            if (r.s1 == r.s0) continue;                                   // no query on this chunk's tracks
+            if (int st = run.produce_for_batch(c)) return st;
+            a.d.s = run.s;
+            a.slot0 = r.s0; a.pk_stride = r.s1 - r.s0;
+            HIPCHK(h, launch_predict_draws_walk(a, 0));
+            HIPCHK(h, launch_predict_draws_query(a, 0));
+        }
+        HIPCHK(h, hipMemcpy(draws_at + per_draw * k0, out.p, per_draw * nb * 8, hipMemcpyDeviceToHost));
+    }
+    HIPCHK(h, hipStreamSynchronize(0));
+    return SSDE_OK;
+}
+
+// the shards' and column pairs' queries: each engine gets the queries on its rows (predict_sharded's deal), counts its deviates by the
+// GLOBAL track ordinal and state column (draws_sharded's) and its columns land in the parent's layout
+int predict_draws_sharded(ssde_handle* parent, const double* par, const int64_t* q_row, const double* q_off, int64_t nq, uint64_t seed,
+                          int64_t draw0, int n_draws, double* draws_at) {
+    const int SD = parent->sdim, P = std::max(parent->n_dim_parts, 1);
+    std::fill(draws_at, draws_at + (size_t)nq * SD * n_draws, std::numeric_limits<double>::quiet_NaN());
+    int64_t track0 = 0;
+    for (size_t k = 0; k < parent->shards.size(); k++) {
+        ssde_handle* sh = parent->shards[k];
+        const int64_t lo = parent->shard_row0[k], m = parent->shard_nrows[k];
+        const int sd = sh->sdim, c0 = parent->shard_col0[k];
+        std::vector<int64_t> idx, rows;
+        std::vector<double> offs;
+        for (int64_t i = 0; i < nq; i++)
+            if (q_row[i] >= lo && q_row[i] < lo + m) { idx.push_back(i); rows.push_back(q_row[i] - lo); offs.push_back(q_off[i]); }
+        const int64_t mq = (int64_t)idx.size();
+        if (mq > 0) {
+            std::vector<double> t((size_t)mq * sd * n_draws);
+            int st = check_kalman(sh);
+            if (!st) st = predict_draws_single(sh, par, rows.data(), offs.data(), mq, seed, draw0, n_draws, t.data(), track0, c0);
+            if (st) { parent->err = sh->err; return st; }
+            for (int q = 0; q < n_draws; q++)
+                for (int c = 0; c < sd; c++)
+                    for (int64_t i = 0; i < mq; i++)
+                        draws_at[(size_t)nq * ((c0 + c) + (size_t)SD * q) + idx[i]] = t[(size_t)mq * (c + (size_t)sd * q) + i];
+        }
+        if ((k + 1) % P == 0) track0 += sh->n_seg;                          // the next track shard's first ordinal
+    }
+    return SSDE_OK;
+}
+
 }  // namespace
 
 namespace ssde_engine {
@@ -686,6 +797,40 @@ int ssde_predict(ssde_handle* h, const double* par, int32_t n_par_full, const in
     if (int st = check_kalman(h)) return st;
     if (!h->shards.empty()) return predict_sharded(h, par, q_row, q_off, n_query, a_pred, P_pred);
     return predict_single(h, par, q_row, q_off, n_query, a_pred, P_pred);
+}
+
+int ssde_predict_draws(ssde_handle* h, const double* par, int32_t n_par_full, const int64_t* q_row, const double* q_off, int64_t n_query,
+                       uint64_t seed, int64_t draw0, int32_t n_draws, double* draws_at, uint32_t flags) {
+    if (!h || !par || !q_row || !q_off || !draws_at) { if (h) h->err = "ssde_predict_draws: no parameter vector, no queries, or no output"; return SSDE_ERR_ARG; }
+    if (int st = check_par_len(h, n_par_full)) return st;
+    if (n_query < 1) { h->err = "ssde_predict_draws: n_query >= 1 is required"; return SSDE_ERR_ARG; }
+    for (int64_t k = 0; k < n_query; k++) {
+        if (q_row[k] < 0 || q_row[k] >= h->n) { h->err = "ssde_predict_draws: a query row outside [0, n)"; return SSDE_ERR_ARG; }
+        if (!std::isfinite(q_off[k]) || q_off[k] < 0.0) { h->err = "ssde_predict_draws: a query offset that is negative or not finite"; return SSDE_ERR_ARG; }
+    }
+    if (n_draws < 1 || draw0 < 0 || draw0 + (int64_t)n_draws >= ((int64_t)1 << 28)) {
+        h->err = "ssde_predict_draws: n_draws >= 1, draw0 >= 0 and draw0 + n_draws < 2^28 are required";
+        return SSDE_ERR_ARG;
+    }
+    if (flags != 0) { h->err = "ssde_predict_draws: unknown flag"; return SSDE_ERR_ARG; }
+    // the bridge deviates' counter holds the track ordinal's low word and the rank of an offset in its interval, 32 bits each
+    if (h->n_seg >= ((int64_t)1 << 32)) { h->err = "ssde_predict_draws: 2^32 or more tracks"; return SSDE_ERR_ARG; }
+    if (n_query >= ((int64_t)1 << 32)) {
+        // (the distinct offsets of a slot are at most those of one caller's row, and one more)
+        std::vector<int64_t> by((size_t)n_query);
+        for (int64_t k = 0; k < n_query; k++) by[(size_t)k] = k;
+        std::sort(by.begin(), by.end(), [&](int64_t a, int64_t b) { return q_row[a] != q_row[b] ? q_row[a] < q_row[b] : q_off[a] < q_off[b]; });
+        int64_t run_len = 0;
+        for (int64_t k = 0; k < n_query; k++) {
+            if (k == 0 || q_row[by[k]] != q_row[by[k - 1]]) run_len = 1;
+            else if (q_off[by[k]] != q_off[by[k - 1]]) run_len++;
+            if (run_len + 1 >= ((int64_t)1 << 32)) { h->err = "ssde_predict_draws: an interval with 2^32 or more distinct offsets"; return SSDE_ERR_ARG; }
+        }
+    }
+    if (int st = check_kalman(h)) return st;
+    if (!h->shards.empty()) return predict_draws_sharded(h, par, q_row, q_off, n_query, seed, draw0, n_draws, draws_at);
+    if (int st = check_not_coupled_wide(h, "ssde_predict_draws")) return st;        // (every check before the device is touched)
+    return predict_draws_single(h, par, q_row, q_off, n_query, seed, draw0, n_draws, draws_at, 0, 0);
 }
 
 int ssde_smooth(ssde_handle* h, const double* par, int32_t n_par_full, double* a_smooth, double* P_smooth, double* resid) {

@@ -73,10 +73,11 @@ __device__ __forceinline__ RecLane rec_lane(const S& A) {
 
 // The draws' walk from the lane's last step to its first: the row's factors once per step, then CH paths (draws draw_first + q of
 // the stream `seed`, counted by `trk`) one step each.  on_row(row) runs once per state row, on_path(q, alpha) with path q's state
-// there.  Pass lambdas over the kernel's own locals: accumulators behind a functor's members cost path_stats_kernel its occupancy.
+// there.  smin (wave-uniform): the walk stops below that step (ssde_predict_draws: nothing under the lowest wanted step is asked for).
+// Pass lambdas over the kernel's own locals: accumulators behind a functor's members cost path_stats_kernel its occupancy.
 template <int MODEL, int D, int CH, class Row, class Path>
 __device__ __forceinline__ void rec_draw_walk(const RecLane& L, uint64_t seed, uint64_t trk, uint32_t draw_first, int col0,
-                                              Row&& on_row, Path&& on_path) {
+                                              Row&& on_row, Path&& on_path, int smin = 0) {
     typedef SmoothRec<MODEL, D> RC;
     typedef DrawFac<MODEL, D> FC;
     constexpr int SD = RC::SD;
@@ -87,7 +88,7 @@ __device__ __forceinline__ void rec_draw_walk(const RecLane& L, uint64_t seed, u
         for (int c = 0; c < SD; c++) al[q][c] = 0.0;
     DrawNext<SD> nx;
     draw_next_init<SD>(nx);
-    for (int s = L.smax - 1; s >= 0; s--) {
+    for (int s = L.smax - 1; s >= smin; s--) {
         if (s >= L.ns) continue;
         const RecRow rec = L.row<RC::R>(s);
         const bool tail = s == L.ns - 1;

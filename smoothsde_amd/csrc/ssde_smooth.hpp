@@ -22,6 +22,21 @@ struct SmoothRec {
     SSDE_HD static constexpr int up(int r, int c) { return r <= c ? c * (c + 1) / 2 + r : r * (r + 1) / 2 + c; }
 };
 
+// makeT's two coefficients over dt as smooth_record_row forms them below: CTCRW [[1, t12], [0, e]] per dimension, OU e I, BM I.  For
+// the bridges of ssde_predict_draws (ssde_bridge.hpp).  smooth_record_row and predict_query_row keep their own lines: routing them
+// through this function changes predict_query_kernel's register allocation, and their kernels stay as they are.
+template <int MODEL, int D>
+SSDE_HD void smooth_trans_coef(const DualN<0>* par, double dt, double& t12, double& e) {
+    t12 = 0.0; e = 1.0;
+    if (MODEL == M_CTCRW) {
+        const double tau = exp(par[D].v), beta = 1.0 / tau;
+        e = exp(-(beta * dt));
+        t12 = (1.0 - e) / beta;
+    } else if (MODEL == M_OU_SSM) {
+        e = exp(-dt / exp(par[D].v));
+    }
+}
+
 // The row's record, from the lane's state before dense_step.  par / H as dense_step takes them (values only).  Returns whether the
 // row takes an update (false: a NA row, or det F <= 0 -- what ssde_predict's side row tells apart).
 template <int MODEL, int D, class W>

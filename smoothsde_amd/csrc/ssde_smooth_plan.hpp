@@ -1,8 +1,8 @@
 // ssde_smooth_plan.hpp -- the host-side plans of the calls that consume the smoother's records (ssde_engine_smooth.hip): how the
 // groups are cut into chunks under the budget, how many draws go into one batch, which form every wavefront group of
-// ssde_path_occupancy runs, and where every query of ssde_predict lands.
+// ssde_path_occupancy runs, where every query of ssde_predict lands, and the distinct offsets of every slot of ssde_predict_draws.
 // Plain C++17, no HIP: the engine uploads and launches what these return, tests/hostsim/hostsim_predict.cpp exports them to
-// tests/test_smooth_plan_host.py.
+// tests/test_smooth_plan_host.py (and hostsim_predict_draws.cpp the last to tests/test_predict_draws_plan_host.py).
 #ifndef SSDE_SMOOTH_PLAN_HPP
 #define SSDE_SMOOTH_PLAN_HPP
 
@@ -139,6 +139,57 @@ inline QueryRange chunk_queries(const QueryPlan& P, int g_lo, int g_hi, int wave
     const int64_t s0 = P.want_off[l0], s1 = P.want_off[l1];
     return QueryRange{s0, s1, std::lower_bound(P.q_slot.begin(), P.q_slot.end(), s0) - P.q_slot.begin(),
                       std::lower_bound(P.q_slot.begin(), P.q_slot.end(), s1) - P.q_slot.begin()};
+}
+
+// ---- ssde_predict_draws' offsets ----------------------------------------------------------------------------------
+// Per slot, the distinct residual offsets of its queries in ascending order (a CSR list: slot i holds off_val[off_ptr[i] ..
+// off_ptr[i + 1]), entry r of it is the offset of rank r); per planned query, its rank in its slot's list; and per distinct offset
+// the queries that carry it: the caller's indices q_dest[q_ptr[g] .. q_ptr[g + 1]) for entry g of off_val.  Offsets compare as
+// doubles: equal ones (+0.0 and -0.0 too) share one rank and one answer.
+struct SlotOffsets {
+    std::vector<int64_t> off_ptr, q_rank, q_ptr, q_dest;
+    std::vector<double> off_val;
+    int64_t most = 0;                                               // the longest list
+};
+
+inline SlotOffsets plan_slot_offsets(const QueryPlan& P) {
+    const int64_t nv = (int64_t)P.order.size(), n_slots = (int64_t)P.want_step.size();
+    SlotOffsets S;
+    S.off_ptr.assign((size_t)n_slots + 1, 0);
+    S.q_rank.resize((size_t)nv);
+    S.q_dest.resize((size_t)nv);
+    S.q_ptr.push_back(0);
+    std::vector<int64_t> idx;
+    for (int64_t i0 = 0; i0 < nv;) {
+        int64_t i1 = i0;
+        while (i1 < nv && P.q_slot[i1] == P.q_slot[i0]) i1++;
+        idx.resize((size_t)(i1 - i0));
+        for (int64_t i = i0; i < i1; i++) idx[(size_t)(i - i0)] = i;
+        std::stable_sort(idx.begin(), idx.end(), [&](int64_t a, int64_t b) { return P.off[a] < P.off[b]; });
+        int64_t rank = -1;
+        for (size_t k = 0; k < idx.size(); k++) {
+            const int64_t i = idx[k];
+            if (k == 0 || P.off[i] != P.off[idx[k - 1]]) {
+                if (k > 0) S.q_ptr.push_back((int64_t)(i0 + k));
+                S.off_val.push_back(P.off[i]);
+                rank++;
+            }
+            S.q_rank[(size_t)i] = rank;
+            S.q_dest[(size_t)(i0 + k)] = P.order[(size_t)i];
+        }
+        S.q_ptr.push_back(i1);
+        S.off_ptr[(size_t)P.q_slot[i0] + 1] = rank + 1;
+        S.most = std::max(S.most, rank + 1);
+        i0 = i1;
+    }
+    for (int64_t i = 0; i < n_slots; i++) S.off_ptr[i + 1] += S.off_ptr[i];
+    return S;
+}
+
+// ssde_predict_draws' draws per batch through batch_cap: a draw costs the ends of every slot (2 SD doubles each) and its rows of the
+// output, next to the records and side rows the budget already pays for; any number of draws goes (unit 1), one always
+inline int predict_draws_batch_cap(int64_t budget, int64_t n_slots, int sd, int64_t n_query, int ch, int n_draws) {
+    return batch_cap(budget, n_slots * 2 * sd + n_query * sd, 1, ch, n_draws);
 }
 
 }  // namespace ssde_plan

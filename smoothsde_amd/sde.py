@@ -483,22 +483,15 @@ class SDE:
         out = self.engine_.smooth(self._current_par_full(), cov=cov, resid=False)
         return {"mean": out["mean"], "cov": out["cov"]}
 
-    def predict_states(self, ID, time, cov=True):
-        """Smoothed states of a state-space model (CTCRW, OU_SSM, BM_SSM) at any times, at the current parameters (ssde_predict,
-        DESIGN.md §3.11).  `ID` and `time` are arrays of equal length: query k asks for the state of track ID[k] at time[k].  Between two
-        rows of the track the state is interpolated (with the covariates of the row before), after its last row it is a forecast.
-        Returns {"mean": n_query x sdim, "cov": n_query x sdim x sdim or None}, columns as in smooth_states; NaN for an unknown ID
-        and for a time before the track's second time stamp (the first row carries no state)."""
-        if self.type_ not in ("CTCRW", "OU_SSM", "BM_SSM"):
-            raise NotImplementedError(f"predict_states: no latent state in the model {self.type_!r}")
-        if self.engine_ is None:
-            raise RuntimeError("call setup() or fit() first")
+    def _rows_and_offsets(self, ID, time):
+        """(rows, offsets) of the queries (ID[k], time[k]): the last row of track ID[k] with a time stamp <= time[k] and the time past
+        it; row -1 for an unknown ID, a time that is not finite or one before the track's first time stamp."""
         ID, time = np.asarray(ID).ravel(), np.asarray(time, dtype=np.float64).ravel()
         if ID.shape != time.shape:
             raise ValueError("ID and time must have the same length")
         ids = np.asarray(self.data_["ID"])
         t = np.asarray(self.data_["time"], dtype=np.float64)
-        n, m, sd = len(ids), len(ID), self.problem_.sdim
+        n, m = len(ids), len(ID)
         start = np.r_[0, np.nonzero(ids[1:] != ids[:-1])[0] + 1]
         end = np.r_[start[1:], n]
         seg_of = {}
@@ -512,11 +505,28 @@ class SDE:
             j = int(np.searchsorted(t[start[seg]:end[seg]], time[k], side="right")) - 1      # the last row with time <= the query's
             if j >= 0:
                 rows[k] = start[seg] + j
+        offs = np.zeros(m)
+        ok = rows >= 0
+        offs[ok] = time[ok] - t[rows[ok]]
+        return rows, offs
+
+    def predict_states(self, ID, time, cov=True):
+        """Smoothed states of a state-space model (CTCRW, OU_SSM, BM_SSM) at any times, at the current parameters (ssde_predict,
+        DESIGN.md §3.11).  `ID` and `time` are arrays of equal length: query k asks for the state of track ID[k] at time[k].  Between two
+        rows of the track the state is interpolated (with the covariates of the row before), after its last row it is a forecast.
+        Returns {"mean": n_query x sdim, "cov": n_query x sdim x sdim or None}, columns as in smooth_states; NaN for an unknown ID
+        and for a time before the track's second time stamp (the first row carries no state)."""
+        if self.type_ not in ("CTCRW", "OU_SSM", "BM_SSM"):
+            raise NotImplementedError(f"predict_states: no latent state in the model {self.type_!r}")
+        if self.engine_ is None:
+            raise RuntimeError("call setup() or fit() first")
+        rows, offs = self._rows_and_offsets(ID, time)
+        m, sd = len(rows), self.problem_.sdim
         ok = rows >= 0
         mean = np.full((m, sd), np.nan)
         P = np.full((m, sd, sd), np.nan) if cov else None
         if ok.any():
-            out = self.engine_.predict(self._current_par_full(), rows[ok], time[ok] - t[rows[ok]], cov=cov)
+            out = self.engine_.predict(self._current_par_full(), rows[ok], offs[ok], cov=cov)
             mean[ok] = out["mean"]
             if cov:
                 P[ok] = out["cov"]
@@ -530,6 +540,24 @@ class SDE:
         if self.type_ not in ("CTCRW", "OU_SSM", "BM_SSM"):
             raise NotImplementedError(f"sample_states: no latent state in the model {self.type_!r}")
         return self.engine_.smooth_draws(self._current_par_full(), n_draws, seed=seed)
+
+    def sample_states_at(self, ID, time, n_draws, seed=0):
+        """Joint posterior draws of the state of a state-space model (CTCRW, OU_SSM, BM_SSM) at any times, at the current parameters
+        (ssde_predict_draws): an array (n_draws, n_query, sdim), columns as in smooth_states.  `ID` and `time` as
+        predict_states takes them.  Draw k is the path sample_states(n_draws, seed) returns as draw k, refined between its rows (with
+        the covariates of the row before) and continued past a track's last row: querying the data's own times returns
+        sample_states' numbers.  All the times of interest go into one call -- the answers inside one interval are jointly
+        distributed only within a call.  NaN for an unknown ID and for a time before the track's second time stamp."""
+        if self.type_ not in ("CTCRW", "OU_SSM", "BM_SSM"):
+            raise NotImplementedError(f"sample_states_at: no latent state in the model {self.type_!r}")
+        if self.engine_ is None:
+            raise RuntimeError("call setup() or fit() first")
+        rows, offs = self._rows_and_offsets(ID, time)
+        ok = rows >= 0
+        out = np.full((int(n_draws), len(rows), self.problem_.sdim), np.nan)
+        if ok.any():
+            out[:, ok, :] = self.engine_.predict_draws(self._current_par_full(), rows[ok], offs[ok], n_draws, seed=seed)
+        return out
 
     def path_summary(self, n_draws, seed=0, regions=None, weight="dt"):
         """Summaries of the posterior state paths of a state-space model (CTCRW, OU_SSM, BM_SSM) at the current parameters, reduced
