@@ -35,6 +35,8 @@
  *                         groups of tracks: a utilisation distribution, summed on the device as integers and so bitwise reproducible
  *   ssde_predict_draws <- (new) those draws' states at any time between or after the rows: the same paths as ssde_smooth_draws,
  *                         refined by Gaussian bridges inside the intervals and simulated past a track's last row, without NA rows
+ *   ssde_path_occupancy_fine <- (new) that utilisation distribution on the refined paths of ssde_predict_draws: every interval's
+ *                         weight spread over the points of a bridge between its two fixes, so that sparse data leave no holes
  *   ssde_penalty       <- smoothing penalty     (nllk_ctcrw.hpp:254-280, nllk_sde.hpp:89-124)
  *   ssde_info          <- InfoADFunObject       (src/init.c:7)
  *   ssde_forget        <- (new) drops the memo of ssde_eval
@@ -456,6 +458,45 @@ int ssde_path_occupancy(ssde_handle *h, const double *par, int32_t n_par_full, u
 /* The kernel forms of the handle's last ssde_path_occupancy: 0 none yet, 1 every wavefront group ran the LDS-tile form, 2 every group
  * the global form, 3 both ran.  A multi-device parent reports its first shard.  NULL gives -1. */
 int ssde_last_occupancy_form(const ssde_handle *h);
+
+/* Occupancy grids of posterior state paths refined between the fixes (definitions: DESIGN.md §3.15).  The grid, occ, outside, group,
+ * weight, the draws, the position columns, the cell rule, the validation of the weights, SSDE_OCC_FORCE_GLOBAL and the quantum (the
+ * same e: b is the bit length of n * n_draws, n the whole handle's caller rows) are ssde_path_occupancy's.  What is new is WHERE a
+ * state row's weight goes:
+ *   1. Slots and sub-steps.  A slot is a state row s of a track in the handle's resident layout (on a lattice-padded handle: a
+ *      lattice row) that is not the track's last state row; Delta_s is the interval the handle holds for it (the lattice step on a
+ *      lattice-padded handle) and m_s = min(SSDE_OCC_MAX_SUB, max(1, ceil(Delta_s / max_step))), an IEEE division, computed once on
+ *      the host from the handle's data; max_step = +inf gives m = 1.  A track's last state row has one point, its own.
+ *   2. Points.  A slot's points are the draw's state at row s and, for k = 1 .. m_s - 1, its state at the offset
+ *      delta_k = (k * Delta_s) / m_s (the product first, then the quotient, in double): the state ssde_predict_draws returns for a
+ *      call whose queries in that slot are exactly those m_s - 1 offsets (delta_k has rank k - 1, each point is drawn given the one
+ *      below it, row s's parameters apply).  The two calls describe THE SAME PATH.
+ *   3. Weights.  A caller's state row j with W_j quanta owns the N_j points of every resident slot from its own up to, not
+ *      including, the next caller row's slot (one slot on an unpadded handle, the padded rows' points included on a lattice
+ *      handle).  Every point gets W_j div N_j quanta and the row's own point W_j mod N_j more, so per group the sum of occ plus
+ *      outside is still EXACTLY n_draws times the sum of w_j over the group's state rows, and with every m = 1 on an unpadded
+ *      handle the result is bitwise ssde_path_occupancy's.
+ *   4. Outside.  A point with a non-finite position coordinate is outside: a row that rejected its update (every inner point of its
+ *      slot), a NaN end, a non-positive pivot of chol(S) (the larger offsets of that slot and draw only, as in ssde_predict_draws).
+ *   5. The result is bitwise independent of SSDE_OPT_SMOOTH_BUDGET_MB, the devices, the kernel form, how the draws are batched
+ *      inside a call and repeated calls.  Over draw RANGES cut over calls the guarantee is WEAKER than ssde_path_occupancy's rules 2
+ *      and 3: a point's amount is the floor W_j div N_j, and the quantum depends on n_draws.  Two calls' ranges add up bitwise to
+ *      the whole range's call only where every W_j is a whole multiple of N_j in the quanta of all the calls involved (w_j = N_j
+ *      times a dyadic number, for instance; NULL weights and dyadic dt do NOT suffice once an m exceeds 1); otherwise they add up
+ *      to within hits * 3 * N_max * 2^e per cell, hits the points of all the draws in the cell, N_max the largest N_j and e the
+ *      coarsest call's.  With every m = 1 on an unpadded handle rules 2 and 3 of ssde_path_occupancy hold as they stand.
+ * The call always runs its own kernels, also when every m is 1.  ssde_last_occupancy_form reports this call's forms too.
+ * SSDE_ERR_ARG for every case of ssde_path_occupancy; max_step NaN or <= 0 (+inf is allowed); a handle with 2^32 or more tracks (the
+ * bridge deviates' counter holds the ordinal's low word).  SSDE_ERR_MODEL exactly where ssde_path_occupancy gives it.  Every check
+ * runs before anything touches the device.  Multi-device handles are served.  Leaves the memo, the window state, the TV records,
+ * n_evals / n_memo_hits and every later result of every other call as they were. */
+#define SSDE_OCC_MAX_SUB 64
+int ssde_path_occupancy_fine(ssde_handle *h, const double *par, int32_t n_par_full, uint64_t seed, int64_t draw0, int32_t n_draws,
+                             const ssde_occ_grid *grid, double max_step, const double *weight, const int32_t *group, int32_t n_groups,
+                             double *occ, double *outside, uint32_t flags);
+/* of the handle's last ssde_path_occupancy_fine: path points per draw that carried weight (the sum of N_j over the state rows of the
+ * tracks that take part), and intervals of those tracks whose m was cut to the cap.  Either pointer may be NULL. */
+int ssde_last_occupancy_points(const ssde_handle *h, int64_t *n_points, int64_t *n_capped);
 
 /* Multiply the warm-up overlap of the time windows by `factor` for all later evaluations
  * (factor <= 0: force one sequential window). */

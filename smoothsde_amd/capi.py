@@ -508,6 +508,11 @@ def load_library():
     lib.ssde_path_occupancy.restype = C.c_int
     lib.ssde_last_occupancy_form.argtypes = [C.c_void_p]
     lib.ssde_last_occupancy_form.restype = C.c_int
+    lib.ssde_path_occupancy_fine.argtypes = [C.c_void_p, _dp, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.POINTER(SsdeOccGrid), C.c_double,
+                                             _dp, C.POINTER(C.c_int32), C.c_int32, _dp, _dp, C.c_uint32]
+    lib.ssde_path_occupancy_fine.restype = C.c_int
+    lib.ssde_last_occupancy_points.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.ssde_last_occupancy_points.restype = C.c_int
     lib.ssde_widen_windows.argtypes = [C.c_void_p, C.c_int32]
     lib.ssde_widen_windows.restype = C.c_int
     lib.ssde_relax_windows.argtypes = [C.c_void_p]
@@ -580,12 +585,13 @@ class EngineError(RuntimeError):
 PATH_MAX_REGIONS = 8   # SSDE_PATH_MAX_REGIONS (include/ssde.h)
 DRAWS_DEVICE_OUT = 1   # ssde_smooth_draws flag: `draws` is an HBM pointer on the handle's device (include/ssde.h)
 OCC_FORCE_GLOBAL = 1   # ssde_path_occupancy flag: every wavefront group runs the global form (SSDE_OCC_FORCE_GLOBAL)
+OCC_MAX_SUB = 64       # SSDE_OCC_MAX_SUB: the most sub-steps ssde_path_occupancy_fine cuts an interval into
 
 WINDOW_TOL = 1e-11  # largest tolerated relative hand-over disagreement between time windows
 
 EXPORTED_SYMBOLS = ("ssde_create", "ssde_eval", "ssde_eval_device", "ssde_penalty", "ssde_report", "ssde_widen_windows", "ssde_relax_windows",
                     "ssde_info", "ssde_destroy", "ssde_last_error", "ssde_abi_version", "ssde_comm_unique_id", "ssde_comm_init_rank", "ssde_forget", "ssde_laplace_eval", "ssde_last_kernel_ms", "ssde_kernel_ms_history",
-                    "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth", "ssde_smooth_draws", "ssde_predict", "ssde_predict_draws", "ssde_path_stats", "ssde_path_occupancy", "ssde_last_occupancy_form",
+                    "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth", "ssde_smooth_draws", "ssde_predict", "ssde_predict_draws", "ssde_path_stats", "ssde_path_occupancy", "ssde_last_occupancy_form", "ssde_path_occupancy_fine", "ssde_last_occupancy_points",
                     "ssde_lagstats_host_m", "ssde_lagstats_read_m", "ssde_lagforms_host_m", "ssde_reduce_host", "ssde_last_finish_form", "ssde_last_gain_feed", "ssde_last_gain_rows")
 
 
@@ -1036,6 +1042,20 @@ class Engine:
         `group`: one label per track in -1 ... n_groups - 1 (-1: the track is left out), or None for one pooled grid; `n_groups`
         defaults to max(group) + 1.  The sums are integers of a fixed quantum: the same bits whatever the chunking, the devices
         or the kernel form (`force_global` picks the form that adds straight into HBM)."""
+        return self._occupancy(None, par, n_draws, grid, seed, draw0, weight, group, n_groups, force_global)
+
+    def path_occupancy_fine(self, par, n_draws: int, grid, max_step: float, seed: int = 0, draw0: int = 0, weight=None, group=None,
+                            n_groups=None, force_global: bool = False):
+        """path_occupancy on the paths refined between the fixes (ssde_path_occupancy_fine): every interval longer than
+        `max_step` is cut into m = min(OCC_MAX_SUB, ceil(interval / max_step)) equal sub-steps, the draw's state at the m - 1 inner
+        times is the one predict_draws returns for those offsets, and the row's weight is shared equally among the interval's m
+        points (whole quanta; the remainder stays with the row's own point).  Everything else, and the result's shape, is
+        path_occupancy's; max_step = inf places every weight as path_occupancy does, bit for bit.  The same bits whatever the
+        chunking, the devices or the kernel form; the sums of calls over parts of a draw range equal the whole range's call only to
+        within the bound of include/ssde.h (rule 5), since a share is a whole number of a quantum that depends on n_draws."""
+        return self._occupancy(float(max_step), par, n_draws, grid, seed, draw0, weight, group, n_groups, force_global)
+
+    def _occupancy(self, max_step, par, n_draws, grid, seed, draw0, weight, group, n_groups, force_global):
         par = np.ascontiguousarray(par, dtype=np.float64)
         if par.shape != (self.n_par_full,):
             raise ValueError(f"par must have length {self.n_par_full}")
@@ -1056,17 +1076,26 @@ class Engine:
         ng = 1 if n_groups is None else int(n_groups)
         occ = np.zeros((max(ng, 0), max(g.ny, 0), max(g.nx, 0)))                        # element (ix, iy, g) at ix + nx (iy + ny g)
         outside = np.zeros(max(ng, 0))
-        self._check(self.lib.ssde_path_occupancy(self._h, par.ctypes.data_as(_dp), self.n_par_full, int(seed), int(draw0), int(n_draws),
-                                                 C.byref(g), None if w is None else w.ctypes.data_as(_dp),
-                                                 None if grp is None else grp.ctypes.data_as(C.POINTER(C.c_int32)), ng,
-                                                 occ.ctypes.data_as(_dp), outside.ctypes.data_as(_dp),
-                                                 OCC_FORCE_GLOBAL if force_global else 0))
+        head = (self._h, par.ctypes.data_as(_dp), self.n_par_full, int(seed), int(draw0), int(n_draws), C.byref(g))
+        tail = (None if w is None else w.ctypes.data_as(_dp), None if grp is None else grp.ctypes.data_as(C.POINTER(C.c_int32)), ng,
+                occ.ctypes.data_as(_dp), outside.ctypes.data_as(_dp), OCC_FORCE_GLOBAL if force_global else 0)
+        if max_step is None:
+            self._check(self.lib.ssde_path_occupancy(*head, *tail))
+        else:
+            self._check(self.lib.ssde_path_occupancy_fine(*head, max_step, *tail))
         return occ, outside
 
     def last_occupancy_form(self) -> int:
         """The kernel forms of the last path_occupancy (ssde_last_occupancy_form): 0 none yet, 1 the LDS-tile form in every wavefront
-        group, 2 the global form in every group, 3 both."""
+        group, 2 the global form in every group, 3 both.  path_occupancy_fine reports here too."""
         return int(self.lib.ssde_last_occupancy_form(self._h))
+
+    def last_occupancy_points(self):
+        """(n_points, n_capped) of the last path_occupancy_fine (ssde_last_occupancy_points): the path points per draw that carried
+        weight, and the intervals whose sub-steps were cut to OCC_MAX_SUB."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        self._check(self.lib.ssde_last_occupancy_points(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
 
     def close(self):
         if self._h:

@@ -708,6 +708,25 @@ struct PredictDrawArgs {
 };
 hipError_t launch_predict_draws_walk(const PredictDrawArgs& a, hipStream_t s);
 hipError_t launch_predict_draws_query(const PredictDrawArgs& a, hipStream_t s);
+// ---- occupancy grids of the drawn paths refined between the rows (k_path_occ_fine.hip) ----
+// The ends and side packets that launch_predict_draws_walk left for the slots of `p` (every state row that places weight:
+// plan_all_slots; p's offset lists and output are not read), and per slot its sub-steps m and the quanta of the point at its row
+// (own) and of each of its m - 1 inner points (share).  A workgroup of OCC_FINE_TB threads takes one wavefront group's slots and
+// OCC_FINE_DRAWS draws of the batch; the grids, forms and accumulators are OccArgs'.
+constexpr int OCC_FINE_TB = 256;
+constexpr int OCC_FINE_DRAWS = 8;
+struct OccFineArgs {
+    PredictDrawArgs p;
+    OccGrid grid;
+    const int32_t* m;            // [n_slots]
+    const uint64_t* own;         // [n_slots]
+    const uint64_t* share;       // [n_slots]
+    const int32_t* lane_grp;     // as OccArgs
+    const int32_t* grp_of;       // as OccArgs
+    unsigned long long* acc;
+    unsigned long long* acc_out;
+};
+hipError_t launch_path_occ_fine(const OccFineArgs& a, bool tile, hipStream_t s);
 hipError_t launch_tv_a0(const TvArgs& a, const double* a0_src, const int64_t* trk_seg, int64_t n_seg, int sdim,
                         double* a0_dst, hipStream_t s);
 hipError_t launch_tv_prepare(const TvArgs& a, hipStream_t s);

@@ -1,7 +1,8 @@
 // ssde_engine_smooth.hip -- ssde_smooth: the fixed-interval smoother of the Kalman families, and
 // ssde_smooth_draws: joint posterior draws of the state path from the same records, and ssde_predict: the smoothed
 // state between and after the rows from them, and ssde_path_stats / ssde_path_occupancy: reductions of the drawn paths
-// on the device, and ssde_predict_draws: the drawn paths refined between and after the rows.
+// on the device, and ssde_predict_draws: the drawn paths refined between and after the rows,
+// and ssde_path_occupancy_fine: the occupancy grids of the refined paths.
 //
 // A forward pass in record mode (dense_kernel MODE 2 on the tiled routes, smooth_tv_record_kernel on PATH_TV) writes every state
 // row's record, smooth_back_kernel walks them back and writes the smoothed mean, covariance and whitened innovation in the long
@@ -409,6 +410,170 @@ int occ_sharded(ssde_handle* parent, const double* par, uint64_t seed, int64_t d
     return SSDE_OK;
 }
 
+// ---- ssde_path_occupancy_fine -------------------------------------------------------------------------------------------------
+// The interval the handle holds for every slot of plan_all_slots' lists (lane-major, steps ascending), read once on the host: the one
+// interval of a globally regular grid (on a lattice-padded handle: of the lattice), else the tiles' dt channel; on PATH_TV the
+// differences of the times.  A lane's last step has no interval to the next row; its entry is not read.
+int slot_intervals(ssde_handle* h, const RecordRun& run, const QueryPlan& P, const std::vector<int64_t>& row0, std::vector<double>& dt) {
+    const int64_t nl = run.n_lanes, n_slots = (int64_t)P.want_step.size();
+    dt.assign((size_t)n_slots, 0.0);
+    if (n_slots == 0) return SSDE_OK;
+    if (run.tv) {
+        std::vector<double> tm((size_t)h->n);
+        HIPCHK(h, hipMemcpy(tm.data(), h->times.p, (size_t)h->n * 8, hipMemcpyDeviceToHost));
+        for (int64_t l = 0; l < nl; l++)
+            for (int64_t i = P.want_off[l]; i < P.want_off[l + 1]; i++) {
+                const int64_t row = row0[l] + 1 + (i - P.want_off[l]);
+                dt[(size_t)i] = row + 1 < h->n ? tm[(size_t)row + 1] - tm[(size_t)row] : h->last_dt;
+            }
+        return SSDE_OK;
+    }
+    if (h->c_obs == 0) { std::fill(dt.begin(), dt.end(), h->dt_all); return SSDE_OK; }
+    // channel 0 of every tile row: group g's rows start at the sum of the group lengths before it
+    std::vector<int32_t> glen((size_t)h->n_groups);
+    HIPCHK(h, hipMemcpy(glen.data(), h->group_len.p, (size_t)h->n_groups * 4, hipMemcpyDeviceToHost));
+    std::vector<int64_t> grow((size_t)h->n_groups + 1, 0);
+    for (int g = 0; g < h->n_groups; g++) grow[g + 1] = grow[g] + glen[g];
+    std::vector<double> ch((size_t)grow[h->n_groups] * WAVE);
+    if (!ch.empty())
+        HIPCHK(h, hipMemcpy2D(ch.data(), (size_t)WAVE * 8, h->tiles.p, (size_t)h->C * WAVE * 8, (size_t)WAVE * 8, (size_t)grow[h->n_groups],
+                              hipMemcpyDeviceToHost));
+    // (in the tiles' order, step by step over a group's 64 lanes: the 80 MB of a large handle are read once, front to back)
+    for (int g = 0; g < h->n_groups; g++)
+        for (int64_t s = 0; s < glen[g]; s++) {
+            const double* row = ch.data() + (size_t)(grow[g] + s) * WAVE;
+            for (int64_t l = (int64_t)g * WAVE; l < std::min<int64_t>((int64_t)(g + 1) * WAVE, nl); l++)
+                if (s < P.want_off[l + 1] - P.want_off[l]) dt[(size_t)(P.want_off[l] + s)] = row[l - (int64_t)g * WAVE];
+        }
+    return SSDE_OK;
+}
+
+// One engine's refined occupancy counts, ADDED to `counts` as occ_single's, and its two counts of ssde_last_occupancy_points added
+// to n_points / n_capped.  occ_single's tables (the lanes' output grids, the groups' forms, the quantised weights, the accumulator
+// zeroed once per call) under predict_draws_single's run: the record pass with side rows, chunks of whole groups under the budget
+// (chunks without a slot skipped), batches from occ_fine_batch_cap with produce_for_batch; per batch and chunk the draws' walk that
+// leaves the ends of every slot, then path_occ_fine_kernel.
+int occ_fine_single(ssde_handle* h, const double* par, uint64_t seed, int64_t draw0, int n_draws, const ssde_occ_grid& grid,
+                    double max_step, const double* weight, const int32_t* group, int n_groups, int e, bool force_global,
+                    std::vector<uint64_t>& counts, int64_t& n_points, int64_t& n_capped, int64_t track0) {
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(0));
+    RecordRun run;
+    run.SW = predict_side_doubles(h->model, h->d);
+    if (run.SW <= 0) { h->err = "ssde_path_occupancy_fine: no kernels for this model and width"; return SSDE_ERR_MODEL; }
+    if (int st = run.setup(h, par, "ssde_path_occupancy_fine")) return st;
+    const int64_t nt = run.nt, n = h->n, nl = run.n_lanes;
+    const int64_t ncell = (int64_t)grid.nx * grid.ny;
+    const int ez = 2 * h->sdim;
+    if ((int64_t)h->lane_seg.n < nl) { h->err = "ssde_path_occupancy_fine: the handle holds no track ordinals for its lanes"; return SSDE_ERR_ARG; }
+    h->last_occ_form = 0; h->last_occ_points = 0; h->last_occ_capped = 0;
+    if (h->n_seg == 0 || nl == 0) return SSDE_OK;
+    // every lane's output grid, every wavefront group's form, every slot
+    std::vector<int64_t> lseg((size_t)nl), row0((size_t)nl), rmap;
+    std::vector<int32_t> lns((size_t)nl), lgrp((size_t)nl, -1);
+    HIPCHK(h, hipMemcpy(lseg.data(), h->lane_seg.p, (size_t)nl * 8, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(lns.data(), run.s.lane_ns, (size_t)nl * 4, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(row0.data(), run.s.lane_row0, (size_t)nl * 8, hipMemcpyDeviceToHost));
+    for (int64_t l = 0; l < nl; l++)
+        if (lns[l] > 0 && lseg[l] >= 0 && lseg[l] < h->n_seg) lgrp[l] = group ? group[lseg[l]] : 0;
+    const std::vector<int32_t> grp_of = plan_occ_groups(lgrp, WAVE, ncell, OCC_TILE_CELLS, force_global, OCC_GROUP_MIXED);
+    const QueryPlan P = plan_all_slots(lns, lgrp);
+    const int64_t n_slots = (int64_t)P.want_step.size();
+    if (n_slots == 0) return SSDE_OK;
+    std::vector<double> sdt;
+    if (int st = slot_intervals(h, run, P, row0, sdt)) return st;
+    DevBuf<int64_t> map;
+    DevBuf<uint64_t> ob, sb;
+    DevBuf<unsigned long long> acc;
+    DevBuf<int32_t> lg, go, mb, ws;
+    DevBuf<int64_t> wo, sl;
+    DevBuf<double> ends, sidepk;
+    Release guard(map, ob, sb, acc, lg, go, mb, ws, wo, sl, ends, sidepk);
+    if (nt != n) {                                                      // the caller's row OF each lattice row, for the host plan
+        HIPCHK(h, map.alloc((size_t)nt));
+        HIPCHK(h, launch_path_row_map(h->pad_row.p, n, nt, map.p, 0));
+        rmap.resize((size_t)nt);
+        HIPCHK(h, hipMemcpy(rmap.data(), map.p, (size_t)nt * 8, hipMemcpyDeviceToHost));
+    }
+    std::vector<uint64_t> wq;
+    if (weight && n > 0) { wq.resize((size_t)n); occ_quantise_all(weight, n, e, wq.data()); }
+    const FineWeights F = plan_fine_weights(P, row0, sdt, max_step, SSDE_OCC_MAX_SUB, nt != n ? rmap.data() : nullptr,
+                                            wq.empty() ? nullptr : wq.data(), occ_quantise(1.0, e));
+    std::vector<uint64_t>().swap(wq);
+    sdt = std::vector<double>();
+    std::vector<int64_t> slot_lane((size_t)n_slots);
+    for (int64_t l = 0; l < nl; l++)
+        for (int64_t i = P.want_off[l]; i < P.want_off[l + 1]; i++) slot_lane[(size_t)i] = l;
+    int64_t most = 0;
+    for (size_t c = 0; c < run.n_chunks(); c++) {
+        const QueryRange r = chunk_queries(P, run.cut[c], run.cut[c + 1], WAVE);
+        most = std::max(most, r.s1 - r.s0);
+    }
+    HIPCHK(h, wo.upload(P.want_off)); HIPCHK(h, ws.upload(P.want_step)); HIPCHK(h, sl.upload(slot_lane));
+    HIPCHK(h, mb.upload(F.m)); HIPCHK(h, ob.upload(F.own)); HIPCHK(h, sb.upload(F.share));
+    HIPCHK(h, lg.upload(lgrp)); HIPCHK(h, go.upload(grp_of));
+    const size_t n_acc = (size_t)ncell * n_groups + (size_t)n_groups;
+    HIPCHK(h, acc.alloc(n_acc));
+    HIPCHK(h, hipMemset(acc.p, 0, n_acc * 8));
+    // draws per batch: what fits beside the records and side rows (the free memory asked for again, as draws_single does)
+    int64_t budget = run.budget;
+    if (h->smooth_budget_mb <= 0) if (int st = free_budget(h, budget)) return st;
+    const int nb_cap = occ_fine_batch_cap(budget, most, ez, DRAW_CH, n_draws);
+    HIPCHK(h, ends.alloc((size_t)most * ez * nb_cap));
+    HIPCHK(h, sidepk.alloc((size_t)most * run.SW));
+    OccFineArgs a;
+    memset(&a, 0, sizeof(a));
+    a.p.d.lane_trk = h->lane_seg.p; a.p.d.track0 = track0; a.p.d.seed = seed; a.p.d.col0 = 0;
+    a.p.want_off = wo.p; a.p.want_step = ws.p; a.p.ends = ends.p; a.p.sidepk = sidepk.p; a.p.slot_lane = sl.p;
+    a.grid.x0 = grid.x0; a.grid.dx = grid.dx; a.grid.y0 = grid.y0; a.grid.dy = grid.dy; a.grid.nx = grid.nx; a.grid.ny = grid.ny;
+    a.m = mb.p; a.own = ob.p; a.share = sb.p;
+    a.lane_grp = lg.p; a.grp_of = go.p; a.acc = acc.p; a.acc_out = acc.p + (size_t)ncell * n_groups;
+    int forms = 0;
+    for (int k0 = 0; k0 < n_draws; k0 += nb_cap) {
+        a.p.d.draw0 = (uint32_t)(draw0 + k0); a.p.d.n_draws = std::min(nb_cap, n_draws - k0);
+        for (size_t c = 0; c < run.n_chunks(); c++) {
+            const QueryRange r = chunk_queries(P, run.cut[c], run.cut[c + 1], WAVE);
+            if (r.s1 == r.s0) continue;                                   // no slot on this chunk's tracks
+            if (int st = run.produce_for_batch(c)) return st;
+            a.p.d.s = run.s;
+            a.p.slot0 = r.s0; a.p.pk_stride = r.s1 - r.s0;
+            bool tile = false, global = false;
+            for (int g = run.cut[c]; g < run.cut[c + 1]; g++) {
+                if (grp_of[g] == OCC_GROUP_MIXED) global = true;
+                else if (grp_of[g] >= 0) tile = true;
+            }
+            HIPCHK(h, launch_predict_draws_walk(a.p, 0));
+            if (tile) HIPCHK(h, launch_path_occ_fine(a, true, 0));
+            if (global) HIPCHK(h, launch_path_occ_fine(a, false, 0));
+            forms |= (tile ? 1 : 0) | (global ? 2 : 0);
+        }
+    }
+    std::vector<uint64_t> got(n_acc);
+    HIPCHK(h, hipMemcpy(got.data(), acc.p, n_acc * 8, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipStreamSynchronize(0));
+    for (size_t i = 0; i < n_acc; i++) counts[i] += got[i];
+    h->last_occ_form = forms; h->last_occ_points = F.n_points; h->last_occ_capped = F.n_capped;
+    n_points += F.n_points; n_capped += F.n_capped;
+    return SSDE_OK;
+}
+
+// the track shards' refined counts, as occ_sharded: slices of the weights and groups, the GLOBAL track ordinal in the deviates, the
+// parent's quantum; integer grids and the two counts add up
+int occ_fine_sharded(ssde_handle* parent, const double* par, uint64_t seed, int64_t draw0, int n_draws, const ssde_occ_grid& grid,
+                     double max_step, const double* weight, const int32_t* group, int n_groups, int e, bool force_global,
+                     std::vector<uint64_t>& counts, int64_t& n_points, int64_t& n_capped) {
+    int64_t track0 = 0;
+    for (size_t k = 0; k < parent->shards.size(); k++) {
+        ssde_handle* sh = parent->shards[k];
+        const int64_t lo = parent->shard_row0[k];
+        int st = occ_fine_single(sh, par, seed, draw0, n_draws, grid, max_step, weight ? weight + lo : nullptr,
+                                 group ? group + track0 : nullptr, n_groups, e, force_global, counts, n_points, n_capped, track0);
+        if (st) { parent->err = sh->err; return st; }
+        track0 += sh->n_seg;
+    }
+    return SSDE_OK;
+}
+
 // ---- ssde_predict -------------------------------------------------------------------------------------------------------------
 // One engine's queries.  plan_queries (ssde_smooth_plan.hpp) places them on the host; then, chunk by chunk: the record pass with side
 // rows, the walk that fills the chunk's packets, the query kernel.
@@ -730,43 +895,54 @@ int ssde_path_stats(ssde_handle* h, const double* par, int32_t n_par_full, uint6
     return path_single(h, par, seed, draw0, n_draws, regions, n_regions, weight, stats, 0);
 }
 
-int ssde_path_occupancy(ssde_handle* h, const double* par, int32_t n_par_full, uint64_t seed, int64_t draw0, int32_t n_draws,
-                        const ssde_occ_grid* grid, const double* weight, const int32_t* group, int32_t n_groups, double* occ,
-                        double* outside, uint32_t flags) {
-    if (!h || !par || !grid || !occ) { if (h) h->err = "ssde_path_occupancy: no parameter vector, no grid, or no output"; return SSDE_ERR_ARG; }
+// what ssde_path_occupancy and ssde_path_occupancy_fine check alike, before anything touches the device; wmax: the largest weight (1
+// without weights)
+static int occ_check(ssde_handle* h, const char* who, const double* par, int32_t n_par_full, int64_t draw0, int32_t n_draws,
+                     const ssde_occ_grid* grid, const double* weight, const int32_t* group, int32_t n_groups, const double* occ,
+                     uint32_t flags, double& wmax) {
+    const std::string w(who);
+    if (!h || !par || !grid || !occ) { if (h) h->err = w + ": no parameter vector, no grid, or no output"; return SSDE_ERR_ARG; }
     if (int st = check_par_len(h, n_par_full)) return st;
     if (n_draws < 1 || draw0 < 0 || draw0 + (int64_t)n_draws >= ((int64_t)1 << 28)) {
-        h->err = "ssde_path_occupancy: n_draws >= 1, draw0 >= 0 and draw0 + n_draws < 2^28 are required";
+        h->err = w + ": n_draws >= 1, draw0 >= 0 and draw0 + n_draws < 2^28 are required";
         return SSDE_ERR_ARG;
     }
-    if (flags & ~(uint32_t)SSDE_OCC_FORCE_GLOBAL) { h->err = "ssde_path_occupancy: unknown flag"; return SSDE_ERR_ARG; }
-    if (grid->nx < 1 || grid->nx > 4096 || grid->ny < 1 || grid->ny > 4096) { h->err = "ssde_path_occupancy: nx and ny must be 1 ... 4096"; return SSDE_ERR_ARG; }
+    if (flags & ~(uint32_t)SSDE_OCC_FORCE_GLOBAL) { h->err = w + ": unknown flag"; return SSDE_ERR_ARG; }
+    if (grid->nx < 1 || grid->nx > 4096 || grid->ny < 1 || grid->ny > 4096) { h->err = w + ": nx and ny must be 1 ... 4096"; return SSDE_ERR_ARG; }
     if (n_groups < 1 || (int64_t)grid->nx * grid->ny * (int64_t)n_groups > ((int64_t)1 << 28)) {
-        h->err = "ssde_path_occupancy: n_groups >= 1 and nx * ny * n_groups <= 2^28 are required";
+        h->err = w + ": n_groups >= 1 and nx * ny * n_groups <= 2^28 are required";
         return SSDE_ERR_ARG;
     }
-    if (!group && n_groups != 1) { h->err = "ssde_path_occupancy: without a group table there is one group"; return SSDE_ERR_ARG; }
+    if (!group && n_groups != 1) { h->err = w + ": without a group table there is one group"; return SSDE_ERR_ARG; }
     if (int st = check_kalman(h)) return st;
     if (h->d > 2) {
-        h->err = "ssde_path_occupancy: a response of three or more columns is not served, as column pairs or as one coupled filter (a cell needs the position columns in one lane)";
+        h->err = w + ": a response of three or more columns is not served, as column pairs or as one coupled filter (a cell needs the position columns in one lane)";
         return SSDE_ERR_MODEL;
     }
-    if (h->d == 1 && grid->ny != 1) { h->err = "ssde_path_occupancy: one position column takes ny = 1"; return SSDE_ERR_ARG; }
+    if (h->d == 1 && grid->ny != 1) { h->err = w + ": one position column takes ny = 1"; return SSDE_ERR_ARG; }
     if (!std::isfinite(grid->x0) || !std::isfinite(grid->dx) || grid->dx <= 0.0 ||
         (h->d == 2 && (!std::isfinite(grid->y0) || !std::isfinite(grid->dy) || grid->dy <= 0.0))) {
-        h->err = "ssde_path_occupancy: the grid's origin must be finite and its steps finite and positive";
+        h->err = w + ": the grid's origin must be finite and its steps finite and positive";
         return SSDE_ERR_ARG;
     }
     for (int64_t t = 0; group && t < h->n_seg; t++)
-        if (group[t] < -1 || group[t] >= n_groups) { h->err = "ssde_path_occupancy: a group outside -1 ... n_groups - 1"; return SSDE_ERR_ARG; }
-    double wmax = weight ? 0.0 : 1.0;
+        if (group[t] < -1 || group[t] >= n_groups) { h->err = w + ": a group outside -1 ... n_groups - 1"; return SSDE_ERR_ARG; }
+    wmax = weight ? 0.0 : 1.0;
     for (int64_t i = 0; weight && i < h->n; i++) {
         if (!(weight[i] >= 0.0 && weight[i] <= std::numeric_limits<double>::max())) {      // negative, NaN or inf
-            h->err = "ssde_path_occupancy: a weight that is negative or not finite";
+            h->err = w + ": a weight that is negative or not finite";
             return SSDE_ERR_ARG;
         }
         wmax = std::max(wmax, weight[i]);
     }
+    return SSDE_OK;
+}
+
+int ssde_path_occupancy(ssde_handle* h, const double* par, int32_t n_par_full, uint64_t seed, int64_t draw0, int32_t n_draws,
+                        const ssde_occ_grid* grid, const double* weight, const int32_t* group, int32_t n_groups, double* occ,
+                        double* outside, uint32_t flags) {
+    double wmax = 1.0;
+    if (int st = occ_check(h, "ssde_path_occupancy", par, n_par_full, draw0, n_draws, grid, weight, group, n_groups, occ, flags, wmax)) return st;
     // the quantum of the whole handle's call; the counts of every engine, chunk and batch add up as integers
     const int e = occ_quantum_exp(wmax, h->n, n_draws);
     const bool force_global = (flags & SSDE_OCC_FORCE_GLOBAL) != 0;
@@ -777,6 +953,37 @@ int ssde_path_occupancy(ssde_handle* h, const double* par, int32_t n_par_full, u
     if (st) return st;
     for (size_t i = 0; i < n_cells; i++) occ[i] = ldexp((double)counts[i], e);
     for (int g = 0; outside && g < n_groups; g++) outside[g] = ldexp((double)counts[n_cells + g], e);
+    return SSDE_OK;
+}
+
+int ssde_path_occupancy_fine(ssde_handle* h, const double* par, int32_t n_par_full, uint64_t seed, int64_t draw0, int32_t n_draws,
+                             const ssde_occ_grid* grid, double max_step, const double* weight, const int32_t* group, int32_t n_groups,
+                             double* occ, double* outside, uint32_t flags) {
+    double wmax = 1.0;
+    if (int st = occ_check(h, "ssde_path_occupancy_fine", par, n_par_full, draw0, n_draws, grid, weight, group, n_groups, occ, flags, wmax)) return st;
+    if (!(max_step > 0.0)) { h->err = "ssde_path_occupancy_fine: max_step must be positive (+inf: no refinement)"; return SSDE_ERR_ARG; }
+    // the bridge deviates' counter holds the track ordinal's low word (ssde_predict_draws)
+    if (h->n_seg >= ((int64_t)1 << 32)) { h->err = "ssde_path_occupancy_fine: 2^32 or more tracks"; return SSDE_ERR_ARG; }
+    const int e = occ_quantum_exp(wmax, h->n, n_draws);
+    const bool force_global = (flags & SSDE_OCC_FORCE_GLOBAL) != 0;
+    const size_t n_cells = (size_t)grid->nx * grid->ny * n_groups;
+    std::vector<uint64_t> counts(n_cells + (size_t)n_groups, 0);
+    int64_t n_points = 0, n_capped = 0;
+    h->last_occ_points = 0; h->last_occ_capped = 0;
+    const int st = h->shards.empty()
+        ? occ_fine_single(h, par, seed, draw0, n_draws, *grid, max_step, weight, group, n_groups, e, force_global, counts, n_points, n_capped, 0)
+        : occ_fine_sharded(h, par, seed, draw0, n_draws, *grid, max_step, weight, group, n_groups, e, force_global, counts, n_points, n_capped);
+    if (st) return st;
+    h->last_occ_points = n_points; h->last_occ_capped = n_capped;
+    for (size_t i = 0; i < n_cells; i++) occ[i] = ldexp((double)counts[i], e);
+    for (int g = 0; outside && g < n_groups; g++) outside[g] = ldexp((double)counts[n_cells + g], e);
+    return SSDE_OK;
+}
+
+int ssde_last_occupancy_points(const ssde_handle* h, int64_t* n_points, int64_t* n_capped) {
+    if (!h) return SSDE_ERR_ARG;
+    if (n_points) *n_points = h->last_occ_points;
+    if (n_capped) *n_capped = h->last_occ_capped;
     return SSDE_OK;
 }
 

@@ -1,8 +1,10 @@
 // ssde_smooth_plan.hpp -- the host-side plans of the calls that consume the smoother's records (ssde_engine_smooth.hip): how the
 // groups are cut into chunks under the budget, how many draws go into one batch, which form every wavefront group of
-// ssde_path_occupancy runs, where every query of ssde_predict lands, and the distinct offsets of every slot of ssde_predict_draws.
+// ssde_path_occupancy runs, where every query of ssde_predict lands, the distinct offsets of every slot of ssde_predict_draws, and the
+// slots, sub-steps and shares of ssde_path_occupancy_fine.
 // Plain C++17, no HIP: the engine uploads and launches what these return, tests/hostsim/hostsim_predict.cpp exports them to
-// tests/test_smooth_plan_host.py (and hostsim_predict_draws.cpp the last to tests/test_predict_draws_plan_host.py).
+// tests/test_smooth_plan_host.py (hostsim_predict_draws.cpp the offsets to tests/test_predict_draws_plan_host.py, hostsim_occ_fine.cpp
+// the last to tests/test_occ_fine_plan_host.py).
 #ifndef SSDE_SMOOTH_PLAN_HPP
 #define SSDE_SMOOTH_PLAN_HPP
 
@@ -190,6 +192,85 @@ inline SlotOffsets plan_slot_offsets(const QueryPlan& P) {
 // output, next to the records and side rows the budget already pays for; any number of draws goes (unit 1), one always
 inline int predict_draws_batch_cap(int64_t budget, int64_t n_slots, int sd, int64_t n_query, int ch, int n_draws) {
     return batch_cap(budget, n_slots * 2 * sd + n_query * sd, 1, ch, n_draws);
+}
+
+// ---- ssde_path_occupancy_fine ------------------------------------------------------------------------------------
+// The wanted steps of a call that places weight at EVERY state row: lane l's list is 0 .. ns[l] - 1 when the lane takes part
+// (lane_grp[l] >= 0 and ns[l] > 0) and empty otherwise.  Written arithmetically into a QueryPlan's want_off / want_step (its other
+// lists stay empty): O(lanes + slots), no sort.
+inline QueryPlan plan_all_slots(const std::vector<int32_t>& ns, const std::vector<int32_t>& lane_grp) {
+    const int64_t nl = (int64_t)ns.size();
+    QueryPlan P;
+    P.want_off.assign((size_t)nl + 1, 0);
+    for (int64_t l = 0; l < nl; l++) P.want_off[l + 1] = P.want_off[l] + ((lane_grp[l] >= 0 && ns[l] > 0) ? ns[l] : 0);
+    P.want_step.resize((size_t)P.want_off[nl]);
+    for (int64_t l = 0; l < nl; l++) {
+        int32_t* w = P.want_step.data() + P.want_off[l];
+        for (int64_t s = 0, m = P.want_off[l + 1] - P.want_off[l]; s < m; s++) w[s] = (int32_t)s;
+    }
+    return P;
+}
+
+// sub-steps of an interval dt: min(max_sub, max(1, ceil(dt / max_step))), the division IEEE; an interval that is NaN or <= 0 has one;
+// *capped is set where the cap cut it
+inline int32_t occ_fine_substeps(double dt, double max_step, int max_sub, bool* capped = nullptr) {
+    const double c = std::ceil(dt / max_step);
+    if (capped) *capped = c > (double)max_sub;
+    if (!(c >= 1.0)) return 1;
+    return c > (double)max_sub ? max_sub : (int32_t)c;
+}
+
+// Per slot of plan_all_slots' lists: its sub-steps m, the quanta `own` of the point at its row and `share` of each of the m - 1
+// points inside it.  slot_dt: the interval of every slot (unread at a lane's last step, which has one point: m = 1); row0: the lanes'
+// first rows in the resident layout (step s of lane l is row row0[l] + 1 + s); row_map: the caller's row of every resident row, -1 on
+// a padded row, or NULL when the rows ARE the caller's; wq: the quantised weights by the caller's row, or NULL: every row weighs
+// `unit`.  A caller's row j with W quanta owns the N points of the slots from its own up to, not including, the next caller row's
+// slot: each gets W div N quanta and the row's own point W mod N more.  A padded row before a lane's first caller row belongs to no
+// state row and gets nothing.  n_points: the sum of N over the caller's rows of the lanes that take part; n_capped: their
+// intervals whose m the cap cut.
+struct FineWeights {
+    std::vector<int32_t> m;
+    std::vector<uint64_t> own, share;
+    int64_t n_points = 0, n_capped = 0;
+};
+
+inline FineWeights plan_fine_weights(const QueryPlan& P, const std::vector<int64_t>& row0, const std::vector<double>& slot_dt,
+                                     double max_step, int max_sub, const int64_t* row_map, const uint64_t* wq, uint64_t unit) {
+    const int64_t nl = (int64_t)P.want_off.size() - 1, n_slots = (int64_t)P.want_step.size();
+    FineWeights F;
+    F.m.assign((size_t)n_slots, 1);
+    F.own.assign((size_t)n_slots, 0);
+    F.share.assign((size_t)n_slots, 0);
+    for (int64_t l = 0; l < nl; l++) {
+        const int64_t w0 = P.want_off[l], w1 = P.want_off[l + 1];
+        for (int64_t i = w0; i + 1 < w1; i++) {                        // (the last step keeps m = 1)
+            bool capped = false;
+            F.m[(size_t)i] = occ_fine_substeps(slot_dt[(size_t)i], max_step, max_sub, &capped);
+            F.n_capped += capped ? 1 : 0;
+        }
+        for (int64_t i = w0; i < w1;) {
+            const int64_t row = row0[l] + 1 + (i - w0);
+            const int64_t crow = row_map ? row_map[row] : row;
+            int64_t i1 = i + 1;
+            while (row_map && i1 < w1 && row_map[row0[l] + 1 + (i1 - w0)] < 0) i1++;   // the padded rows that follow
+            if (crow >= 0) {
+                uint64_t np = 0;
+                for (int64_t k = i; k < i1; k++) np += (uint64_t)F.m[(size_t)k];
+                const uint64_t W = wq ? wq[crow] : unit, sh = W / np;
+                for (int64_t k = i; k < i1; k++) F.own[(size_t)k] = F.share[(size_t)k] = sh;
+                F.own[(size_t)i] += W % np;
+                F.n_points += (int64_t)np;
+            }
+            i = i1;
+        }
+    }
+    return F;
+}
+
+// ssde_path_occupancy_fine's draws per batch through batch_cap: a draw costs the ends of every slot (ez = BridgePk::EZ doubles
+// each), next to the records and side rows the budget already pays for; any number of draws goes (unit 1), one always
+inline int occ_fine_batch_cap(int64_t budget, int64_t n_slots, int ez, int ch, int n_draws) {
+    return batch_cap(budget, n_slots * ez, 1, ch, n_draws);
 }
 
 }  // namespace ssde_plan

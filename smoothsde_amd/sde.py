@@ -583,7 +583,7 @@ class SDE:
         weight[:-1][same] = (t[1:] - t[:-1])[same]
         return weight
 
-    def utilisation(self, n_draws, seed=0, cells=(64, 64), extent=None, by=None, weight="dt"):
+    def utilisation(self, n_draws, seed=0, cells=(64, 64), extent=None, by=None, weight="dt", max_step=None):
         """The utilisation distribution of a state-space model (CTCRW, OU_SSM, BM_SSM) at the current parameters: the share of the
         weighted time that the posterior state paths spend in every cell of a regular grid, summed on the device
         (ssde_path_occupancy).  `cells`: (nx, ny) (an integer, or ny = 1, for one response column); `extent`:
@@ -591,7 +591,11 @@ class SDE:
         pools every track, "ID" gives one grid per track, an integer array one group label per track (-1: left out); `weight`
         as path_summary's.  {"x_edges": (nx + 1,), "y_edges": (ny + 1,), "density": (n_groups, ny, nx), "outside": (n_groups,)}:
         the sums divided per group by n_draws times the group's total weight, so density and outside together sum to 1 (NaN
-        for a group without weight).  The draws are those of sample_states(n_draws, seed)."""
+        for a group without weight).  The draws are those of sample_states(n_draws, seed).  `max_step`: None places every
+        interval's weight at the row that starts it; a positive number spreads it along the path refined between the fixes
+        (ssde_path_occupancy_fine, DESIGN.md §3.15: intervals longer than max_step are cut into equal sub-steps, the states inside
+        them are sample_states_at's) and adds "n_points", the path points per draw that carried weight; a warning is issued when an
+        interval needed more sub-steps than the cap allows."""
         if self.type_ not in ("CTCRW", "OU_SSM", "BM_SSM"):
             raise NotImplementedError(f"utilisation: no latent state in the model {self.type_!r}")
         pb = self.problem_
@@ -622,7 +626,16 @@ class SDE:
             group = np.arange(n_seg, dtype=np.int32)
         else:
             group = np.ascontiguousarray(by, dtype=np.int32)
-        occ, outside = self.engine_.path_occupancy(self._current_par_full(), n_draws, grid, seed=seed, weight=weight, group=group)
+        extra = {}
+        if max_step is None:
+            occ, outside = self.engine_.path_occupancy(self._current_par_full(), n_draws, grid, seed=seed, weight=weight, group=group)
+        else:
+            occ, outside = self.engine_.path_occupancy_fine(self._current_par_full(), n_draws, grid, max_step, seed=seed, weight=weight,
+                                                            group=group)
+            extra["n_points"], n_capped = self.engine_.last_occupancy_points()
+            if n_capped > 0:
+                warnings.warn(f"utilisation: {n_capped} intervals need more than {capi.OCC_MAX_SUB} sub-steps of max_step={max_step}; "
+                              "they were cut into that many", stacklevel=2)
         # the total weight of every group's state rows (a track's first row carries no state)
         start = np.asarray(pb.seg_start, dtype=np.int64)
         w = np.ones(len(pb.times)) if weight is None else np.array(weight, dtype=np.float64)
@@ -634,7 +647,7 @@ class SDE:
             density, out = occ / total[:, None, None], outside / total
         return {"x_edges": grid["x0"] + grid["dx"] * np.arange(nx + 1),
                 "y_edges": (grid["y0"] + grid["dy"] * np.arange(ny + 1)) if d == 2 else np.array([-np.inf, np.inf]),
-                "density": density, "outside": out}
+                "density": density, "outside": out, **extra}
 
     def residuals(self):
         """Model residuals, iid N(0, 1) under the model (one column per response variable).
