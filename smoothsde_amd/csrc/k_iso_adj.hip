@@ -99,13 +99,17 @@ __global__ __launch_bounds__(WG_WAVES * WAVE, 1) void iso_adj_kernel(const IsoAr
     double* const rec = &recs[wv][lane];
     const double h = A.h;
 
-    // a row's channels by BUFFER loads: one resource over the window's rows (scalar registers), the row as a scalar byte offset, the
-    // channel + lane as a 32-bit vector offset formed once -- no vector address arithmetic per load
+    // a row's channels by BUFFER loads: one resource per ROW (scalar registers: the window's first row + the row's 64-bit byte offset,
+    // adj_row_offset -- a window of 2 GiB or more is an ordinary plan on a long track, and a 32-bit offset from one resource over the
+    // window wrapped there), one row's bytes as its records, the channel + lane as a 32-bit vector offset formed once -- no vector
+    // address arithmetic per load
 #ifndef ADJ_LOADS
 #define ADJ_LOADS 1
 #endif
 #if ADJ_LOADS == 1
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(gbase + (int64_t)s_begin * C * WAVE), 0, 0x7fffffff, 0x00020000);
+    static_assert(ADJ_TILE_LANES == WAVE, "adj_row_bytes: a tile row is C channels of one wave's lanes");
+    const char* const wbase = (const char*)(gbase + (int64_t)s_begin * C * WAVE);
+    const int row_bytes = (int)adj_row_bytes(C);
     unsigned voff[W];
     voff[0] = (unsigned)lane * 8u;
 #pragma unroll
@@ -116,11 +120,11 @@ __global__ __launch_bounds__(WG_WAVES * WAVE, 1) void iso_adj_kernel(const IsoAr
     for (int k = 0; k < KS; k++) voff[CO + k] = (unsigned)((c_col + (k < K ? k : 0)) * WAVE + lane) * 8u;      // (past the last column: column 0 again, coefficient 0)
     auto load_row = [&](double (&dst)[W], int s) {
         if (A.adj_diag & 1) s = s_begin + (s & 3);                 // (timing experiment: every row from the cache -- the numbers mean nothing)
-        const int so = (s - s_begin) * C * (WAVE * 8);
+        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(wbase + adj_row_offset(s - s_begin, C)), 0, row_bytes, 0x00020000);
 #ifndef ADJ_AUX
 #define ADJ_AUX 0
 #endif
-        auto at = [&](int i) { return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff[i], so, ADJ_AUX)); };
+        auto at = [&](int i) { return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff[i], 0, ADJ_AUX)); };
         dst[0] = tv.dt_all;
         if (c_obs) dst[0] = at(0);
 #pragma unroll

@@ -16,6 +16,7 @@
 // Written as __host__ __device__ inline code: k_iso_adj.hip runs it lane = track; tests/hostsim compiles it with g++.
 #ifndef SSDE_ADJ_HPP
 #define SSDE_ADJ_HPP
+#include <cstdint>
 #include <type_traits>
 
 #include "ssde_math.hpp"
@@ -27,6 +28,17 @@ template <int D>
 struct AdjRowGrad {
     double g1, g2, gmu[D], gh;
 };
+
+// Where a window's rows lie in the tile.  A row of a group is C channels x 64 lanes of doubles whatever the number of tracks in
+// it, so a window over `rows` rows spans rows x C x 512 bytes: 2^31 at 209 716 rows of 20 channels, 2^32 at 419 431.  One window per
+// track is an ordinary plan (slow forgetting, a plan that gave up, SSDE_CHUNKS=1), so the offset of a row from its window's first
+// row is a 64-BIT product: k_iso_adj.hip opens its buffer resource AT the row (base + adj_row_offset, adj_row_bytes records) and
+// every 32-bit offset a load then carries stays below one row's bytes.  tests/test_adj_offsets_host.py pins both sides of 2^31 and
+// 2^32 and INT32_MAX rows.
+constexpr int ADJ_TILE_LANES = 64;
+SSDE_HD int64_t adj_row_bytes(int C) { return (int64_t)C * (ADJ_TILE_LANES * 8); }
+SSDE_HD int64_t adj_row_offset(int row, int C) { return (int64_t)row * adj_row_bytes(C); }      // row: counted from the window's first
+SSDE_HD int64_t adj_window_span(int rows, int C) { return (int64_t)rows * adj_row_bytes(C); }
 
 // exp(x) for the row transitions.  The library's exp is one dependent Horner chain of ~12 fp64 FMAs, and three of them per row
 // (tau, nu, e^{-beta dt}) were most of what a lone wave per SIMD waited for (8-9 cycles per dependent instruction against the pipe's

@@ -433,7 +433,9 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
     a.derive = (h->knobs.no_derive || h->drift) ? 0 : 1;
     a.stream_nt = h->stream_nt ? 1 : 0;
     a.all_clean = ((h->use_shared && h->n_clean_groups == h->n_groups) || h->drift) ? 1 : 0;      // (drift: one dump layout for every group)
-    a.nstate_clean = h->drift ? h->drift_nstate
+    // (the reverse sweep's records hold the state AND its adjoint; a value-only evaluation writes the states alone -- iso_adj_kernel,
+    //  !grad -- and is checked on them alone: the adjoint halves are whatever an earlier evaluation, or a failed attempt of one, left)
+    a.nstate_clean = h->drift ? (h->drift == 3 && h->cv_adj && order < 1 ? h->drift_nstate / 2 : h->drift_nstate)
                    : h->use_shared ? shared_nstate(h->sdim, order >= 1 ? a.part_mask[0] : 0, h->model != SSDE_MODEL_BM_SSM) : 0;
     a.group_flags = h->group_flags.p;
     a.group_mode = 0;

@@ -436,6 +436,11 @@ int hostsim_balanced_window0(int glen, int nc, int window, int can_derive, int w
     return balanced_window0(glen, nc, window, can_derive != 0, win_align);
 }
 
+// where the reverse sweep's rows lie in the tile (ssde_adj.hpp: what k_iso_adj.hip forms a row's address from)
+int64_t hostsim_adj_row_bytes(int C) { return adj_row_bytes(C); }
+int64_t hostsim_adj_row_offset(int row, int C) { return adj_row_offset(row, C); }
+int64_t hostsim_adj_window_span(int rows, int C) { return adj_window_span(rows, C); }
+
 void* hostsim_policy_new(int max_chunks, int want_chunks) {
     PolicySim* s = new PolicySim();
     s->max_chunks = max_chunks; s->want_chunks = want_chunks;

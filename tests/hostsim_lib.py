@@ -98,6 +98,9 @@ def load():
         lib.hostsim_warmup.restype = C.c_int64
         lib.hostsim_balanced_window0.argtypes = [C.c_int] * 5
         lib.hostsim_balanced_window0.restype = C.c_int
+        lib.hostsim_adj_row_bytes.argtypes = [C.c_int]
+        lib.hostsim_adj_row_offset.argtypes = lib.hostsim_adj_window_span.argtypes = [C.c_int, C.c_int]
+        lib.hostsim_adj_row_bytes.restype = lib.hostsim_adj_row_offset.restype = lib.hostsim_adj_window_span.restype = C.c_int64
         lib.hostsim_policy_new.argtypes = [C.c_int, C.c_int]
         lib.hostsim_policy_new.restype = C.c_void_p
         lib.hostsim_policy_free.argtypes = [C.c_void_p]
