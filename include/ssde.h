@@ -498,6 +498,14 @@ int ssde_path_occupancy_fine(ssde_handle *h, const double *par, int32_t n_par_fu
  * tracks that take part), and intervals of those tracks whose m was cut to the cap.  Either pointer may be NULL. */
 int ssde_last_occupancy_points(const ssde_handle *h, int64_t *n_points, int64_t *n_capped);
 
+/* Of the handle's last ssde_hess, where it ran the hyper-dual lanes over time windows (scope 3, ESEAL_SSM excepted): the warm-up rows
+ * of the accepted attempt (0: one sequential window per track), the most windows a track was cut into, the attempts it took (a failed
+ * hand-over check quadruples the warm-up; the fourth failure, or a warm-up no track holds twice, ends in one sequential window) and
+ * the accepted hand-over check.  A sharded or companion-backed handle reports the largest of each over the engines that ran.  All
+ * zero before any ssde_hess and after one that ran no windowed pass (direct families, drift coefficients, ESEAL_SSM).  Any pointer
+ * may be NULL; SSDE_ERR_ARG for a NULL handle. */
+int ssde_last_hess_plan(const ssde_handle *h, int32_t *warm_up, int32_t *windows_max, int32_t *attempts, double *check);
+
 /* Multiply the warm-up overlap of the time windows by `factor` for all later evaluations
  * (factor <= 0: force one sequential window). */
 int ssde_widen_windows(ssde_handle *h, int32_t factor);

@@ -513,6 +513,8 @@ def load_library():
     lib.ssde_path_occupancy_fine.restype = C.c_int
     lib.ssde_last_occupancy_points.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.ssde_last_occupancy_points.restype = C.c_int
+    lib.ssde_last_hess_plan.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp]
+    lib.ssde_last_hess_plan.restype = C.c_int
     lib.ssde_widen_windows.argtypes = [C.c_void_p, C.c_int32]
     lib.ssde_widen_windows.restype = C.c_int
     lib.ssde_relax_windows.argtypes = [C.c_void_p]
@@ -591,7 +593,7 @@ WINDOW_TOL = 1e-11  # largest tolerated relative hand-over disagreement between 
 
 EXPORTED_SYMBOLS = ("ssde_create", "ssde_eval", "ssde_eval_device", "ssde_penalty", "ssde_report", "ssde_widen_windows", "ssde_relax_windows",
                     "ssde_info", "ssde_destroy", "ssde_last_error", "ssde_abi_version", "ssde_comm_unique_id", "ssde_comm_init_rank", "ssde_forget", "ssde_laplace_eval", "ssde_last_kernel_ms", "ssde_kernel_ms_history",
-                    "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth", "ssde_smooth_draws", "ssde_predict", "ssde_predict_draws", "ssde_path_stats", "ssde_path_occupancy", "ssde_last_occupancy_form", "ssde_path_occupancy_fine", "ssde_last_occupancy_points",
+                    "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth", "ssde_smooth_draws", "ssde_predict", "ssde_predict_draws", "ssde_path_stats", "ssde_path_occupancy", "ssde_last_occupancy_form", "ssde_path_occupancy_fine", "ssde_last_occupancy_points", "ssde_last_hess_plan",
                     "ssde_lagstats_host_m", "ssde_lagstats_read_m", "ssde_lagforms_host_m", "ssde_reduce_host", "ssde_last_finish_form", "ssde_last_gain_feed", "ssde_last_gain_rows")
 
 
@@ -881,6 +883,14 @@ class Engine:
         self._check(self.lib.ssde_hess(self._h, par.ctypes.data_as(_dp), self.n_par_full, ix.ctypes.data_as(_ip), len(ix),
                                        H.ctypes.data_as(_dp)))
         return H
+
+    def hess_plan(self):
+        """What the last hess() ran on the hyper-dual lanes (ssde_last_hess_plan): {"warm_up": rows of the accepted attempt (0: one
+        sequential window per track), "windows_max": the most windows a track was cut into, "attempts", "check": the accepted
+        hand-over check}; the largest of each over shards or a companion; zeros before any call and where no windowed pass ran."""
+        w, n, a, c = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_double(0.0)
+        self._check(self.lib.ssde_last_hess_plan(self._h, C.byref(w), C.byref(n), C.byref(a), C.byref(c)))
+        return dict(warm_up=int(w.value), windows_max=int(n.value), attempts=int(a.value), check=float(c.value))
 
     def set_option(self, option: int, value: int):
         self._check(self.lib.ssde_set_option(self._h, option, value))

@@ -356,6 +356,9 @@ __global__ __launch_bounds__(64) void direct_hess_reduce_kernel(const DirectHess
     const int tile = blockIdx.x, e = blockIdx.y, a = e / HESS_T, b = e % HESS_T;
     const int k = A.tile_i[tile] * HESS_T + a, l = A.tile_j[tile] * HESS_T + b;
     if (k >= A.nu || l >= A.nu) return;
+    // a diagonal tile holds (k, l) and (l, k), two accumulations that differ in their rounding: one of them, always the same, fills
+    // both places (two blocks storing to the same two places made the result depend on which finished last)
+    if (A.tile_i[tile] == A.tile_j[tile] && a > b) return;
     const double* p = A.partials + ((int64_t)tile * HESS_T * HESS_T + e) * n_blocks;
     double s = 0.0;
     for (int i = threadIdx.x; i < n_blocks; i += 64) s += p[i];

@@ -352,7 +352,7 @@ __global__ __launch_bounds__(WAVE) void hess_finish_kernel(const TvHessArgs A, i
             const double a = live ? out_c[k * WAVE] : 0.0, b = live ? in_n[k * WAVE] : 0.0;
             double err = fabs(a - b), sc = fmax(fabs(a), fabs(b));
             if (live && !(err == err)) err = INFINITY;
-            // scale of a component: its largest magnitude over the lanes' (every pair's) copies of it, and over its group of four parts
+            // scale of a component: its largest magnitude over the lanes' (every pair's) copies of it; each of its four hyper-dual parts is a component of its own here
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) { err = fmax(err, __shfl_xor(err, o, 64)); sc = fmax(sc, __shfl_xor(sc, o, 64)); }
             if (err > 0.0) worst = fmax(worst, err / sc);

@@ -144,7 +144,8 @@ static int hess_data_device(ssde_handle* h, const double* par, const std::vector
 // lane = direction handle (row-varying coefficients): data-term Hessian over the DIRECTIONS dk[] (indices into the handle's gradient
 // directions: log_sigma_obs and every free coefficient), host matrix Hd (n x n, column-major).  One lane per pair, hyper-dual
 // arithmetic (k_tv_hess.hip); the time windows are the evaluation's, with a warm-up of their own and a hand-over check on every
-// component -- widened until it passes, finally one sequential window.
+// component -- widened until it passes, finally one sequential window (the plan and the retry rule: ssde_windows.hpp; what
+// ran is kept for ssde_last_hess_plan).
 static int hess_tv_device(ssde_handle* h, const double* par, const std::vector<int>& dk, std::vector<double>& Hd) {
     HIPCHK(h, hipSetDevice(h->device));
     const int n = (int)dk.size();
@@ -177,21 +178,14 @@ static int hess_tv_device(ssde_handle* h, const double* par, const std::vector<i
     HIPCHK(h, d_rec.alloc((size_t)h->n * HESS_RS));
     HIPCHK(h, d_out.alloc((size_t)4 * n_pb * WAVE + 1));
     const int64_t M = h->n_seg;
-    int W = h->tv_window > 0 ? 2 * h->tv_window + WIN_ALIGN : 0;      // second-order tangents forget like t^2 rho^t
+    int W = hess_first_warmup(h->tv_window, h->knobs.hess_window, WIN_ALIGN);
     if (is_eseal(h->model)) W = 0;                                    // (one sequential window per track, as its evaluation)
     Hd.assign((size_t)n * n, 0.0);
+    h->hess_plan = HessPlanInfo();
     for (int attempt = 0;; attempt++) {
-        // windows per track: as many as keep ~2048 waves busy, each at least two alignment units of scored rows
+        // the item plan and the retry rule below: ssde_windows.hpp
         std::vector<TvItem> items;
-        const int target = h->knobs.tv_waves.value_or(2048);
-        const int nc_cap = (int)std::max<int64_t>(1, (target + M * n_pb - 1) / (M * n_pb));
-        for (int64_t t = 0; t < M; t++) {
-            const int L = h->tv_ns_host[(size_t)t];
-            int nc = 1;
-            if (W > 0 && L >= 2 * W) nc = std::max(1, std::min(nc_cap, (L + 2 * WIN_ALIGN - 1) / (2 * WIN_ALIGN)));
-            for (int b = 0; b < n_pb; b++)
-                for (int c = 0; c < nc; c++) items.push_back({(int32_t)t, c, nc, b});
-        }
+        hess_item_plan(h->tv_ns_host, M, n_pb, W, h->knobs.tv_waves.value_or(2048), WIN_ALIGN, items);
         d_items.release(); d_bnd.release(); d_part.release();
         HIPCHK(h, d_items.upload(items));
         HIPCHK(h, d_bnd.alloc(items.size() * 2 * HESS_NSTATE * WAVE));
@@ -215,7 +209,12 @@ static int hess_tv_device(ssde_handle* h, const double* par, const std::vector<i
         HIPCHK(h, hipMemcpyAsync(out.data(), d_out.p, out.size() * 8, hipMemcpyDeviceToHost, s));
         HIPCHK(h, hipStreamSynchronize(s));
         const double check = out.back();
-        if (check <= 1e-10 || W == 0) {
+        if (check <= SSDE_HESS_WINDOW_TOL || W == 0) {
+            if (!is_eseal(h->model)) {
+                int nc_max = 0;
+                for (const TvItem& it : items) nc_max = std::max(nc_max, (int)it.nc);
+                h->hess_plan.warm_up = W; h->hess_plan.windows_max = nc_max; h->hess_plan.attempts = attempt + 1; h->hess_plan.check = check;
+            }
             int p = 0;
             for (int a2 = 0; a2 < n; a2++)
                 for (int b2 = a2; b2 < n; b2++, p++) {
@@ -225,8 +224,7 @@ static int hess_tv_device(ssde_handle* h, const double* par, const std::vector<i
             break;
         }
         // the hand-over of some component disagrees: a longer warm-up, finally one sequential window
-        W = attempt >= 3 ? 0 : 4 * W;
-        if ((int64_t)2 * W > h->glen_max) W = 0;
+        W = hess_next_warmup(W, attempt, h->glen_max);
     }
     return SSDE_OK;
 }
@@ -248,6 +246,7 @@ int hess_exact(ssde_handle* h, const double* par, const int32_t* idx, int n_idx,
         }
     }
     for (size_t k = 0; k < (size_t)n_idx * n_idx; k++) H[k] = 0.0;
+    h->hess_plan = HessPlanInfo();
     // ---- data term: the entries that are coefficients of the linear predictor -------------------------------------
     std::vector<int> cidx, cpos;
     for (int k = 0; k < n_idx; k++) {
@@ -278,6 +277,7 @@ int hess_exact(ssde_handle* h, const double* par, const int32_t* idx, int n_idx,
             }
             int st = hess_tv_device(t, par, dk, Hd);
             if (st) { h->err = t->err; return st; }
+            if (t != h) h->hess_plan.merge(t->hess_plan);               // a companion, shards: the largest over the engines that ran
             for (size_t k = 0; k < Hsum.size(); k++) Hsum[k] += Hd[k];
             return SSDE_OK;
         };
@@ -392,6 +392,15 @@ int hess_exact(ssde_handle* h, const double* par, const int32_t* idx, int n_idx,
 }
 
 }  // namespace ssde_engine
+
+extern "C" int ssde_last_hess_plan(const ssde_handle* h, int32_t* warm_up, int32_t* windows_max, int32_t* attempts, double* check) {
+    if (!h) return SSDE_ERR_ARG;
+    if (warm_up) *warm_up = h->hess_plan.warm_up;
+    if (windows_max) *windows_max = h->hess_plan.windows_max;
+    if (attempts) *attempts = h->hess_plan.attempts;
+    if (check) *check = h->hess_plan.check;
+    return SSDE_OK;
+}
 
 extern "C" int ssde_hess(ssde_handle* h, const double* par, int32_t n_par_full, const int32_t* idx, int32_t n_idx, double* hess) {
     if (!h || !par || !idx || !hess || n_idx < 1) return SSDE_ERR_ARG;

@@ -19,6 +19,7 @@ struct Knobs {
     bool no_colvar = false, no_colvar_full = false, cv_no_share = false, cv_no_mu_cols = false, cv_no_few = false, tv_no_lean = false;
     bool no_exact_hess = false, publish = false, trace = false;
     std::optional<int> chunks, window, adj_tail, tv_waves, tv_minlen;   // time-window geometry (window, adj_tail, tv_waves >= 1; tv_minlen a multiple of WIN_ALIGN)
+    std::optional<int> hess_window;                  // first warm-up of the Hessian pass's windows, rows (>= 1, rounded up to WIN_ALIGN)
     std::optional<int> drift_min_tracks, cv_adj;     // a track count decides for the register lanes / 0: forward tangents everywhere, 2: the reverse sweep for few columns too
     std::optional<int> lagstats;                     // 0: never built, 2: built whatever the rule says, 1: the rule (as unset)
     std::optional<bool> fused_finalize;              // 1: the finalising work inside iso_shared_kernel (slower); 0: always a finalize launch after
@@ -28,7 +29,7 @@ struct Knobs {
     double grid_rtol = 1e-12;                        // how far an interval may be from the grid step and still count as regular (lattice_pad)
 };
 
-// win_align: WIN_ALIGN of ssde_device.hpp (SSDE_TV_MINLEN is rounded down to it), which a host-only header does not include
+// win_align: WIN_ALIGN of ssde_device.hpp (SSDE_TV_MINLEN is rounded down to it, SSDE_HESS_WINDOW up), which a host-only header does not include
 inline Knobs knobs_from_env(int win_align) {
     static const struct { const char* name; bool Knobs::*flag; } switches[] = {
         {"SSDE_NO_QUIET", &Knobs::no_quiet}, {"SSDE_QUIET_ALWAYS", &Knobs::quiet_always}, {"SSDE_NO_NA_SORT", &Knobs::no_na_sort}, {"SSDE_NO_SHARED", &Knobs::no_shared}, {"SSDE_NO_TV", &Knobs::no_tv},
@@ -46,6 +47,7 @@ inline Knobs knobs_from_env(int win_align) {
     k.adj_tail = at_least(1, num("SSDE_ADJ_TAIL"));
     k.tv_waves = at_least(1, num("SSDE_TV_WAVES"));
     if (auto v = num("SSDE_TV_MINLEN")) k.tv_minlen = std::max(win_align, *v / win_align * win_align);
+    if (auto v = num("SSDE_HESS_WINDOW")) k.hess_window = (std::min(std::max(1, *v), 1 << 24) + win_align - 1) / win_align * win_align;   // (64 x it fits an int)
     k.quiet_window = std::max(0, num("SSDE_QUIET_WINDOW").value_or(0));
     k.iso_split = str("SSDE_ISO_SPLIT");
     k.drift_min_tracks = num("SSDE_DRIFT_MIN_TRACKS");

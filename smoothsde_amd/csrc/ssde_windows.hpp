@@ -1,13 +1,15 @@
 // ssde_windows.hpp -- the time-window policy of the register and row-varying paths, as pure functions over plain
-// structs: the stationary closed-loop radius, the warm-up and chunk plan, the geometry that follows the plan, and the retry /
-// rounding-floor / probation state machine around an evaluation.  Host code only, no HIP type: the engine (ssde_engine*.hip) calls it
-// next to its launches, tests/hostsim compiles it with g++ and tests/test_windows_host.py drives it without a GPU.
+// structs: the stationary closed-loop radius, the warm-up and chunk plan, the geometry that follows the plan, the retry /
+// rounding-floor / probation state machine around an evaluation, and the item plan and retry rule of the Hessian pass.  Host code
+// only, no HIP type: the engine (ssde_engine*.hip, ssde_hess.hip) calls it next to its launches, tests/hostsim compiles it with g++
+// and tests/test_windows_host.py and tests/test_hess_plan_host.py drive it without a GPU.
 #ifndef SSDE_WINDOWS_HPP
 #define SSDE_WINDOWS_HPP
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <optional>
+#include <vector>
 
 #include "../../include/ssde.h"
 #include "ssde_math.hpp"
@@ -506,6 +508,54 @@ struct WindowPolicy {
     // ssde_widen_windows (factor >= 1; the caller sends every engine to one sequential window for factor <= 0), ssde_relax_windows
     void widen(int factor) { if (factor > 0 && window_boost < (1 << 20)) window_boost *= factor; }
     void relax() { window_boost = std::max(1, window_boost / 2); }
+};
+
+// ---- the Hessian pass of the lane = direction path (ssde_hess.hip: hess_tv_device, k_tv_hess.hip) ---------------------------------
+// Its windows are window_bounds' equal windows (t0 = 0) with a warm-up of its own; one wave per (track, pair block, window).
+constexpr double SSDE_HESS_WINDOW_TOL = 1e-10;   // largest tolerated hand-over disagreement of a hyper-dual component
+
+// the first attempt's warm-up: second-order tangents forget like t^2 rho^t -- twice the evaluation's warm-up and one alignment
+// unit, 0 (one sequential window per track) where the evaluation has none; SSDE_HESS_WINDOW (rows, already aligned) replaces either
+// (testing: the hand-over check decides, as everywhere)
+inline int hess_first_warmup(int tv_window, const std::optional<int>& knob, int win_align) {
+    if (knob) return *knob;
+    return tv_window > 0 ? 2 * tv_window + win_align : 0;
+}
+// windows of a track of L steps: as many as keep `waves` waves busy over M tracks x n_pb pair blocks, each at least two alignment
+// units of scored rows, and only on tracks of at least two warm-ups
+inline int hess_window_cap(int waves, int64_t M, int n_pb) { return (int)std::max<int64_t>(1, (waves + M * n_pb - 1) / (M * n_pb)); }
+inline int hess_track_windows(int L, int W, int nc_cap, int win_align) {
+    if (!(W > 0 && L >= 2 * W)) return 1;
+    return std::max(1, std::min(nc_cap, (L + 2 * win_align - 1) / (2 * win_align)));
+}
+// The work items in (track, pair block, window) order: the windows of one (track, pair block) are neighbours in the list, which is
+// what hess_finish_kernel's hand-over check (item against item + 1) assumes.  Item: {track, window c, of nc, pair block} (TvItem).
+template <class Item, class Lengths>
+inline void hess_item_plan(const Lengths& track_steps, int64_t M, int n_pb, int W, int waves, int win_align, std::vector<Item>& items) {
+    items.clear();
+    const int nc_cap = hess_window_cap(waves, M, n_pb);
+    for (int64_t t = 0; t < M; t++) {
+        const int nc = hess_track_windows((int)track_steps[(size_t)t], W, nc_cap, win_align);
+        for (int b = 0; b < n_pb; b++)
+            for (int c = 0; c < nc; c++) items.push_back(Item{(int32_t)t, c, nc, b});
+    }
+}
+// after a failed hand-over check of attempt `attempt` (0-based): four times the warm-up; one sequential window (0) after the
+// fourth failure or where a track no longer holds two warm-ups
+inline int hess_next_warmup(int W, int attempt, int glen_max) {
+    W = attempt >= 3 ? 0 : 4 * W;
+    if ((int64_t)2 * W > glen_max) W = 0;
+    return W;
+}
+// what ssde_last_hess_plan reports of the last ssde_hess: the accepted attempt's warm-up, the most windows a track was cut into,
+// the attempts it took and the accepted hand-over check; all 0 where no windowed pass ran.  Several engines: the largest of each.
+struct HessPlanInfo {
+    int warm_up = 0, windows_max = 0, attempts = 0;
+    double check = 0.0;
+    void merge(const HessPlanInfo& o) {
+        warm_up = std::max(warm_up, o.warm_up); windows_max = std::max(windows_max, o.windows_max);
+        attempts = std::max(attempts, o.attempts); check = std::max(check, o.check);
+    }
 };
 
 }  // namespace ssde_engine

@@ -357,7 +357,7 @@ int hostsim_knobs(int win_align, char* buf, int cap) {
     put("CV_NO_SHARE", k.cv_no_share); put("CV_NO_MU_COLS", k.cv_no_mu_cols); put("CV_NO_FEW", k.cv_no_few);
     put("TV_NO_LEAN", k.tv_no_lean); put("NO_EXACT_HESS", k.no_exact_hess); put("PUBLISH", k.publish); put("TRACE", k.trace);
     opt("CHUNKS", k.chunks); opt("WINDOW", k.window); opt("ADJ_TAIL", k.adj_tail); opt("TV_WAVES", k.tv_waves);
-    opt("TV_MINLEN", k.tv_minlen); put("QUIET_WINDOW", k.quiet_window); opt("ISO_SPLIT", k.iso_split);
+    opt("TV_MINLEN", k.tv_minlen); opt("HESS_WINDOW", k.hess_window); put("QUIET_WINDOW", k.quiet_window); opt("ISO_SPLIT", k.iso_split);
     opt("DRIFT_MIN_TRACKS", k.drift_min_tracks); opt("CV_ADJ", k.cv_adj); opt("LAGSTATS", k.lagstats);
     opt("FUSED_FINALIZE", k.fused_finalize); put("GRID_RTOL", k.grid_rtol); put("ADJ_DIAG", k.adj_diag);
     opt("WAVE_CLOCK", k.wave_clock);
@@ -434,6 +434,20 @@ int64_t hostsim_warmup(double rho, int slack, int knob, int boost, int align) {
 }
 int hostsim_balanced_window0(int glen, int nc, int window, int can_derive, int win_align) {
     return balanced_window0(glen, nc, window, can_derive != 0, win_align);
+}
+
+// ---- the Hessian pass's plan (csrc/ssde_windows.hpp) -------------------------------------------------------------------------------
+int hostsim_hess_first_warmup(int tv_window, int knob, int win_align) {
+    return hess_first_warmup(tv_window, knob >= 0 ? std::optional<int>(knob) : std::nullopt, win_align);
+}
+int hostsim_hess_next_warmup(int W, int attempt, int glen_max) { return hess_next_warmup(W, attempt, glen_max); }
+// items = [track, c, nc, block] per work item; returns their number (nothing is written past cap items)
+int64_t hostsim_hess_item_plan(const int32_t* track_steps, int64_t M, int n_pb, int W, int waves, int win_align, int32_t* items, int64_t cap) {
+    struct Item { int32_t track, c, nc, b; };
+    std::vector<Item> v;
+    hess_item_plan(track_steps, M, n_pb, W, waves, win_align, v);
+    for (size_t k = 0; k < v.size() && (int64_t)k < cap; k++) { items[4 * k] = v[k].track; items[4 * k + 1] = v[k].c; items[4 * k + 2] = v[k].nc; items[4 * k + 3] = v[k].b; }
+    return (int64_t)v.size();
 }
 
 // where the reverse sweep's rows lie in the tile (ssde_adj.hpp: what k_iso_adj.hip forms a row's address from)

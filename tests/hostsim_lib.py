@@ -98,6 +98,11 @@ def load():
         lib.hostsim_warmup.restype = C.c_int64
         lib.hostsim_balanced_window0.argtypes = [C.c_int] * 5
         lib.hostsim_balanced_window0.restype = C.c_int
+        lib.hostsim_hess_first_warmup.argtypes = [C.c_int] * 3
+        lib.hostsim_hess_next_warmup.argtypes = [C.c_int] * 3
+        _i32 = C.POINTER(C.c_int32)
+        lib.hostsim_hess_item_plan.argtypes = [_i32, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _i32, C.c_int64]
+        lib.hostsim_hess_item_plan.restype = C.c_int64
         lib.hostsim_adj_row_bytes.argtypes = [C.c_int]
         lib.hostsim_adj_row_offset.argtypes = lib.hostsim_adj_window_span.argtypes = [C.c_int, C.c_int]
         lib.hostsim_adj_row_bytes.restype = lib.hostsim_adj_row_offset.restype = lib.hostsim_adj_window_span.restype = C.c_int64
@@ -178,6 +183,26 @@ def window_geometry(consts, params, boost=1, gave_up=False, ev=None, **facts):
     g = {k: int(v) for k, v in zip(GEOMETRY_OUT, out[8:])}
     g["first"], g["plan"] = _plan_dict(out[:4]), _plan_dict(out[4:8])
     return g
+
+
+# ---- the Hessian pass's plan (csrc/ssde_windows.hpp: hess_first_warmup, hess_item_plan, hess_next_warmup) -------------------------
+def hess_first_warmup(tv_window, knob, win_align):
+    """knob: SSDE_HESS_WINDOW as knobs_from_env leaves it (None: unset)"""
+    return load().hostsim_hess_first_warmup(tv_window, -1 if knob is None else knob, win_align)
+
+
+def hess_next_warmup(W, attempt, glen_max):
+    return load().hostsim_hess_next_warmup(W, attempt, glen_max)
+
+
+def hess_item_plan(track_steps, n_pb, W, waves, win_align):
+    """the work items as (track, window c, of nc, pair block) rows, in launch order"""
+    ts = np.ascontiguousarray(track_steps, dtype=np.int32)
+    _i32 = C.POINTER(C.c_int32)
+    n = load().hostsim_hess_item_plan(ts.ctypes.data_as(_i32), len(ts), n_pb, W, waves, win_align, None, 0)
+    items = np.zeros((max(int(n), 1), 4), dtype=np.int32)
+    assert load().hostsim_hess_item_plan(ts.ctypes.data_as(_i32), len(ts), n_pb, W, waves, win_align, items.ctypes.data_as(_i32), n) == n
+    return items[:n]
 
 
 class WindowPolicy:

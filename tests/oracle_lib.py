@@ -64,6 +64,8 @@ def _load_quad():
         _QLIB = C.CDLL(path)
         _QLIB.oracle_eval_quad.argtypes = [C.POINTER(SsdeDesc), _dp, C.c_int, _dp, _dp, C.c_double]
         _QLIB.oracle_eval_quad.restype = C.c_int
+        _QLIB.oracle_hess_quad.argtypes = [C.POINTER(SsdeDesc), _dp, C.POINTER(C.c_int32), C.c_int, _dp, C.c_double, C.c_int]
+        _QLIB.oracle_hess_quad.restype = C.c_int
     return _QLIB
 
 
@@ -79,6 +81,25 @@ def oracle_eval_quad(problem: Problem, par, order: int = 1, fd_step: float = 1e-
     st = _QLIB.oracle_eval_quad(C.byref(d), par.ctypes.data_as(_dp), order, C.byref(val), grad.ctypes.data_as(_dp), fd_step)
     assert st == 0
     return (val.value, grad) if order >= 1 else val.value
+
+
+def oracle_hess_quad(problem: Problem, par, idx, fd_step: float = 1e-8, threads: int | None = None):
+    """Hessian of nllk + penalty over the full-parameter indices idx (every one differentiated, fixed or not): second central
+    differences of the binary128 function (oracle/oracle_quad.cpp), each entry rounded to double once; the pairs are dealt to
+    `threads` threads (default min(16, the machine's)).  Honours keep_P_symmetric."""
+    CALLS[0] += 1
+    _load_quad()
+    d = problem.desc()
+    par = np.ascontiguousarray(par, dtype=np.float64)
+    idx = np.ascontiguousarray(idx, dtype=np.int32)
+    assert par.size == problem.n_par_full and idx.size >= 1
+    if threads is None:
+        threads = min(16, os.cpu_count() or 1)
+    H = np.zeros((idx.size, idx.size))
+    st = _QLIB.oracle_hess_quad(C.byref(d), par.ctypes.data_as(_dp), idx.ctypes.data_as(C.POINTER(C.c_int32)), int(idx.size),
+                                H.ctypes.data_as(_dp), float(fd_step), int(threads))
+    assert st == 0
+    return H
 
 
 _FLIB = None

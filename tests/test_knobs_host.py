@@ -52,7 +52,7 @@ def clean_env(monkeypatch):
 def test_no_variable_set_is_the_documented_default(clean_env):
     k = hostsim_lib.knobs(WIN_ALIGN)
     assert set(k) == set(_header_names())
-    unset = {"SSDE_CHUNKS", "SSDE_WINDOW", "SSDE_ADJ_TAIL", "SSDE_TV_WAVES", "SSDE_TV_MINLEN", "SSDE_ISO_SPLIT",
+    unset = {"SSDE_CHUNKS", "SSDE_WINDOW", "SSDE_ADJ_TAIL", "SSDE_TV_WAVES", "SSDE_TV_MINLEN", "SSDE_HESS_WINDOW", "SSDE_ISO_SPLIT",
              "SSDE_DRIFT_MIN_TRACKS", "SSDE_CV_ADJ", "SSDE_LAGSTATS", "SSDE_FUSED_FINALIZE", "SSDE_WAVE_CLOCK"}
     for name, v in k.items():
         if name in unset:
@@ -67,6 +67,8 @@ def test_no_variable_set_is_the_documented_default(clean_env):
     ("SSDE_WINDOW", "0", "1"), ("SSDE_WINDOW", "48", "48"),
     ("SSDE_ADJ_TAIL", "-3", "1"), ("SSDE_TV_WAVES", "0", "1"),
     ("SSDE_TV_MINLEN", "1", str(WIN_ALIGN)), ("SSDE_TV_MINLEN", str(3 * WIN_ALIGN + 5), str(3 * WIN_ALIGN)),
+    ("SSDE_HESS_WINDOW", "0", str(WIN_ALIGN)), ("SSDE_HESS_WINDOW", str(WIN_ALIGN), str(WIN_ALIGN)),
+    ("SSDE_HESS_WINDOW", str(2 * WIN_ALIGN + 1), str(3 * WIN_ALIGN)), ("SSDE_HESS_WINDOW", "2147483647", str(1 << 24)),
     ("SSDE_QUIET_WINDOW", "-5", "0"), ("SSDE_QUIET_WINDOW", "32", "32"),
     ("SSDE_LAGSTATS", "0", "0"), ("SSDE_LAGSTATS", "1", "1"), ("SSDE_LAGSTATS", "2", "2"), ("SSDE_LAGSTATS", "7", "1"),
     ("SSDE_FUSED_FINALIZE", "0", "0"), ("SSDE_FUSED_FINALIZE", "1", "1"),
