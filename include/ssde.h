@@ -37,6 +37,8 @@
  *                         refined by Gaussian bridges inside the intervals and simulated past a track's last row, without NA rows
  *   ssde_path_occupancy_fine <- (new) that utilisation distribution on the refined paths of ssde_predict_draws: every interval's
  *                         weight spread over the points of a bridge between its two fixes, so that sparse data leave no holes
+ *   ssde_path_proximity <- (new) how close the drawn paths of two tracks come, where, and for how long they are within up to eight
+ *                         radii of each other: the states of ssde_predict_draws paired and reduced on the device, per pair and draw
  *   ssde_penalty       <- smoothing penalty     (nllk_ctcrw.hpp:254-280, nllk_sde.hpp:89-124)
  *   ssde_info          <- InfoADFunObject       (src/init.c:7)
  *   ssde_forget        <- (new) drops the memo of ssde_eval
@@ -497,6 +499,45 @@ int ssde_path_occupancy_fine(ssde_handle *h, const double *par, int32_t n_par_fu
 /* of the handle's last ssde_path_occupancy_fine: path points per draw that carried weight (the sum of N_j over the state rows of the
  * tracks that take part), and intervals of those tracks whose m was cut to the cap.  Either pointer may be NULL. */
 int ssde_last_occupancy_points(const ssde_handle *h, int64_t *n_points, int64_t *n_capped);
+
+/* Proximity of posterior paths between tracks (definitions: DESIGN.md §3.16).  Point i compares side A, the query (qa_row[i],
+ * qa_off[i]), with side B, the query (qb_row[i], qb_off[i]); both are queries of ssde_predict_draws: a caller's row and an offset >= 0
+ * past its stamp.  Pair p owns the points pair_ptr[p] .. pair_ptr[p + 1] - 1: a CSR list with pair_ptr[0] == 0, non-decreasing,
+ * n_point = pair_ptr[n_pairs].  A pair may be empty.  Nothing requires the two sides to be different tracks or one side to stay on
+ * one track: a pair is a set of points; the same track at two times is legal, and so are two identical sides.
+ *   1. The states.  For draw number draw0 + q the two states of point i are exactly what ssde_predict_draws returns for ONE call
+ *      whose 2 * n_point queries are all the A queries followed by all the B queries: they go through one plan, are jointly
+ *      distributed inside an interval and lie on the path every other call uses for that seed and draw number.  Tracks are
+ *      independent given par, so draw q of two tracks at one clock time is a joint draw.  The position columns are ssde_path_stats'
+ *      and the distance is its Euclidean one (|difference| for n_dim = 1).
+ *   2. stats [n_pairs x n_stat x n_draws], n_stat = 2 + n_radii, element (p, k, q) at p + n_pairs * (k + n_stat * q):
+ *      k = 0 the smallest distance over the pair's points; k = 1 the index inside the pair (0-based, as a double) of the first point
+ *      that attains it (a tie gives the smallest index); k = 2 + r the sum of w_i over the pair's points with dist_i <= radii[r].
+ *   3. Fixed-point sums, by ssde_path_occupancy's rule with e taken for wmax (the largest weight; 1 without weights), n_point and
+ *      ONE draw: every w_i enters as nearbyint(ldexp(w_i, -e)) quanta, the quanta are summed as unsigned 64-bit integers and the
+ *      output is ldexp((double)sum, e).  The quantum does not depend on n_draws, so draw ranges cut over calls give the whole range's
+ *      numbers back bitwise.  The minimum, its index and the sums do not depend on the order in which points are combined: the result
+ *      is bitwise independent of SSDE_OPT_SMOOTH_BUDGET_MB, of the devices and of repeated calls.  weight: [n_point] in host memory, or
+ *      NULL for 1.  wmax == 0 gives 0 in every sum.
+ *   4. NaN.  Every statistic of a (pair, draw) is NaN if either side of any of its points has a position that is not finite (as in
+ *      ssde_path_stats; a query on a track's first row is such a case), and every statistic of an empty pair is NaN.
+ * SSDE_ERR_ARG for NULL h / par / a query array / pair_ptr / stats; n_pairs < 1; a pair_ptr that is not as described, or n_point <
+ * 1; a row outside [0, n), an offset that is negative or not finite; n_draws < 1, draw0 < 0, draw0 + n_draws >= 2^28; n_radii outside
+ * 0 ... SSDE_PROX_MAX_RADII, radii NULL with n_radii > 0, a radius that is NaN or < 0 (+inf is allowed); a weight that is negative or
+ * not finite; flags != 0; the limits of ssde_predict_draws (2^32 tracks, 2^32 distinct offsets in an interval).  SSDE_ERR_MODEL exactly
+ * where ssde_path_stats gives it.  Every check runs before anything touches the device.  Lattice-padded handles, PATH_TV handles,
+ * row-varying parameters and multi-device handles (a pair may straddle shards) are served.  Leaves the memo, the window state, the TV
+ * records, n_evals / n_memo_hits and every later result of every other call as they were. */
+#define SSDE_PROX_MAX_RADII 8
+int ssde_path_proximity(ssde_handle *h, const double *par, int32_t n_par_full, uint64_t seed, int64_t draw0, int32_t n_draws,
+                        const int64_t *qa_row, const double *qa_off, const int64_t *qb_row, const double *qb_off,
+                        const int64_t *pair_ptr, int32_t n_pairs, const double *weight,
+                        const double *radii, int32_t n_radii, double *stats, uint32_t flags);
+/* Of the handle's last ssde_path_proximity: the tiles (every pair is cut into tiles of 256 consecutive points; a tile never spans
+ * pairs and an empty pair has none), the most tiles one pair was cut into, the batches of draws, and the route: 1 the positions never
+ * left the device, 2 they were gathered from the shards of a multi-device handle.  All zero before any call.  Any pointer may be NULL;
+ * SSDE_ERR_ARG for a NULL handle. */
+int ssde_last_proximity_plan(const ssde_handle *h, int64_t *n_tiles, int64_t *tiles_max, int32_t *n_batches, int32_t *route);
 
 /* Of the handle's last ssde_hess, where it ran the hyper-dual lanes over time windows (scope 3, ESEAL_SSM excepted): the warm-up rows
  * of the accepted attempt (0: one sequential window per track), the most windows a track was cut into, the attempts it took (a failed

@@ -513,6 +513,12 @@ def load_library():
     lib.ssde_path_occupancy_fine.restype = C.c_int
     lib.ssde_last_occupancy_points.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.ssde_last_occupancy_points.restype = C.c_int
+    _lp64 = C.POINTER(C.c_int64)
+    lib.ssde_path_proximity.argtypes = [C.c_void_p, _dp, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, _lp64, _dp, _lp64, _dp, _lp64,
+                                        C.c_int32, _dp, _dp, C.c_int32, _dp, C.c_uint32]
+    lib.ssde_path_proximity.restype = C.c_int
+    lib.ssde_last_proximity_plan.argtypes = [C.c_void_p, _lp64, _lp64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.ssde_last_proximity_plan.restype = C.c_int
     lib.ssde_last_hess_plan.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp]
     lib.ssde_last_hess_plan.restype = C.c_int
     lib.ssde_widen_windows.argtypes = [C.c_void_p, C.c_int32]
@@ -587,13 +593,14 @@ class EngineError(RuntimeError):
 PATH_MAX_REGIONS = 8   # SSDE_PATH_MAX_REGIONS (include/ssde.h)
 DRAWS_DEVICE_OUT = 1   # ssde_smooth_draws flag: `draws` is an HBM pointer on the handle's device (include/ssde.h)
 OCC_FORCE_GLOBAL = 1   # ssde_path_occupancy flag: every wavefront group runs the global form (SSDE_OCC_FORCE_GLOBAL)
+PROX_MAX_RADII = 8     # SSDE_PROX_MAX_RADII: the most radii of one ssde_path_proximity
 OCC_MAX_SUB = 64       # SSDE_OCC_MAX_SUB: the most sub-steps ssde_path_occupancy_fine cuts an interval into
 
 WINDOW_TOL = 1e-11  # largest tolerated relative hand-over disagreement between time windows
 
 EXPORTED_SYMBOLS = ("ssde_create", "ssde_eval", "ssde_eval_device", "ssde_penalty", "ssde_report", "ssde_widen_windows", "ssde_relax_windows",
                     "ssde_info", "ssde_destroy", "ssde_last_error", "ssde_abi_version", "ssde_comm_unique_id", "ssde_comm_init_rank", "ssde_forget", "ssde_laplace_eval", "ssde_last_kernel_ms", "ssde_kernel_ms_history",
-                    "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth", "ssde_smooth_draws", "ssde_predict", "ssde_predict_draws", "ssde_path_stats", "ssde_path_occupancy", "ssde_last_occupancy_form", "ssde_path_occupancy_fine", "ssde_last_occupancy_points", "ssde_last_hess_plan",
+                    "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth", "ssde_smooth_draws", "ssde_predict", "ssde_predict_draws", "ssde_path_stats", "ssde_path_occupancy", "ssde_last_occupancy_form", "ssde_path_occupancy_fine", "ssde_last_occupancy_points", "ssde_last_hess_plan", "ssde_path_proximity", "ssde_last_proximity_plan",
                     "ssde_lagstats_host_m", "ssde_lagstats_read_m", "ssde_lagforms_host_m", "ssde_reduce_host", "ssde_last_finish_form", "ssde_last_gain_feed", "ssde_last_gain_rows")
 
 
@@ -1106,6 +1113,49 @@ class Engine:
         a, b = C.c_int64(0), C.c_int64(0)
         self._check(self.lib.ssde_last_occupancy_points(self._h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
+
+    def path_proximity(self, par, qa_rows, qa_offs, qb_rows, qb_offs, pair_ptr, n_draws: int, seed: int = 0, draw0: int = 0,
+                       radii=None, weight=None):
+        """How close the posterior paths of two tracks come, reduced on the device (ssde_path_proximity): an array
+        of shape (n_draws, n_pairs, n_stat), n_stat = 2 + n_radii.  Point i compares the query (qa_rows[i], qa_offs[i]) with
+        (qb_rows[i], qb_offs[i]), both queries of predict_draws; pair p owns the points pair_ptr[p] .. pair_ptr[p + 1] - 1.  Per pair
+        and draw: the smallest distance between the two drawn positions, the index inside the pair of the first point that attains
+        it, then per radius the sum of `weight` (one finite number >= 0 per point, or None for 1) over the points within it.  Draw k
+        is draw number draw0 + k of the stream `seed`: the states are the ones predict_draws returns for the A queries followed by
+        the B queries.  The sums are integers of a fixed quantum that does not depend on n_draws: the same bits whatever the
+        chunking, the devices or how a draw range is cut over calls.  NaN for an empty pair and for a (pair, draw) with a position
+        that is not finite (a query on a track's first row)."""
+        par = np.ascontiguousarray(par, dtype=np.float64)
+        if par.shape != (self.n_par_full,):
+            raise ValueError(f"par must have length {self.n_par_full}")
+        ra, rb, pp = (np.ascontiguousarray(v, dtype=np.int64).ravel() for v in (qa_rows, qb_rows, pair_ptr))
+        oa, ob = (np.ascontiguousarray(v, dtype=np.float64).ravel() for v in (qa_offs, qb_offs))
+        if not (ra.shape == rb.shape == oa.shape == ob.shape):
+            raise ValueError("the four query arrays must have the same length")
+        if len(pp) < 1 or (len(pp) > 1 and int(pp[-1]) != len(ra)):
+            raise ValueError("pair_ptr must hold n_pairs + 1 entries and end at the number of points")
+        rad = np.zeros(0) if radii is None else np.ascontiguousarray(radii, dtype=np.float64).ravel()
+        w = None
+        if weight is not None:
+            w = np.ascontiguousarray(weight, dtype=np.float64)
+            if w.shape != ra.shape:
+                raise ValueError("weight must hold one number per point")
+        n_pairs, n_stat = len(pp) - 1, 2 + len(rad)
+        lp = C.POINTER(C.c_int64)
+        buf = np.zeros((max(int(n_draws), 0), max(n_stat, 0), max(n_pairs, 0)))         # element (p, k, q) at p + n_pairs (k + n_stat q)
+        self._check(self.lib.ssde_path_proximity(self._h, par.ctypes.data_as(_dp), self.n_par_full, int(seed), int(draw0), int(n_draws),
+                                                 ra.ctypes.data_as(lp), oa.ctypes.data_as(_dp), rb.ctypes.data_as(lp), ob.ctypes.data_as(_dp),
+                                                 pp.ctypes.data_as(lp), n_pairs, None if w is None else w.ctypes.data_as(_dp),
+                                                 rad.ctypes.data_as(_dp) if len(rad) else None, len(rad), buf.ctypes.data_as(_dp), 0))
+        return buf.transpose(0, 2, 1)
+
+    def last_proximity_plan(self):
+        """Of the last path_proximity (ssde_last_proximity_plan): a dict with n_tiles (every pair is cut into tiles of 256 points),
+        tiles_max (the most tiles of one pair), n_batches (of draws) and route (1: the positions never left the device, 2: they were
+        gathered from the shards of a multi-device handle); zeros before any call."""
+        a, b, c, d = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int32(0)
+        self._check(self.lib.ssde_last_proximity_plan(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return {"n_tiles": int(a.value), "tiles_max": int(b.value), "n_batches": int(c.value), "route": int(d.value)}
 
     def close(self):
         if self._h:

@@ -727,6 +727,37 @@ struct OccFineArgs {
     unsigned long long* acc_out;
 };
 hipError_t launch_path_occ_fine(const OccFineArgs& a, bool tile, hipStream_t s);
+// ---- proximity of the drawn paths between tracks (k_path_prox.hip, ssde_prox.hpp) ----
+// One batch of n_draws draws of 2 n_point queries (side A, then side B) in `pos`: element (k, c, q) at k + n_query * (c + n_col * q),
+// draw_stride = n_query * n_col; the position columns are DenseDims::z(c) of n_col = sdim state columns (packed = 0: the buffer
+// predict_draws_query_kernel filled) or c of n_col = d (packed = 1: the gathered buffer of a multi-device parent).  Tile i holds the
+// points tile_first[i] .. + tile_count[i], the first of them point tile_idx0[i] of its pair; pair p owns the tiles pair_tile[p] ..
+// pair_tile[p + 1].  part: word k of the record of (tile i, draw q) at k * n_tiles * n_draws + i + n_tiles * q.  stats: element (p, k, q)
+// of [n_pairs x n_stat x n_draws of the batch].
+#ifndef SSDE_PROX_MAX_RADII
+#define SSDE_PROX_MAX_RADII 8
+#endif
+struct ProxArgs {
+    int model, d;
+    const double* pos;
+    int64_t n_point, n_query, draw_stride;
+    int packed, n_draws;
+    const int64_t* tile_first;   // [n_tiles]
+    const int64_t* tile_idx0;    // [n_tiles]
+    const int32_t* tile_count;   // [n_tiles]
+    const int64_t* pair_tile;    // [n_pairs + 1]
+    int64_t n_tiles, n_pairs;
+    const uint64_t* wq;          // [n_point]: w_i in quanta, or NULL: every point weighs `unit`
+    uint64_t unit;
+    uint64_t* part;              // [PROX_REC x n_tiles x n_draws]
+    double* stats;
+    int n_radii, e;              // the call's quantum 2^e
+    double radii[SSDE_PROX_MAX_RADII];
+};
+hipError_t launch_prox_tile(const ProxArgs& a, hipStream_t s);
+hipError_t launch_prox_fold(const ProxArgs& a, hipStream_t s);
+hipError_t launch_prox_gather(const double* src, int64_t n_src, int n_col, int col_step, int d, int n_draws, const int64_t* idx,
+                              double* dst, int64_t n_dst, hipStream_t s);
 hipError_t launch_tv_a0(const TvArgs& a, const double* a0_src, const int64_t* trk_seg, int64_t n_seg, int sdim,
                         double* a0_dst, hipStream_t s);
 hipError_t launch_tv_prepare(const TvArgs& a, hipStream_t s);

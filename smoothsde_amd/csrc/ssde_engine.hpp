@@ -205,7 +205,9 @@ struct ssde_handle {
     int last_gain_rows = 0;
     int last_occ_form = 0;         // the forms of the last ssde_path_occupancy: bit 0 the LDS-tile form, bit 1 the global form (ssde_last_occupancy_form)
     int64_t last_occ_points = 0, last_occ_capped = 0;   // of the last ssde_path_occupancy_fine (ssde_last_occupancy_points)
-    ssde_engine::HessPlanInfo hess_plan;                             // of the last ssde_hess (ssde_last_hess_plan; ssde_windows.hpp)
+    int64_t last_prox_tiles = 0, last_prox_tiles_max = 0;   // of the last ssde_path_proximity (ssde_last_proximity_plan) ...
+    int last_prox_batches = 0, last_prox_route = 0;     // ... its batches of draws, and 1: positions stayed on the device, 2: gathered from shards
+    ssde_engine::HessPlanInfo hess_plan;                            // of the last ssde_hess (ssde_last_hess_plan; ssde_windows.hpp)
     int last_gain_feed = 0;        // how the last evaluation's launch got its gain table: 0 the ring and a copy, 1 by value (ssde_last_gain_feed)
     std::vector<double> gain_scratch;        // a deferred table's rows (build_gain_table / feed_gain_table)
     bool par_ev_pending[PAR_RING] = {false, false, false, false, false, false, false, false};   // slot last used by an asynchronous call

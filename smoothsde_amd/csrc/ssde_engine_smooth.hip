@@ -2,7 +2,8 @@
 // ssde_smooth_draws: joint posterior draws of the state path from the same records, and ssde_predict: the smoothed
 // state between and after the rows from them, and ssde_path_stats / ssde_path_occupancy: reductions of the drawn paths
 // on the device, and ssde_predict_draws: the drawn paths refined between and after the rows,
-// and ssde_path_occupancy_fine: the occupancy grids of the refined paths.
+// and ssde_path_occupancy_fine: the occupancy grids of the refined paths, and ssde_path_proximity: those states of
+// two tracks paired and reduced per pair and draw.
 //
 // A forward pass in record mode (dense_kernel MODE 2 on the tiled routes, smooth_tv_record_kernel on PATH_TV) writes every state
 // row's record, smooth_back_kernel walks them back and writes the smoothed mean, covariance and whitened innovation in the long
@@ -12,12 +13,14 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <tuple>
 
 #include "ssde_engine.hpp"
 #include "ssde_occ.hpp"
 #include "ssde_predict.hpp"
+#include "ssde_prox.hpp"
 #include "ssde_smooth_plan.hpp"
 
 using namespace ssde_engine;
@@ -677,8 +680,14 @@ int predict_sharded(ssde_handle* parent, const double* par, const int64_t* q_row
 // One engine's queries for n_draws draws into host memory [nq x sdim x n_draws].  predict_single's plan and chunks (the record pass
 // with side rows, chunks without a query skipped) under draws_single's batches: per batch and chunk the walk that stores the ends of
 // the wanted intervals, then the query kernel.  track0 / col0 as draws_single's.
+// A call that reduces the states on the device (ssde_path_proximity) passes a consumer: after the chunk loop of a batch `out` holds
+// every query of that batch of draws, and instead of the copy home the consumer gets (out [nq x sdim x nb], the batch's first draw
+// within the call, nb, the most draws a batch of this call holds); out == NULL: no query of the call has a state, every element of all
+// n_draws draws is NaN.  extra_per_draw: the doubles per draw the consumer keeps on this device, accounted for in the batch cap.
+typedef std::function<int(const double* out, int k0, int nb, int nb_cap)> BatchConsumer;
 int predict_draws_single(ssde_handle* h, const double* par, const int64_t* q_row, const double* q_off, int64_t nq, uint64_t seed,
-                         int64_t draw0, int n_draws, double* draws_at, int64_t track0, int col0) {
+                         int64_t draw0, int n_draws, double* draws_at, int64_t track0, int col0,
+                         const BatchConsumer* consume = nullptr, int64_t extra_per_draw = 0) {
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(0));
     const int sd = h->sdim;
@@ -705,7 +714,11 @@ int predict_draws_single(ssde_handle* h, const double* par, const int64_t* q_row
     if (S.most >= ((int64_t)1 << 32)) { h->err = "ssde_predict_draws: an interval with 2^32 or more distinct offsets"; return SSDE_ERR_ARG; }
     const size_t per_draw = (size_t)nq * sd;
     const double nan = std::numeric_limits<double>::quiet_NaN();
-    if (P.order.empty()) { std::fill(draws_at, draws_at + per_draw * n_draws, nan); return SSDE_OK; }
+    if (P.order.empty()) {
+        if (consume) return (*consume)(nullptr, 0, n_draws, n_draws);
+        std::fill(draws_at, draws_at + per_draw * n_draws, nan);
+        return SSDE_OK;
+    }
 
     const int64_t n_slots = (int64_t)P.want_step.size();
     std::vector<int64_t> slot_lane((size_t)n_slots);
@@ -725,7 +738,8 @@ int predict_draws_single(ssde_handle* h, const double* par, const int64_t* q_row
     // draws per batch: what fits beside the records and side rows (the free memory asked for again, as draws_single does)
     int64_t budget = run.budget;
     if (h->smooth_budget_mb <= 0) if (int st = free_budget(h, budget)) return st;
-    const int nb_cap = predict_draws_batch_cap(budget, most, sd, nq, DRAW_CH, n_draws);
+    const int nb_cap = consume ? batch_cap(budget, most * 2 * sd + nq * sd + extra_per_draw, 1, DRAW_CH, n_draws)
+                               : predict_draws_batch_cap(budget, most, sd, nq, DRAW_CH, n_draws);
     HIPCHK(h, out.alloc(per_draw * nb_cap));
     HIPCHK(h, ends.alloc((size_t)most * 2 * sd * nb_cap));
     HIPCHK(h, sidepk.alloc((size_t)most * run.SW));
@@ -747,7 +761,8 @@ int predict_draws_single(ssde_handle* h, const double* par, const int64_t* q_row
             HIPCHK(h, launch_predict_draws_walk(a, 0));
             HIPCHK(h, launch_predict_draws_query(a, 0));
         }
-        HIPCHK(h, hipMemcpy(draws_at + per_draw * k0, out.p, per_draw * nb * 8, hipMemcpyDeviceToHost));
+        if (consume) { if (int st = (*consume)(out.p, k0, nb, nb_cap)) return st; }
+        else HIPCHK(h, hipMemcpy(draws_at + per_draw * k0, out.p, per_draw * nb * 8, hipMemcpyDeviceToHost));
     }
     HIPCHK(h, hipStreamSynchronize(0));
     return SSDE_OK;
@@ -781,6 +796,147 @@ int predict_draws_sharded(ssde_handle* parent, const double* par, const int64_t*
         }
         if ((k + 1) % P == 0) track0 += sh->n_seg;                          // the next track shard's first ordinal
     }
+    return SSDE_OK;
+}
+
+// ---- ssde_path_proximity ------------------------------------------------------------------------------------------------------
+// What both routes share: the call as the host sees it, and the two kernels' tables, partial records and statistics on one device.
+struct ProxCall {
+    int64_t n_point = 0;
+    int n_pairs = 0, n_radii = 0, n_stat = 2, e = 0;
+    const double* radii = nullptr;
+    std::vector<uint64_t> wq;                  // the weights in quanta, quantised once on the host; empty: every point weighs `unit`
+    uint64_t unit = 0;
+    ProxPlan plan;
+    // the doubles (64-bit words) per draw that the two kernels keep
+    int64_t per_draw() const { return plan.n_tiles * PROX_REC + (int64_t)n_pairs * n_stat; }
+};
+
+struct ProxDev {
+    DevBuf<int64_t> tf, ti, pt;
+    DevBuf<int32_t> tc;
+    DevBuf<uint64_t> wq, part;
+    DevBuf<double> sb;
+    ProxArgs a;
+    bool ready = false;
+    ~ProxDev() { tf.release(); ti.release(); pt.release(); tc.release(); wq.release(); part.release(); sb.release(); }
+    // on the CURRENT device: the tables, and room for nb_cap draws
+    int prepare(ssde_handle* h, const ProxCall& c, int nb_cap) {
+        if (ready) return SSDE_OK;
+        HIPCHK(h, tf.upload(c.plan.tile_first)); HIPCHK(h, ti.upload(c.plan.tile_idx0)); HIPCHK(h, tc.upload(c.plan.tile_count));
+        HIPCHK(h, pt.upload(c.plan.pair_tile)); HIPCHK(h, wq.upload(c.wq));
+        HIPCHK(h, part.alloc((size_t)c.plan.n_tiles * PROX_REC * nb_cap));
+        HIPCHK(h, sb.alloc((size_t)c.n_pairs * c.n_stat * nb_cap));
+        memset(&a, 0, sizeof(a));
+        a.model = h->model; a.d = h->d;
+        a.n_point = c.n_point; a.n_query = 2 * c.n_point;
+        a.tile_first = tf.p; a.tile_idx0 = ti.p; a.tile_count = tc.p; a.pair_tile = pt.p;
+        a.n_tiles = c.plan.n_tiles; a.n_pairs = c.n_pairs;
+        a.wq = c.wq.empty() ? nullptr : wq.p; a.unit = c.unit;
+        a.part = part.p; a.stats = sb.p; a.n_radii = c.n_radii; a.e = c.e;
+        for (int r = 0; r < c.n_radii; r++) a.radii[r] = c.radii[r];
+        ready = true;
+        return SSDE_OK;
+    }
+    // nb draws of positions in `pos` (n_col columns per draw; packed: the position columns alone) -> stats_host [n_pairs x n_stat x nb]
+    int reduce(ssde_handle* h, const ProxCall& c, const double* pos, int n_col, bool packed, int nb, double* stats_host) {
+        a.pos = pos; a.draw_stride = a.n_query * n_col; a.packed = packed ? 1 : 0; a.n_draws = nb;
+        HIPCHK(h, launch_prox_tile(a, 0));
+        HIPCHK(h, launch_prox_fold(a, 0));
+        HIPCHK(h, hipMemcpy(stats_host, sb.p, (size_t)c.n_pairs * c.n_stat * nb * 8, hipMemcpyDeviceToHost));
+        return SSDE_OK;
+    }
+};
+
+// route 1: one engine; the positions of a batch never leave its device
+int prox_single(ssde_handle* h, const double* par, const int64_t* q_row, const double* q_off, const ProxCall& c, uint64_t seed,
+                int64_t draw0, int n_draws, double* stats, int& n_batches) {
+    ProxDev dev;
+    const size_t per = (size_t)c.n_pairs * c.n_stat;
+    const BatchConsumer consume = [&](const double* out, int k0, int nb, int nb_cap) -> int {
+        if (!out) { std::fill(stats, stats + per * n_draws, std::numeric_limits<double>::quiet_NaN()); n_batches = 1; return SSDE_OK; }
+        if (int st = dev.prepare(h, c, nb_cap)) return st;
+        n_batches++;
+        return dev.reduce(h, c, out, h->sdim, false, nb, stats + per * k0);
+    };
+    return predict_draws_single(h, par, q_row, q_off, 2 * c.n_point, seed, draw0, n_draws, nullptr, 0, 0, &consume, c.per_draw());
+}
+
+// route 2: a multi-device parent.  Per batch of draws every track shard answers the queries on its rows (predict_draws_sharded's
+// deal: the GLOBAL track ordinal in the deviates) and its position columns are gathered, on the first shard's device, into one buffer
+// [2 n_point x d x nb] at the parent's query indices; the same two kernels run there.  The positions are the single engine's bit for
+// bit and the reduction does not depend on where it runs, so the result is bitwise route 1's.
+int prox_sharded(ssde_handle* parent, const double* par, const int64_t* q_row, const double* q_off, const ProxCall& c, uint64_t seed,
+                 int64_t draw0, int n_draws, double* stats, int& n_batches) {
+    const int64_t nq = 2 * c.n_point;
+    const int D = parent->d, col_step = parent->model == SSDE_MODEL_CTCRW ? 2 : 1;
+    ssde_handle* first = parent->shards[0];
+    const int dev0 = first->device;
+    const size_t per = (size_t)c.n_pairs * c.n_stat;
+    // the deal, once: the queries on every shard's rows
+    const size_t ns = parent->shards.size();
+    std::vector<std::vector<int64_t>> idx(ns), rows(ns);
+    std::vector<std::vector<double>> offs(ns);
+    for (size_t k = 0; k < ns; k++) {
+        if (parent->shards[k]->sdim != parent->sdim) { parent->err = "ssde_path_proximity: column pairs are not served"; return SSDE_ERR_MODEL; }
+        const int64_t lo = parent->shard_row0[k], m = parent->shard_nrows[k];
+        for (int64_t i = 0; i < nq; i++)
+            if (q_row[i] >= lo && q_row[i] < lo + m) { idx[k].push_back(i); rows[k].push_back(q_row[i] - lo); offs[k].push_back(q_off[i]); }
+    }
+    HIPCHK(parent, hipSetDevice(dev0));
+    HIPCHK(parent, hipStreamSynchronize(0));
+    int64_t budget = 0;
+    if (parent->smooth_budget_mb > 0) budget = parent->smooth_budget_mb * (int64_t)(1 << 20) / 8;
+    else if (int st = free_budget(parent, budget)) return st;
+    const int nbp = batch_cap(budget, nq * D + c.per_draw(), 1, DRAW_CH, n_draws);
+    ProxDev dev;
+    DevBuf<double> pos, stage;
+    std::vector<DevBuf<int64_t>> idxd(ns);
+    struct Free {
+        DevBuf<double>&a, &b; std::vector<DevBuf<int64_t>>& v;
+        ~Free() { a.release(); b.release(); for (auto& x : v) x.release(); }
+    } guard{pos, stage, idxd};
+    HIPCHK(parent, pos.alloc((size_t)nq * D * nbp));
+    if (int st = dev.prepare(first, c, nbp)) { parent->err = first->err; return st; }
+    for (size_t k = 0; k < ns; k++) HIPCHK(parent, idxd[k].upload(idx[k]));
+    for (int k0 = 0; k0 < n_draws; k0 += nbp) {
+        const int nb = std::min(nbp, n_draws - k0);
+        HIPCHK(parent, hipSetDevice(dev0));
+        HIPCHK(parent, hipMemset(pos.p, 0xff, (size_t)nq * D * nb * 8));     // NaN (all bits set) where no shard answers
+        HIPCHK(parent, hipStreamSynchronize(0));
+        int64_t track0 = 0;
+        for (size_t k = 0; k < ns; k++) {
+            ssde_handle* sh = parent->shards[k];
+            const int64_t mq = (int64_t)idx[k].size();
+            const int sd = sh->sdim;
+            if (mq > 0) {
+                const BatchConsumer consume = [&](const double* out, int j0, int mb, int) -> int {
+                    if (!out) return SSDE_OK;
+                    const double* src = out;
+                    HIPCHK(sh, hipStreamSynchronize(0));                     // the shard's batch is complete
+                    if (sh->device != dev0) {
+                        HIPCHK(sh, hipSetDevice(dev0));
+                        if (stage.n < (size_t)mq * sd * mb) { stage.release(); HIPCHK(sh, stage.alloc((size_t)mq * sd * mb)); }
+                        HIPCHK(sh, hipMemcpyPeer(stage.p, dev0, out, sh->device, (size_t)mq * sd * mb * 8));
+                        src = stage.p;
+                    }
+                    HIPCHK(sh, launch_prox_gather(src, mq, sd, col_step, D, mb, idxd[k].p, pos.p + (size_t)nq * D * j0, nq, 0));
+                    HIPCHK(sh, hipStreamSynchronize(0));
+                    if (sh->device != dev0) HIPCHK(sh, hipSetDevice(sh->device));
+                    return SSDE_OK;
+                };
+                int st = check_kalman(sh);
+                if (!st) st = predict_draws_single(sh, par, rows[k].data(), offs[k].data(), mq, seed, draw0 + k0, nb, nullptr, track0, 0,
+                                                   &consume, 0);
+                if (st) { parent->err = sh->err; return st; }
+            }
+            track0 += sh->n_seg;
+        }
+        HIPCHK(parent, hipSetDevice(dev0));
+        if (int st = dev.reduce(first, c, pos.p, D, true, nb, stats + per * k0)) { parent->err = first->err; return st; }
+        n_batches++;
+    }
+    HIPCHK(parent, hipStreamSynchronize(0));
     return SSDE_OK;
 }
 
@@ -1038,6 +1194,99 @@ int ssde_predict_draws(ssde_handle* h, const double* par, int32_t n_par_full, co
     if (!h->shards.empty()) return predict_draws_sharded(h, par, q_row, q_off, n_query, seed, draw0, n_draws, draws_at);
     if (int st = check_not_coupled_wide(h, "ssde_predict_draws")) return st;        // (every check before the device is touched)
     return predict_draws_single(h, par, q_row, q_off, n_query, seed, draw0, n_draws, draws_at, 0, 0);
+}
+
+int ssde_path_proximity(ssde_handle* h, const double* par, int32_t n_par_full, uint64_t seed, int64_t draw0, int32_t n_draws,
+                        const int64_t* qa_row, const double* qa_off, const int64_t* qb_row, const double* qb_off,
+                        const int64_t* pair_ptr, int32_t n_pairs, const double* weight, const double* radii, int32_t n_radii,
+                        double* stats, uint32_t flags) {
+    if (!h || !par || !qa_row || !qa_off || !qb_row || !qb_off || !pair_ptr || !stats) {
+        if (h) h->err = "ssde_path_proximity: no parameter vector, no queries, no pair list, or no output";
+        return SSDE_ERR_ARG;
+    }
+    if (int st = check_par_len(h, n_par_full)) return st;
+    if (n_pairs < 1) { h->err = "ssde_path_proximity: n_pairs >= 1 is required"; return SSDE_ERR_ARG; }
+    bool csr = pair_ptr[0] == 0;
+    for (int32_t p = 0; csr && p < n_pairs; p++) csr = pair_ptr[p + 1] >= pair_ptr[p];
+    if (!csr || pair_ptr[n_pairs] < 1) {
+        h->err = "ssde_path_proximity: pair_ptr must start at 0, not decrease, and end at n_point >= 1";
+        return SSDE_ERR_ARG;
+    }
+    const int64_t np = pair_ptr[n_pairs];
+    for (int side = 0; side < 2; side++) {
+        const int64_t* qr = side ? qb_row : qa_row;
+        const double* qo = side ? qb_off : qa_off;
+        for (int64_t k = 0; k < np; k++) {
+            if (qr[k] < 0 || qr[k] >= h->n) { h->err = "ssde_path_proximity: a query row outside [0, n)"; return SSDE_ERR_ARG; }
+            if (!std::isfinite(qo[k]) || qo[k] < 0.0) { h->err = "ssde_path_proximity: a query offset that is negative or not finite"; return SSDE_ERR_ARG; }
+        }
+    }
+    if (n_draws < 1 || draw0 < 0 || draw0 + (int64_t)n_draws >= ((int64_t)1 << 28)) {
+        h->err = "ssde_path_proximity: n_draws >= 1, draw0 >= 0 and draw0 + n_draws < 2^28 are required";
+        return SSDE_ERR_ARG;
+    }
+    if (n_radii < 0 || n_radii > SSDE_PROX_MAX_RADII || (n_radii > 0 && !radii)) {
+        h->err = "ssde_path_proximity: 0 <= n_radii <= SSDE_PROX_MAX_RADII, with a table of radii when there are any";
+        return SSDE_ERR_ARG;
+    }
+    for (int r = 0; r < n_radii; r++)
+        if (!(radii[r] >= 0.0)) { h->err = "ssde_path_proximity: a radius that is NaN or negative"; return SSDE_ERR_ARG; }
+    double wmax = weight ? 0.0 : 1.0;
+    for (int64_t i = 0; weight && i < np; i++) {
+        if (!(weight[i] >= 0.0 && weight[i] <= std::numeric_limits<double>::max())) {          // negative, NaN or inf
+            h->err = "ssde_path_proximity: a weight that is negative or not finite";
+            return SSDE_ERR_ARG;
+        }
+        wmax = std::max(wmax, weight[i]);
+    }
+    if (flags != 0) { h->err = "ssde_path_proximity: unknown flag"; return SSDE_ERR_ARG; }
+    // the limits of ssde_predict_draws: the bridge deviates' counter holds the track ordinal's low word and the rank of an offset
+    if (h->n_seg >= ((int64_t)1 << 32)) { h->err = "ssde_path_proximity: 2^32 or more tracks"; return SSDE_ERR_ARG; }
+    std::vector<int64_t> q_row((size_t)2 * np);
+    std::vector<double> q_off((size_t)2 * np);
+    std::copy(qa_row, qa_row + np, q_row.begin()); std::copy(qb_row, qb_row + np, q_row.begin() + np);
+    std::copy(qa_off, qa_off + np, q_off.begin()); std::copy(qb_off, qb_off + np, q_off.begin() + np);
+    if (2 * np >= ((int64_t)1 << 32)) {
+        std::vector<int64_t> by((size_t)2 * np);
+        for (int64_t k = 0; k < 2 * np; k++) by[(size_t)k] = k;
+        std::sort(by.begin(), by.end(), [&](int64_t a, int64_t b) { return q_row[a] != q_row[b] ? q_row[a] < q_row[b] : q_off[a] < q_off[b]; });
+        int64_t run_len = 0;
+        for (int64_t k = 0; k < 2 * np; k++) {
+            if (k == 0 || q_row[by[k]] != q_row[by[k - 1]]) run_len = 1;
+            else if (q_off[by[k]] != q_off[by[k - 1]]) run_len++;
+            if (run_len + 1 >= ((int64_t)1 << 32)) { h->err = "ssde_path_proximity: an interval with 2^32 or more distinct offsets"; return SSDE_ERR_ARG; }
+        }
+    }
+    if (int st = check_kalman(h)) return st;
+    if (h->d > 2) {
+        h->err = "ssde_path_proximity: a response of three or more columns is not served, as column pairs or as one coupled filter (a distance needs the position columns in one lane)";
+        return SSDE_ERR_MODEL;
+    }
+    // (every check before the device is touched)
+    ProxCall c;
+    c.n_point = np; c.n_pairs = n_pairs; c.n_radii = n_radii; c.n_stat = 2 + n_radii; c.radii = radii;
+    c.e = occ_quantum_exp(wmax, np, 1);                              // no n_draws in the quantum: draw ranges cut over calls agree bitwise
+    c.unit = occ_quantise(1.0, c.e);
+    if (weight) { c.wq.resize((size_t)np); occ_quantise_all(weight, np, c.e, c.wq.data()); }
+    c.plan = plan_prox_tiles(pair_ptr, n_pairs);
+    int n_batches = 0;
+    h->last_prox_tiles = 0; h->last_prox_tiles_max = 0; h->last_prox_batches = 0; h->last_prox_route = 0;
+    const bool sharded = !h->shards.empty();
+    const int st = sharded ? prox_sharded(h, par, q_row.data(), q_off.data(), c, seed, draw0, n_draws, stats, n_batches)
+                           : prox_single(h, par, q_row.data(), q_off.data(), c, seed, draw0, n_draws, stats, n_batches);
+    if (st) return st;
+    h->last_prox_tiles = c.plan.n_tiles; h->last_prox_tiles_max = c.plan.tiles_max;
+    h->last_prox_batches = n_batches; h->last_prox_route = sharded ? 2 : 1;
+    return SSDE_OK;
+}
+
+int ssde_last_proximity_plan(const ssde_handle* h, int64_t* n_tiles, int64_t* tiles_max, int32_t* n_batches, int32_t* route) {
+    if (!h) return SSDE_ERR_ARG;
+    if (n_tiles) *n_tiles = h->last_prox_tiles;
+    if (tiles_max) *tiles_max = h->last_prox_tiles_max;
+    if (n_batches) *n_batches = h->last_prox_batches;
+    if (route) *route = h->last_prox_route;
+    return SSDE_OK;
 }
 
 int ssde_smooth(ssde_handle* h, const double* par, int32_t n_par_full, double* a_smooth, double* P_smooth, double* resid) {

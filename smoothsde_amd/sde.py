@@ -583,6 +583,77 @@ class SDE:
         weight[:-1][same] = (t[1:] - t[:-1])[same]
         return weight
 
+    def _proximity_points(self, pairs, times):
+        """per pair of (ID_a, ID_b): the clock times compared (an empty array for an unknown ID or an empty window)"""
+        ids = np.asarray(self.data_["ID"])
+        t = np.asarray(self.data_["time"], dtype=np.float64)
+        start = np.r_[0, np.nonzero(ids[1:] != ids[:-1])[0] + 1]
+        end = np.r_[start[1:], len(ids)]
+        seg_of = {}
+        for k, s0 in enumerate(start):
+            seg_of.setdefault(ids[s0], k)
+        given = None if times is None else np.sort(np.asarray(times, dtype=np.float64).ravel())
+        out = []
+        for a, b in pairs:
+            sa, sb = seg_of.get(a), seg_of.get(b)
+            if sa is None or sb is None or min(end[sa] - start[sa], end[sb] - start[sb]) < 2:
+                out.append(np.zeros(0))
+                continue
+            ta, tb = t[start[sa]:end[sa]], t[start[sb]:end[sb]]
+            lo = max(ta[1], tb[1])                                    # the later of the two second stamps: both have a state
+            if given is None:
+                hi = min(ta[-1], tb[-1])                              # the earlier of the two last stamps: both have data
+                u = np.union1d(ta, tb)
+                out.append(u[(u >= lo) & (u <= hi)])
+            else:
+                out.append(given[np.isfinite(given) & (given >= lo)])  # later times are kept: forecasts
+        return out
+
+    def proximity(self, pairs, radii, n_draws, seed=0, times=None, weight="dt"):
+        """How close the posterior paths of pairs of tracks come, of a state-space model (CTCRW, OU_SSM, BM_SSM) at the current
+        parameters, reduced on the device (ssde_path_proximity): no draw comes home.  `pairs`: a sequence of
+        (ID_a, ID_b); `radii`: up to eight distances.  `times=None` compares every pair at the sorted union of both tracks' time stamps
+        inside the window where both have a state and data (from the later of the two second stamps to the earlier of the two last
+        stamps); an array compares every pair at those clock times, without the ones before either track's second stamp (later
+        times are kept: forecasts).  `weight`: "dt" weighs a point by the time to the pair's next point (0 at the last), so
+        "time_within" is time; None counts points.  Draw k of either track is the path sample_states(n_draws, seed) returns as draw k
+        (tracks are independent given the parameters, so the two form a joint draw).  Returns {"min_dist": (n_draws, n_pairs),
+        "t_min": (n_draws, n_pairs) the clock time of the closest approach, "time_within": (n_draws, n_pairs, n_radii), "p_within":
+        (n_pairs, n_radii) the share of the finite draws whose minimum distance is <= the radius, "times": the list of the pairs'
+        clock times}.  A pair with an unknown ID or an empty window is NaN and does not fail the call.  The arguments the engine's
+        path_proximity got (qa_rows, qa_offs, qb_rows, qb_offs, pair_ptr, weight) stay in `proximity_queries_`."""
+        if self.type_ not in ("CTCRW", "OU_SSM", "BM_SSM"):
+            raise NotImplementedError(f"proximity: no latent state in the model {self.type_!r}")
+        if self.engine_ is None:
+            raise RuntimeError("call setup() or fit() first")
+        if weight is not None and not (isinstance(weight, str) and weight == "dt"):
+            raise ValueError('weight must be "dt" or None')
+        pairs = [tuple(p) for p in pairs]
+        rad = np.asarray(radii, dtype=np.float64).ravel()
+        n_draws, n_pairs = int(n_draws), len(pairs)
+        tlist = self._proximity_points(pairs, times)
+        pair_ptr = np.r_[0, np.cumsum([len(u) for u in tlist])].astype(np.int64)
+        st = np.full((n_draws, n_pairs, 2 + len(rad)), np.nan)
+        if pair_ptr[-1] > 0 and n_pairs > 0:
+            clock = np.concatenate(tlist)
+            ida = np.concatenate([np.full(len(u), p[0], dtype=object) for p, u in zip(pairs, tlist)])
+            idb = np.concatenate([np.full(len(u), p[1], dtype=object) for p, u in zip(pairs, tlist)])
+            ra, oa = self._rows_and_offsets(ida, clock)
+            rb, ob = self._rows_and_offsets(idb, clock)
+            w = None
+            if weight is not None:
+                w = np.concatenate([np.r_[np.diff(u), 0.0] if len(u) else u for u in tlist])
+            self.proximity_queries_ = (ra, oa, rb, ob, pair_ptr, w)
+            st = self.engine_.path_proximity(self._current_par_full(), ra, oa, rb, ob, pair_ptr, n_draws, seed=seed, radii=rad, weight=w)
+        t_min = np.full((n_draws, n_pairs), np.nan)
+        for p, u in enumerate(tlist):
+            ok = np.isfinite(st[:, p, 1])
+            t_min[ok, p] = u[st[ok, p, 1].astype(np.int64)] if len(u) else np.nan
+        finite = np.isfinite(st[:, :, 0])
+        with np.errstate(invalid="ignore", divide="ignore"):
+            p_within = (finite[:, :, None] & (st[:, :, :1] <= rad[None, None, :])).sum(axis=0) / finite.sum(axis=0)[:, None]
+        return {"min_dist": st[:, :, 0], "t_min": t_min, "time_within": st[:, :, 2:], "p_within": p_within, "times": tlist}
+
     def utilisation(self, n_draws, seed=0, cells=(64, 64), extent=None, by=None, weight="dt", max_step=None):
         """The utilisation distribution of a state-space model (CTCRW, OU_SSM, BM_SSM) at the current parameters: the share of the
         weighted time that the posterior state paths spend in every cell of a regular grid, summed on the device
