@@ -640,8 +640,14 @@ int ssde_comm_init_rank(ssde_handle *h, int32_t n_ranks, int32_t rank, const voi
  *       side by side packs their result vectors and issues one collective for all of them instead of one per handle on
  *       as many streams.  ssde_eval ignores it.
  *   SSDE_OPT_SMOOTH_BUDGET_MB (default 0 = a quarter of the device memory free when ssde_smooth is called): the largest record
- *       buffer ssde_smooth allocates, in MiB (one wavefront group always goes, whatever the cap). */
-enum { SSDE_OPT_KERNEL_STAMPS = 1, SSDE_OPT_COMM_DEFER = 2, SSDE_OPT_SMOOTH_BUDGET_MB = 3 };
+ *       buffer ssde_smooth allocates, in MiB (one wavefront group always goes, whatever the cap).
+ *   SSDE_OPT_LAG_EARLY: 1 = an evaluation on the lag-statistics path (CTCRW) may cut the bulk at the end of its covariance transient
+ *       instead of at row 256: the streamed head is then one window per track, and the rows past the cut come from
+ *       statistics built for that cut (every multiple of 16 from 32 to 128).  Setting it builds those statistics, synchronously, on a
+ *       handle that holds the late ones and not yet these; a handle without lag statistics ignores it.  0 = the cut at row 256 only.
+ *       Default: 1 exactly when ssde_create built the early cuts -- where its dispatch rule itself built the lag statistics and the response
+ *       has two coordinates --, else 0 (with one coordinate the head of the late cut is the faster launch: DESIGN.md §3.3d). */
+enum { SSDE_OPT_KERNEL_STAMPS = 1, SSDE_OPT_COMM_DEFER = 2, SSDE_OPT_SMOOTH_BUDGET_MB = 3, SSDE_OPT_LAG_EARLY = 4 };
 int ssde_set_option(ssde_handle *h, int32_t option, int64_t value);
 
 /* Sum buf_dev[0 .. count) (doubles, HBM) over the ranks of the communicator `h` joined, in place, on `stream` (enqueue only:
@@ -749,6 +755,18 @@ int ssde_last_finish_form(const ssde_handle *h);
    to fit).  ssde_last_gain_rows: the rows of that table.  A multi-device parent reports its first shard; -1 for NULL. */
 int ssde_last_gain_feed(const ssde_handle *h);
 int ssde_last_gain_rows(const ssde_handle *h);
+/* The lag statistics with the first bulk row `cut`: 256 -- ssde_lagstats_host / ssde_lagstats_read --, or an early cut,
+   a multiple of 16 from 32 to 128 (CTCRW: the increments): M_ik = sum_{t = cut}^{n - 1} Dy_{t-i} Dy_{t-k} and s_{a,i} for the lags
+   i, k < cut (the other entries are zero), n_bulk = the rows past the cut; a track of n <= cut rows contributes nothing.  The sizes
+   are those of ssde_lagstats_host.  ssde_lagstats_host_cut: the host reference, track by track.  ssde_lagstats_read_cut: what the
+   handle built on the device (at create, or at ssde_set_option(SSDE_OPT_LAG_EARLY, 1)).  SSDE_ERR_ARG: a NULL pointer, d outside
+   1..2, a cut outside the list, a handle that holds no statistics for it (also a multi-device parent, as for ssde_lagstats_read: ask its
+   shards). */
+int ssde_lagstats_host_cut(const double *y, const int64_t *rows, int64_t n_tracks, int d, int32_t cut, double *M, double *s, double *n_bulk);
+int ssde_lagstats_read_cut(const ssde_handle *h, int32_t cut, double *M, double *s, double *n_bulk);
+/* The first bulk row of the handle's last evaluation: 256 or an early cut where rows came from the lag statistics, 0 where every row
+   was streamed.  A multi-device parent reports its first shard; -1 for NULL. */
+int ssde_last_lag_cut(const ssde_handle *h);
 
 #ifdef __cplusplus
 }

@@ -77,7 +77,8 @@ class SsdeSimDesc(C.Structure):
                 ("reserved", C.c_int32)]
 
 
-OPT_KERNEL_STAMPS, OPT_COMM_DEFER, OPT_SMOOTH_BUDGET_MB = 1, 2, 3
+OPT_KERNEL_STAMPS, OPT_COMM_DEFER, OPT_SMOOTH_BUDGET_MB, OPT_LAG_EARLY = 1, 2, 3, 4
+LAG_CUTS = tuple(range(32, 129, 16))   # the early cuts of the lag statistics (csrc/ssde_lagstats.hpp)
 # ssde_info_t.kernel_id (include/ssde.h: SSDE_KERNEL_*): the kernel family that ran the rows of the last evaluation
 KERNEL_NAMES = {0: "none", 1: "direct_kernel", 2: "direct_fast_kernel", 3: "iso_shared_kernel", 4: "iso_mask_kernel",
                 5: "iso_mask_kernel<uniform grid>", 6: "iso_quiet_kernel", 7: "iso_shared_kernel + general kernel (mixed batch)",
@@ -544,6 +545,12 @@ def load_library():
     lib.ssde_lagstats_host_m.restype = C.c_int
     lib.ssde_lagstats_read_m.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp]
     lib.ssde_lagstats_read_m.restype = C.c_int
+    lib.ssde_lagstats_host_cut.argtypes = [_dp, C.POINTER(C.c_int64), C.c_int64, C.c_int, C.c_int32, _dp, _dp, _dp]
+    lib.ssde_lagstats_host_cut.restype = C.c_int
+    lib.ssde_lagstats_read_cut.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _dp]
+    lib.ssde_lagstats_read_cut.restype = C.c_int
+    lib.ssde_last_lag_cut.argtypes = [C.c_void_p]
+    lib.ssde_last_lag_cut.restype = C.c_int
     lib.ssde_lagforms_host_m.argtypes = [C.c_int32, _dp, _dp, C.c_double, _dp, C.c_int32, _dp, C.c_double, _dp, C.c_int32, C.c_int32,
                                          C.c_int32, _dp, _dp, _dp, _dp]
     lib.ssde_lagforms_host_m.restype = C.c_int
@@ -601,7 +608,8 @@ WINDOW_TOL = 1e-11  # largest tolerated relative hand-over disagreement between 
 EXPORTED_SYMBOLS = ("ssde_create", "ssde_eval", "ssde_eval_device", "ssde_penalty", "ssde_report", "ssde_widen_windows", "ssde_relax_windows",
                     "ssde_info", "ssde_destroy", "ssde_last_error", "ssde_abi_version", "ssde_comm_unique_id", "ssde_comm_init_rank", "ssde_forget", "ssde_laplace_eval", "ssde_last_kernel_ms", "ssde_kernel_ms_history",
                     "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth", "ssde_smooth_draws", "ssde_predict", "ssde_predict_draws", "ssde_path_stats", "ssde_path_occupancy", "ssde_last_occupancy_form", "ssde_path_occupancy_fine", "ssde_last_occupancy_points", "ssde_last_hess_plan", "ssde_path_proximity", "ssde_last_proximity_plan",
-                    "ssde_lagstats_host_m", "ssde_lagstats_read_m", "ssde_lagforms_host_m", "ssde_reduce_host", "ssde_last_finish_form", "ssde_last_gain_feed", "ssde_last_gain_rows")
+                    "ssde_lagstats_host_m", "ssde_lagstats_read_m", "ssde_lagforms_host_m", "ssde_reduce_host", "ssde_last_finish_form", "ssde_last_gain_feed", "ssde_last_gain_rows",
+                    "ssde_lagstats_host_cut", "ssde_lagstats_read_cut", "ssde_last_lag_cut")
 
 
 def reduce_host(sums, group_chk, n_out, map_, lag_acc=None, lag_chk=0.0, add=None, add_slot=None):
@@ -652,6 +660,23 @@ def lagstats_host(tracks, model="CTCRW", ref=None):
     if st != 0:
         raise ValueError(f"ssde_lagstats_host: status {st}")
     return M, s, float(n[0]), int(a0.value)
+
+
+def lagstats_host_cut(tracks, cut):
+    """lagstats_host (CTCRW: the increments) with the first bulk row `cut`: 256, or an early cut (LAG_CUTS).  Returns (M, s, n_bulk);
+    the entries with a lag >= cut are zero."""
+    lib = load_library()
+    nt, a0 = C.c_int32(0), C.c_int32(0)
+    lib.ssde_lagstats_host(None, None, 0, 1, None, None, None, C.byref(nt), C.byref(a0))
+    d = int(tracks[0].shape[1])
+    y = np.ascontiguousarray(np.concatenate([np.asarray(t, dtype=np.float64) for t in tracks]))
+    rows = np.array([t.shape[0] for t in tracks], dtype=np.int64)
+    M = np.zeros((nt.value, nt.value)); s = np.zeros((2, nt.value)); n = np.zeros(1)
+    st = lib.ssde_lagstats_host_cut(y.ctypes.data_as(_dp), rows.ctypes.data_as(C.POINTER(C.c_int64)), len(tracks), d, int(cut),
+                                    M.ctypes.data_as(_dp), s.ctypes.data_as(_dp), n.ctypes.data_as(_dp))
+    if st != 0:
+        raise ValueError(f"ssde_lagstats_host_cut: status {st}")
+    return M, s, float(n[0])
 
 
 def lagforms_host(M, s, n_bulk, theta, dt, K, d=None, p0=None, mask=-1, taps=None, model="CTCRW", ref=None):
@@ -790,6 +815,19 @@ class Engine:
         if st != 0:
             return None
         return M, s, float(n[0])
+
+    def lagstats_cut(self, cut):
+        """(M, s, n_bulk) of the lag statistics the handle built for the first bulk row `cut` (ssde_lagstats_read_cut; the host
+        reference is lagstats_host_cut)."""
+        nt, a0 = C.c_int32(0), C.c_int32(0)
+        self.lib.ssde_lagstats_host(None, None, 0, 1, None, None, None, C.byref(nt), C.byref(a0))
+        M = np.zeros((nt.value, nt.value)); s = np.zeros((2, nt.value)); n = np.zeros(1)
+        self._check(self.lib.ssde_lagstats_read_cut(self._h, int(cut), M.ctypes.data_as(_dp), s.ctypes.data_as(_dp), n.ctypes.data_as(_dp)))
+        return M, s, float(n[0])
+
+    def last_lag_cut(self):
+        """The first bulk row of the last evaluation (ssde_last_lag_cut): 256 or an early cut; 0 where every row was streamed."""
+        return int(self.lib.ssde_last_lag_cut(self._h))
 
     def lagstats_ref(self):
         """The value the statistics' levels are centred on (OU_SSM: y - ref, one number per response coordinate, fixed at create;

@@ -9,6 +9,7 @@ namespace ssde {
 hipError_t launch_iso_shared_ctcrw(int d, const IsoArgs& a, const ReduceArgs& r, dim3 grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, bool deep, const HeadGain* hg);
 hipError_t launch_iso_shared_ou(int d, const IsoArgs& a, const ReduceArgs& r, dim3 grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, bool deep, const HeadGain* hg);
 hipError_t launch_iso_shared_bm(int d, const IsoArgs& a, const ReduceArgs& r, dim3 grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, bool deep, const HeadGain* hg);
+hipError_t launch_iso_shared_cut(int d, const IsoArgs& a, dim3 grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, const HeadGain* hg);     // k_iso_shared_cut.hip
 
 // host side: the stationary constants (layout in ssde_device.hpp)
 void fill_stat_consts(int model, int d, IsoArgs& a) {
@@ -60,6 +61,12 @@ hipError_t launch_iso_shared(int model, int d, const IsoArgs& a0, const ReduceAr
     if (grid.x == 0) return hipSuccess;
     // one workgroup per group (iso_shared_wg_kernel): its windows are the waves of a workgroup, the transient window's wave its own;
     // the grid above is then one workgroup per group of the padded batch
+    // window 0 alone, its direction parts on the waves of a workgroup (iso_shared_cut_kernel; wg_form == 2): one workgroup per padded group
+    if (a.wg_form == 2) {
+        if (!(model == M_CTCRW && a.n_chunks == 1 && a.t0 == 0 && !a.fused && a.group_mode != 1)) return hipErrorInvalidValue;
+        if (hg && hg->rows > HEAD_GAIN_ROWS) return hipErrorInvalidValue;
+        return launch_iso_shared_cut(d, a, dim3(g8 * 8), s, ev0, ev1, hg);
+    }
     if (a.wg_form && !(a.n_chunks == WG_WAVES && a.t0 > 0 && a.t0_delta == 0 && !a.fused && a.group_mode != 1)) return hipErrorInvalidValue;
     if (hg && hg->rows > 0 && !(a.wg_form && hg->rows <= HEAD_GAIN_ROWS)) return hipErrorInvalidValue;      // (by value: that entry only)
     if (!a.wg_form) hg = nullptr;

@@ -215,7 +215,7 @@ struct IsoArgs {
     // the group's check.  mbx != NULL: the record goes to the host's mailbox (pinned; MBX_STRIDE doubles per group: the sums
     // [window][accumulator], the check at MBX_CHK, then this evaluation's sequence number at MBX_SEQ) and the host forms the result
     // (ssde_reduce_host.hpp); NULL: sums to `partials`, the group's check to chk[g], and a finalize launch without check workgroups follows.
-    int wg_form;
+    int wg_form;                 // 1: iso_shared_wg_kernel; 2: iso_shared_cut_kernel (window 0 alone, its direction parts on the waves)
     double* mbx;
     unsigned long long mbx_seq;
     // ... the same models with the gradient by a reverse sweep (k_iso_adj.hip): the state entering every CB-th row of a window
@@ -281,6 +281,26 @@ __host__ __device__ constexpr inline int shared_nstate(int sd, int mask, bool ha
     return (1 + ((mask & DIR_SIG) ? 1 : 0) + ((mask & DIR_P1) ? 1 : 0) + (((mask & DIR_P2) && has_p2) ? 1 : 0) +
             ((mask & DIR_MU) ? 1 : 0)) * sd;
 }
+// The direction parts of window 0 (k_iso_shared_cut.hip): one covariance direction each in the order sigma_obs, par d, par d + 1, mu with
+// the lightest of them (par d + 1, else sigma_obs, else par d -- log tau's carries the extra terms of d T, d B), everything on one part
+// where no covariance direction is wanted.  cut_part_mask: part p's DIR_* bits; cut_part_of: the part that owns a direction.
+__host__ __device__ constexpr inline int cut_n_parts(int mask) {
+    const int n = ((mask & DIR_SIG) ? 1 : 0) + ((mask & DIR_P1) ? 1 : 0) + ((mask & DIR_P2) ? 1 : 0);
+    return n > 0 ? n : 1;
+}
+__host__ __device__ constexpr inline int cut_part_mask(int mask, int p) {
+    const int light = (mask & DIR_P2) ? DIR_P2 : (mask & DIR_SIG) ? DIR_SIG : (mask & DIR_P1) ? DIR_P1 : 0;
+    int k = 0, m = 0;
+    for (int j = 0; j < NDIRP; j++)
+        if (mask & dir_bit(j)) { if (k == p) m = dir_bit(j); k++; }
+    if ((mask & DIR_MU) && p < cut_n_parts(mask) && m == light) m |= DIR_MU;
+    return m;
+}
+__host__ __device__ constexpr inline int cut_part_of(int mask, int bit) {
+    for (int p = 0; p < NDIRP; p++)
+        if (cut_part_mask(mask, p) & bit) return p;
+    return 0;
+}
 hipError_t launch_iso(int model, int d, const IsoArgs& a, bool any_dirty, hipStream_t s);
 // blocks of iso_block_rows() rows in which some lane of a group misses an observation: bits [n_groups][nwords] (k_iso.hip)
 int iso_block_rows(int model);
@@ -317,6 +337,8 @@ hipError_t launch_iso_finalize(int model, int d, const IsoArgs& a, const ReduceA
 // and s0g [G][2] / s0 [2] the sums of the bulk's levels
 hipError_t launch_lagstats(const TileView& tv, int d, double* Qg, double* Dg, double* sg, double* Q, double* D, double* s, hipStream_t st,
                            const double* levels_ref = nullptr, double* s0g = nullptr, double* s0 = nullptr);
+// ... and of the head rows' own contribution to an early cut (CTCRW; the same buffers, the entries below the cut)
+hipError_t launch_lagstats_cut(const TileView& tv, int d, int cut, double* Qg, double* Dg, double* sg, double* Q, double* D, double* s, hipStream_t st);
 void fill_stat_consts(int model, int d, IsoArgs& a);
 int iso_nstate(int model, int d);
 

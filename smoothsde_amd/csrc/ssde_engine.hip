@@ -73,6 +73,8 @@ void release_device(ssde_handle* h) {
     destroy_dist(h);
     h->bnd.release(); h->chk.release(); h->group_flags.release(); h->gain_ring.release(); h->pad_pos.release(); h->pad_row.release(); h->dirty_groups.release(); h->lap_out.release(); h->nan_bits.release(); h->quiet_flag.release();
     h->lag_M.release(); h->lag_s.release(); h->lag_glen.release(); h->lag_ns.release();
+    for (int c = 0; c < LAG_NCUT; c++) { h->lag_cut_M[c].release(); h->lag_cut_s[c].release(); h->lag_cut_glen[c].release(); h->lag_cut_ns[c].release(); }
+    h->lag_cut_mask = 0; h->lag_early = false;
     if (h->gain_pinned) (void)hipHostFree(h->gain_pinned);
     for (int i = 0; i < 2; i++) { if (h->aux[i]) (void)hipStreamDestroy(h->aux[i]); if (h->ev_join[i]) (void)hipEventDestroy(h->ev_join[i]); }
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
@@ -322,6 +324,39 @@ int ssde_lagstats_read(const ssde_handle* h, double* M, double* s, double* n_bul
     if (hipMemcpy(s, h->lag_s.p, h->lag_s.n * 8, hipMemcpyDeviceToHost) != hipSuccess) return SSDE_ERR_HIP;
     *n_bulk = h->lag_n;
     return SSDE_OK;
+}
+
+int ssde_lagstats_host_cut(const double* y, const int64_t* rows, int64_t n_tracks, int d, int32_t cut, double* M, double* s, double* n_bulk) {
+    if (cut == LAG_A) return ssde_lagstats_host(y, rows, n_tracks, d, M, s, n_bulk, nullptr, nullptr);
+    if (!y || d < 1 || d > 2 || !rows || !M || !s || !n_bulk || lag_cut_index(cut) < 0) return SSDE_ERR_ARG;
+    std::vector<double> Q(LAG_N, 0.0), D((size_t)LAG_N * LAG_N, 0.0);
+    for (int i = 0; i < 2 * LAG_N; i++) s[i] = 0.0;
+    double n = 0.0;
+    int64_t off = 0;
+    for (int64_t k = 0; k < n_tracks; k++) {
+        n += (double)lag_track_stats_cut(y + off * d, (int)rows[k], d, cut, INT32_MAX, Q.data(), D.data(), s);
+        off += rows[k];
+    }
+    lag_assemble_cut(Q.data(), D.data(), cut, M);
+    *n_bulk = n;
+    return SSDE_OK;
+}
+
+int ssde_lagstats_read_cut(const ssde_handle* h, int32_t cut, double* M, double* s, double* n_bulk) {
+    if (cut == LAG_A) return ssde_lagstats_read(h, M, s, n_bulk);
+    const int c = lag_cut_index(cut);
+    if (!h || !M || !s || !n_bulk || c < 0 || !((h->lag_cut_mask >> c) & 1u)) return SSDE_ERR_ARG;
+    if (hipSetDevice(h->device) != hipSuccess) return SSDE_ERR_HIP;
+    if (hipMemcpy(M, h->lag_cut_M[c].p, h->lag_cut_M[c].n * 8, hipMemcpyDeviceToHost) != hipSuccess) return SSDE_ERR_HIP;
+    if (hipMemcpy(s, h->lag_cut_s[c].p, h->lag_cut_s[c].n * 8, hipMemcpyDeviceToHost) != hipSuccess) return SSDE_ERR_HIP;
+    *n_bulk = h->lag_cut_n[c];
+    return SSDE_OK;
+}
+
+int ssde_last_lag_cut(const ssde_handle* h) {
+    if (!h) return -1;
+    if (!h->shards.empty()) return ssde_last_lag_cut(h->shards[0]);
+    return h->path == PATH_ISO ? h->last_lag_cut : 0;
 }
 
 int ssde_create(const ssde_desc* desc, ssde_handle** out) {
@@ -780,6 +815,24 @@ int ssde_set_option(ssde_handle* h, int32_t option, int64_t value) {
         h->comm_defer = value != 0;
         return SSDE_OK;
     }
+    if (option == SSDE_OPT_LAG_EARLY) {
+        if (value != 0 && value != 1) { h->err = "SSDE_OPT_LAG_EARLY: 0 or 1"; return SSDE_ERR_ARG; }
+        // 1: the statistics of the early cuts are built now where the handle holds the late ones and not yet these (synchronously); an
+        // engine without lag statistics, or of another model than CTCRW, keeps evaluating as it does
+        std::vector<ssde_handle*> engines(h->shards.begin(), h->shards.end());
+        if (engines.empty()) engines.push_back(h);
+        for (ssde_handle* e : engines) {
+            if (value == 1 && e->lag_ready && e->model == SSDE_MODEL_CTCRW) {
+                if (hipSetDevice(e->device) != hipSuccess) { h->err = "SSDE_OPT_LAG_EARLY: hipSetDevice"; return SSDE_ERR_HIP; }
+                const int st = build_lagstats_early(e);
+                if (st != SSDE_OK) { if (e != h) h->err = e->err; return st; }
+            }
+            e->lag_early = value == 1 && e->lag_cut_mask != 0;
+            e->memo_order = -1;
+        }
+        h->memo_order = -1;
+        return SSDE_OK;
+    }
     h->err = "ssde_set_option: unknown option";
     return SSDE_ERR_ARG;
 }
@@ -903,7 +956,8 @@ int ssde_info(const ssde_handle* h, ssde_info_t* info) {
     else if (h->path == PATH_DENSE) info->n_kernel_blocks = h->n_groups * h->n_dirblocks;
     else if (h->path == PATH_TV) info->n_kernel_blocks = (h->tv_n_items_g + WG_WAVES - 1) / WG_WAVES;
     else info->n_kernel_blocks = h->direct_blocks;
-    info->lanes_per_track = h->path == PATH_ISO ? h->iso_parts * h->last_chunks
+    if (h->path == PATH_ISO && h->last_cut_parts > 0) info->n_kernel_blocks = (h->n_groups + 7) / 8 * 8;     // (one workgroup per padded group, its waves the direction parts)
+    info->lanes_per_track = h->path == PATH_ISO ? (h->last_cut_parts > 0 ? h->last_cut_parts : h->iso_parts * h->last_chunks)
                           : h->path == PATH_DENSE ? h->n_dirblocks
                           : h->path == PATH_TV ? h->tv_ndp * h->tv_max_nc : 1;
     info->window = h->last_window;

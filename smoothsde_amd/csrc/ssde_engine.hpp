@@ -321,6 +321,18 @@ struct ssde_handle {
     double lag_ref[2] = {0.0, 0.0};        // OU_SSM: what the statistics' levels are centred on (ssde_lagstats.hpp); 0 otherwise
     int64_t lag_rows = 0, last_lag_rows = 0;   // ... and those the last evaluation took from the statistics (0: streamed)
     double lag_create_ms = 0.0;            // what building them cost at create
+    // ... at the early cuts (CTCRW; ssde_lagstats.hpp: LAG_CUT_MIN .. LAG_CUT_MAX), index c = lag_cut_index(cut): built with the late ones
+    // when the dispatch rule builds those, or at ssde_set_option(SSDE_OPT_LAG_EARLY, 1); lag_cut_mask == 0: none
+    unsigned lag_cut_mask = 0;             // bit c: the statistics of cut c exist
+    bool lag_early = false;                // SSDE_OPT_LAG_EARLY: an evaluation may cut the bulk at its transient's end
+    std::vector<double> lag_cut_M_host[ssde::LAG_NCUT], lag_cut_s_host[ssde::LAG_NCUT];
+    double lag_cut_n[ssde::LAG_NCUT] = {};
+    int64_t lag_cut_rows[ssde::LAG_NCUT] = {};
+    DevBuf<double> lag_cut_M[ssde::LAG_NCUT], lag_cut_s[ssde::LAG_NCUT];          // the device copies (ssde_lagstats_read_cut)
+    DevBuf<int32_t> lag_cut_glen[ssde::LAG_NCUT], lag_cut_ns[ssde::LAG_NCUT];     // group_len / lane_nsteps capped at the cut
+    std::vector<int32_t> lag_host_glen, lag_host_ns;   // the uncapped lengths, kept for a later build of the early cuts
+    int last_lag_cut = 0;                  // first bulk row of the last evaluation (0: streamed)
+    int last_cut_parts = 0;                // > 0: its head ran as this many direction parts per group, one workgroup per padded group (iso_shared_cut_kernel)
     int last_kernel_id = 0;                   // SSDE_KERNEL_*: the family that ran the last evaluation's rows
     // where a stamped synchronous evaluation spent its time (ssde_last_phase_ms): events on the evaluation's stream
     hipEvent_t ev_ph[3] = {nullptr, nullptr, nullptr};   // first operation | end of the finalising launch | end of the all-reduce
@@ -362,6 +374,7 @@ int fail(ssde_handle* h, int code, const std::string& msg);
 // ssde_engine_build.hip
 int build(const ssde_desc* d, ssde_handle* h, const ParLayout* part_layout = nullptr);
 void destroy(ssde_handle* h);
+int build_lagstats_early(ssde_handle* h);     // the lag statistics at the early cuts (create, ssde_set_option(SSDE_OPT_LAG_EARLY, 1))
 void attach_hess_companion(const ssde_desc* desc, ssde_handle* h);     // SSDE_FLAG_EXACT_HESS (ssde_engine.hip)
 void release_device(ssde_handle* h);          // everything the handle holds on the device / in pinned memory (the handle stays)
 int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipStream_t s, ReduceArgs& ra);   // ssde_engine_iso.hip

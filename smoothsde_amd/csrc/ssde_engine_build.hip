@@ -139,6 +139,66 @@ constexpr double LAG_MIN_BULK_ROWS = 4.4e6;
 // OU_SSM and BM_SSM (the scalar-family forms of ssde_lagforms.hpp; OU_SSM from the statistics of the levels y - ref) sit on the same
 // head launch chain, but no crossover has been measured for them yet: their statistics are built only when forced (SSDE_LAGSTATS=2).
 constexpr double LAG_MIN_BULK_ROWS_OU_SSM = INFINITY, LAG_MIN_BULK_ROWS_BM_SSM = INFINITY;
+// SSDE_OPT_LAG_EARLY on a handle whose create built the early cuts (the dispatch rule, CTCRW, d = 2): on
+constexpr bool LAG_EARLY_DEFAULT = true;
+// The statistics at the early cuts (ssde_lagstats.hpp; CTCRW): the late ones plus the head rows' own contribution, one pass per cut over
+// rows [0, LAG_A) of every track, the same fixed-order sums -- two builds give the same bits.  A device that cannot hold the
+// temporaries keeps the late cut (lag_cut_mask stays 0).  Synchronous; called at create and from ssde_set_option.
+int build_lagstats_early(ssde_handle* h) {
+    if (!h->lag_ready || h->model != SSDE_MODEL_CTCRW || h->lag_cut_mask == LAG_CUT_ALL || h->lag_host_ns.empty()) return SSDE_OK;
+    const int G = h->n_groups;
+    TileView tv;
+    tv.tiles = h->tiles.p; tv.group_off = h->group_off.p; tv.group_len = h->group_len.p; tv.lane_nsteps = h->lane_nsteps.p;
+    tv.a0 = h->a0.p; tv.n_groups = G; tv.C = h->C; tv.c_obs = h->c_obs; tv.dt_all = h->dt_all;
+    const size_t NN = (size_t)LAG_N * LAG_N;
+    DevBuf<double> Qg, Dg, sg, sums;
+    auto drop = [&]() { Qg.release(); Dg.release(); sg.release(); sums.release(); };
+    if (Qg.alloc((size_t)G * LAG_N) != hipSuccess || Dg.alloc((size_t)G * NN) != hipSuccess || sg.alloc((size_t)G * 2 * LAG_N) != hipSuccess ||
+        sums.alloc(LAG_N + NN + 2 * LAG_N) != hipSuccess) {
+        (void)hipGetLastError();
+        drop();
+        return SSDE_OK;
+    }
+    std::vector<double> host(sums.n), dM(NN);
+    unsigned mask = 0;
+    for (int c = 0; c < LAG_NCUT; c++) {
+        const int cut = LAG_CUT_MIN + c * LAG_CUT_STEP;
+        if (h->lag_cut_mask & (1u << c)) continue;
+        hipError_t e = launch_lagstats_cut(tv, h->d, cut, Qg.p, Dg.p, sg.p, sums.p, sums.p + LAG_N, sums.p + LAG_N + NN, 0);
+        if (e == hipSuccess) e = hipMemcpy(host.data(), sums.p, host.size() * 8, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { drop(); h->lag_cut_mask |= mask; h->err = std::string("lag statistics, early cuts: ") + hipGetErrorString(e); return SSDE_ERR_HIP; }     // (the cuts built so far stand)
+        lag_assemble_cut(host.data(), host.data() + LAG_N, cut, dM.data());
+        std::vector<double>& M = h->lag_cut_M_host[c];
+        std::vector<double>& sv = h->lag_cut_s_host[c];
+        M.assign(NN, 0.0); sv.assign(2 * LAG_N, 0.0);
+        for (int i = 0; i < cut; i++)
+            for (int k = 0; k < cut; k++) M[(size_t)i * LAG_N + k] = h->lag_M_host[(size_t)i * LAG_N + k] + dM[(size_t)i * LAG_N + k];
+        for (int a = 0; a < 2; a++)
+            for (int i = 0; i < cut; i++) sv[a * LAG_N + i] = h->lag_s_host[a * LAG_N + i] + host[LAG_N + NN + a * LAG_N + i];
+        int64_t rows = h->lag_rows;
+        for (int32_t ns : h->lag_host_ns) rows += std::max(std::min(ns, (int32_t)LAG_A) - cut, 0);
+        h->lag_cut_rows[c] = rows; h->lag_cut_n[c] = (double)rows;
+        std::vector<int32_t> cg(h->lag_host_glen), cn(h->lag_host_ns);
+        for (auto& v : cg) v = std::min(v, (int32_t)cut);
+        for (auto& v : cn) v = std::min(v, (int32_t)cut);
+        e = h->lag_cut_M[c].p ? hipSuccess : h->lag_cut_M[c].upload(M);
+        if (e == hipSuccess && !h->lag_cut_s[c].p) e = h->lag_cut_s[c].upload(sv);
+        if (e == hipSuccess && !h->lag_cut_glen[c].p) e = h->lag_cut_glen[c].upload(cg);
+        if (e == hipSuccess && !h->lag_cut_ns[c].p) e = h->lag_cut_ns[c].upload(cn);
+        if (e != hipSuccess) {                               // (no room for the copies: the cuts built so far stand, the others keep the late cut)
+            (void)hipGetLastError();
+            h->lag_cut_M[c].release(); h->lag_cut_s[c].release(); h->lag_cut_glen[c].release(); h->lag_cut_ns[c].release();
+            break;
+        }
+        h->hbm_bytes += (int64_t)(NN + 2 * LAG_N) * 8;
+        mask |= 1u << c;
+    }
+    drop();
+    HIPCHK(h, hipDeviceSynchronize());
+    h->lag_cut_mask |= mask;
+    return SSDE_OK;
+}
+
 static int build_lagstats(ssde_handle* h, int G, const std::vector<int32_t>& lane_ns, const std::vector<int32_t>& glen) {
     if (h->knobs.lagstats == 0) return SSDE_OK;
     const bool scal = h->model == SSDE_MODEL_OU_SSM || h->model == SSDE_MODEL_BM_SSM;
@@ -202,8 +262,18 @@ static int build_lagstats(ssde_handle* h, int G, const std::vector<int32_t>& lan
     h->lag_rows = bulk;
     h->lag_n = (double)bulk;
     h->lag_ready = true;
-    h->lag_create_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     h->hbm_bytes += (int64_t)(NN + 2 * LAG_N) * 8;
+    h->lag_host_glen.assign(glen.begin(), glen.end()); h->lag_host_ns.assign(lane_ns.begin(), lane_ns.end());
+    // the early cuts: with the late ones where the dispatch rule itself builds those (not where SSDE_LAGSTATS=2 alone forces them:
+    // ssde_set_option(SSDE_OPT_LAG_EARLY, 1) builds them there); BM_SSM and OU_SSM keep the late cut
+    // (d = 2 only: with one response coordinate the direction parts are not the single wave's bits, DESIGN.md §3.3d, so a d = 1 handle
+    //  keeps the late cut and its one-workgroup head unless the option is set by hand -- and pays no create time for cuts it would not use)
+    if (h->model == SSDE_MODEL_CTCRW && h->d == 2 && (double)bulk >= min_rows) {
+        const int st = build_lagstats_early(h);
+        if (st) return st;
+        h->lag_early = LAG_EARLY_DEFAULT && h->lag_cut_mask != 0;
+    }
+    h->lag_create_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return SSDE_OK;
 }
 

@@ -21,6 +21,7 @@ WindowFacts window_facts(const ssde_handle* h) {
     for (int j = 0; j < 2; j++) { f.cv_eta_lo[j] = h->cv_eta_lo[j]; f.cv_eta_hi[j] = h->cv_eta_hi[j]; }
     f.any_dirty = h->n_clean_groups < h->n_groups; f.quiet_ok = h->quiet_ok; f.lag_ready = h->lag_ready;
     f.quiet_window = h->knobs.quiet_window; f.block_rows = iso_block_rows(h->model);
+    f.lag_early = h->lag_early; f.lag_cut_mask = h->lag_cut_mask; f.lag_cut_min = LAG_CUT_MIN; f.lag_cut_step = LAG_CUT_STEP;
     return f;
 }
 
@@ -237,7 +238,8 @@ void lag_form_taps_scal(int model, const IsoArgs& a, int d, int mask, int K, con
 }
 
 // ... and their result into the reducing launch's arguments, as the window after the `n_windows` that live in the partial sums
-int lag_forms_into(ssde_handle* h, const IsoArgs& a, int order, int K, int n_windows, ReduceArgs& ra) {
+// (cut: the first bulk row -- LAG_A, or an early cut whose statistics the handle holds)
+int lag_forms_into(ssde_handle* h, const IsoArgs& a, int order, int K, int n_windows, ReduceArgs& ra, int cut) {
     // the reductions recognise the by-value window as the one after the windows of direction part 0 (reduce_slot, reduce_all_wave):
     // one part, one plan, and the sums run over exactly the windows that live in the partial sums
     if (a.n_parts != 1 || a.dual || ra.n_value_parts != n_windows || ra.chunks_per_part != n_windows || ra.n_parts != n_windows) {
@@ -246,10 +248,16 @@ int lag_forms_into(ssde_handle* h, const IsoArgs& a, int order, int K, int n_win
     }
     LagFormOut o;
     const int mask = order >= 1 ? a.part_mask[0] : 0;
+    const int ci = cut < LAG_A ? lag_cut_index(cut) : -1;
+    if (cut < LAG_A && (ci < 0 || !((h->lag_cut_mask >> ci) & 1u) || h->model != SSDE_MODEL_CTCRW || K >= cut)) {
+        h->err = "lag statistics: no statistics for the evaluation's cut";
+        return SSDE_ERR_ARG;
+    }
     if (h->model == SSDE_MODEL_CTCRW) {
         LagFormArgs f;
         lag_form_taps(a, h->d, mask, K, f);
         f.M = h->lag_M_host.data(); f.s = h->lag_s_host.data(); f.n = h->lag_n;
+        if (ci >= 0) { f.M = h->lag_cut_M_host[ci].data(); f.s = h->lag_cut_s_host[ci].data(); f.n = h->lag_cut_n[ci]; }
         lag_forms_host(f, o);
     } else {
         LagScalArgs f;
@@ -336,7 +344,7 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
     const ParLayout& L = h->L;
     IsoArgs a;
     memset(&a, 0, sizeof(a));
-    h->last_lag_rows = 0;
+    h->last_lag_rows = 0; h->last_lag_cut = 0;
     a.tv.tiles = h->tiles.p; a.tv.group_off = h->group_off.p; a.tv.group_len = h->group_len.p;
     a.tv.lane_nsteps = h->lane_nsteps.p; a.tv.a0 = h->a0.p; a.tv.n_groups = h->n_groups; a.tv.C = h->C; a.tv.c_obs = h->c_obs; a.tv.dt_all = h->dt_all;
     a.partials = h->partials.p;
@@ -463,14 +471,24 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
     we.gain_last = a.gain_last; we.gain_usable = h->gain_stationary && a.gain_stat[0] != 0.0;
     const WindowGeometry g = window_geometry(wf, WINDOW_CONSTS, wp, plan, policy.boost(), policy.gave_up, we);
     const int lag_K = g.lag_K;
+    // the bulk cut at the transient's end (head_early_cut): the head is window 0 alone -- one window from row 0 over tracks capped at the cut
+    const int lag_cut = lag_K > 0 ? g.lag_cut : 0;
+    const bool early = lag_K > 0 && lag_cut < LAG_A;
     h->plan_warmup = g.plan.warmup; h->plan_rho = g.plan.rho;
     a.n_chunks = g.n_chunks; a.window = g.window; a.t0 = g.t0; a.t0_delta = g.t0_delta;
+    if (early) { a.n_chunks = 1; a.t0 = 0; a.t0_delta = 0; }          // (window stays the warm-up in force -- the forms' K: one window reads none, ssde_info reports it)
     h->last_chunks = a.n_chunks; h->last_window = a.window; h->last_t0 = a.t0; h->last_t0_delta = a.t0_delta;
     h->last_quiet_window = g.quiet_window;
+    if (early) {
+        const int ci = lag_cut_index(lag_cut);
+        a.tv.group_len = h->lag_cut_glen[ci].p; a.tv.lane_nsteps = h->lag_cut_ns[ci].p;
+        h->last_lag_rows = h->lag_cut_rows[ci];
+    } else
     if (lag_K > 0) {                         // the head: every track capped at LAG_A rows
         a.tv.group_len = h->lag_glen.p; a.tv.lane_nsteps = h->lag_ns.p;
         h->last_lag_rows = h->lag_rows;
     }
+    h->last_lag_cut = lag_cut;
     if (g.quiet_window > 0) {
         a.nan_bits = h->nan_bits.p; a.nan_words = h->nan_words; a.quiet_flag = h->quiet_flag.p;
         a.quiet_w = g.quiet_w; a.quiet_b0 = g.quiet_b0;
@@ -487,10 +505,18 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
     // sent to its mailbox and forms the result on the host (run_once), every other caller gets them in device memory and a finalize
     // launch without check workgroups.  SSDE_FUSED_FINALIZE unset: this form; = 0: the two-launch form on iso_shared_kernel (A/B).
     static_assert(HEAD_WG_WAVES == WG_WAVES, "the plan credits the windows of one workgroup");
-    const bool wg = shared_alone && !h->knobs.fused_finalize && a.n_parts == 1 && a.t0 > 0 && a.t0_delta == 0 && a.n_chunks == WG_WAVES;
+    // The bulk cut at the transient's end: window 0 alone, its direction parts on the waves of the group's workgroup
+    // (iso_shared_cut_kernel) -- the same record, the same two ways out.  SSDE_FUSED_FINALIZE=0 / =1: the single wave of iso_shared_kernel
+    // on that window (A/B -- bitwise the same).
+    // (d = 2 only: with one response coordinate the parts' value is NOT the single wave's bits -- 4 ulp on a one-track batch, cause not
+    //  found.  A d = 1 handle has the option off by default and keeps the late cut with its one-workgroup head; set by hand, its early
+    //  cut runs the single wave of iso_shared_kernel and a finalize launch: the tests' form, slower than the late cut's head)
+    const bool cut_wg = early && shared_alone && !h->knobs.fused_finalize && a.n_parts == 1 && h->model == SSDE_MODEL_CTCRW && h->d == 2;
+    const bool wg = cut_wg || (shared_alone && !h->knobs.fused_finalize && a.n_parts == 1 && a.t0 > 0 && a.t0_delta == 0 && a.n_chunks == WG_WAVES);
     const bool host_finish = wg && h->host_finish_ok && h->mbx_pinned;
+    h->last_cut_parts = cut_wg ? cut_n_parts(order >= 1 ? a.part_mask[0] : 0) : 0;
     if (wg) {
-        a.wg_form = 1;
+        a.wg_form = cut_wg ? 2 : 1;
         if (host_finish) { a.mbx = h->mbx_pinned; a.mbx_seq = ++h->mbx_seq; }
     }
     HeadGain gv;
@@ -517,7 +543,7 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
         IsoArgs b = a;
         b.group_mode = 2;
         if (h->knobs.wave_clock) {
-            const int items = ((h->n_groups + 7) / 8 * 8) * a.n_chunks + 8;
+            const int items = ((h->n_groups + 7) / 8 * 8) * (cut_wg ? WG_WAVES : a.n_chunks) + 8;
             if ((int)h->wave_clock.n < 4 * items) { h->wave_clock.release(); HIPCHK(h, h->wave_clock.alloc((size_t)4 * items)); }
             HIPCHK(h, hipMemsetAsync(h->wave_clock.p, 0, (size_t)4 * items * 8, s));
             b.wave_clock = h->wave_clock.p; h->wave_clock_items = items;
@@ -546,7 +572,7 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
             }
             // the bulk's forms, on the host: the single launch of the fused form needs them; the two-launch form computes them
             // while the head runs (below), for its finalize launch
-            if (lag_K > 0 && fused) { const int st = lag_forms_into(h, a, order, lag_K, a.n_chunks, ra); if (st) return st; }
+            if (lag_K > 0 && fused) { const int st = lag_forms_into(h, a, order, lag_K, a.n_chunks, ra, lag_cut); if (st) return st; }
             HIPCHK(h, launch_iso_shared(h->model, h->d, b, ra, s, h->stamps ? h->ev_k0 : nullptr, h->stamps ? h->ev_k1 : nullptr,
                                         gv.rows > 0 ? &gv : nullptr));
         }
@@ -605,7 +631,7 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
     if (h->knobs.trace) { const double t = tick(); h->trace_us[2] += t - tk0; tk0 = t; }
     if (!fused) fill_reduce_args(h, a, order, add, ra);
     if (wg) ra.n_chk = h->n_groups;                     // (one check per group, from the main launch)
-    if (!fused && lag_K > 0) { const int st = lag_forms_into(h, a, order, lag_K, a.n_chunks, ra); if (st) return st; }     // (the head is running: this overlaps it)
+    if (!fused && lag_K > 0) { const int st = lag_forms_into(h, a, order, lag_K, a.n_chunks, ra, lag_cut); if (st) return st; }     // (the head is running: this overlaps it)
     // the hand-over checks and the final sums in one launch (unless the main launch has done them)
     if (host_finish) { h->host_ra = ra; h->host_armed = true; }      // (run_once: the spin on the mailbox and reduce_host)
     else if (!fused) HIPCHK(h, launch_iso_finalize(h->model, h->d, a, ra, s));

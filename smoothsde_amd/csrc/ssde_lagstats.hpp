@@ -56,6 +56,58 @@ inline void lag_track_stats(const double* y, int rows, int d, double* Q, double*
     }
 }
 
+// ---- early cuts (CTCRW) ----------------------------------------------------------------------------------------------------------
+// The same statistics with the first bulk row A' < LAG_A: every multiple of LAG_CUT_STEP (= WIN_ALIGN) from LAG_CUT_MIN to LAG_CUT_MAX,
+// for lags i, k < A' (no evaluation asks for more: K <= A' - s_stat).  A track with n <= A' contributes nothing, one with
+// A' < n <= LAG_A its rows [A', n).  They are the late statistics plus the head rows' own contribution,
+//     M(A') = M(LAG_A) + M~(A'),   M~(A')_ik = sum_{t = A'}^{min(n, LAG_A) - 1} Dy_{t-i} Dy_{t-k}
+// (s and n alike), and M~(A') is the definition above applied to the tracks CUT OFF after LAG_A rows: Toeplitz sums over
+// [A', min(n, LAG_A)) and the end terms h_j = Dy_{A'-1-j}, g_j = Dy_{min(n, LAG_A)-1-j}.  Entries with a lag >= A' are zero.
+constexpr int LAG_CUT_MIN = 32, LAG_CUT_MAX = 128, LAG_CUT_STEP = 16;
+constexpr int LAG_NCUT = (LAG_CUT_MAX - LAG_CUT_MIN) / LAG_CUT_STEP + 1;
+static_assert(LAG_CUT_MAX < LAG_A && LAG_CUT_MAX <= LAG_N && LAG_CUT_MIN % LAG_CUT_STEP == 0, "early cuts");
+// index of an early cut, -1 where A' is none
+inline int lag_cut_index(int cut) {
+    return (cut >= LAG_CUT_MIN && cut <= LAG_CUT_MAX && cut % LAG_CUT_STEP == 0) ? (cut - LAG_CUT_MIN) / LAG_CUT_STEP : -1;
+}
+// bit c set: cut LAG_CUT_MIN + c LAG_CUT_STEP (what the window policy reads: ssde_windows.hpp)
+constexpr unsigned LAG_CUT_ALL = (1u << LAG_NCUT) - 1u;
+
+// lag_track_stats with the first bulk row `cut` and the track cut off after `cap` rows (cap >= n: the whole track): Q[l], D[p][q], s[a][i]
+// for l, i < cut and p, q <= cut - 2, the other entries untouched.  Returns the bulk rows of the track.
+inline int lag_track_stats_cut(const double* y, int rows, int d, int cut, int cap, double* Q, double* D, double* s) {
+    const int n = rows < cap ? rows : cap;
+    if (n <= cut) return 0;
+    auto Y = [&](int t, int a) { return y[(int64_t)t * d + a]; };
+    auto Dy = [&](int t, int a) { return Y(t, a) - Y(t - 1, a); };
+    const int nl = cut < LAG_N ? cut : LAG_N;
+    for (int a = 0; a < d; a++) {
+        for (int l = 0; l < nl; l++) {
+            double q = 0.0;
+            for (int t = cut; t < n; t++) q += Dy(t, a) * Dy(t - l, a);
+            Q[l] += q;
+        }
+        for (int p = 0; p + 2 <= cut && p < LAG_N; p++)
+            for (int q = 0; q + 2 <= cut && q < LAG_N; q++)
+                D[(int64_t)p * LAG_N + q] += Dy(cut - 1 - p, a) * Dy(cut - 1 - q, a) - Dy(n - 1 - p, a) * Dy(n - 1 - q, a);
+        for (int i = 0; i < nl; i++) s[a * LAG_N + i] += Y(n - 1 - i, a) - Y(cut - 1 - i, a);
+    }
+    return n - cut;
+}
+
+// M of an early cut from its Q and D (lag_assemble's order), entries with a lag >= cut zero
+inline void lag_assemble_cut(const double* Q, const double* D, int cut, double* M) {
+    for (int64_t e = 0; e < (int64_t)LAG_N * LAG_N; e++) M[e] = 0.0;
+    const int nl = cut < LAG_N ? cut : LAG_N;
+    for (int l = 0; l < nl; l++) {
+        double run = Q[l];
+        for (int i = 0; i + l < nl; i++) {
+            M[(int64_t)i * LAG_N + i + l] = M[(int64_t)(i + l) * LAG_N + i] = run;
+            run += D[(int64_t)i * LAG_N + i + l];
+        }
+    }
+}
+
 // OU_SSM (stationary around mu: no factor 1 - q^-1 to take on the data) needs the same statistics of the LEVELS z_{a,t} = y_{a,t} - ref_a
 // instead of the increments; ref_a is one number per coordinate, fixed at create near the data (the handle's: the observation at
 // row LAG_A - 1 of the first track in tiled order that has a bulk), so that z stays within a few process standard deviations.  The

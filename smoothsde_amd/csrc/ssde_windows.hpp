@@ -136,6 +136,10 @@ struct WindowFacts {
     bool any_dirty = false, quiet_ok = false, lag_ready = false;
     int quiet_window = 0;                        // SSDE_QUIET_WINDOW
     int block_rows = 1;                          // iso_block_rows(model): rows per block of the quiet-row flags
+    // the lag statistics at early cuts (ssde_lagstats.hpp): SSDE_OPT_LAG_EARLY, and bit c: cut lag_cut_min + c lag_cut_step is built
+    bool lag_early = false;
+    unsigned lag_cut_mask = 0;
+    int lag_cut_min = 0, lag_cut_step = 1;
 };
 
 struct WindowPlan {
@@ -243,7 +247,8 @@ struct WindowGeometry {
     int t0 = 0, t0_delta = 0;     // the transient window [0, t0); rows taken off window 1, whose wave runs it too (0 with t0 > 0: it has a wave of its own)
     bool dual = false;            // mixed batch: the general launch runs a plan of its own ...
     int n_chunks_d = 0, t0_d = 0; // ... of this many windows, window 0 = [0, t0_d)
-    int lag_K = 0;                // > 0: rows past LAG_A from the lag statistics, with this many taps
+    int lag_K = 0;                // > 0: rows past lag_cut from the lag statistics, with this many taps
+    int lag_cut = 0;              // the first bulk row: LAG_A, or t0 where the statistics of that cut exist (head_early_cut): the head is then window 0 alone
     int s_stat = 0;               // stationary_row of the gain table
     int quiet_window = 0;         // rows of memory of the quiet rows (0: none), in blocks: quiet_w, first quiet block: quiet_b0
     int quiet_w = 0, quiet_b0 = 0;
@@ -294,9 +299,24 @@ inline void head_latency_plan(const WindowFacts& f, const WindowConsts& c, Windo
     if (best_k > 0) { g.n_chunks = best_k + 1; g.t0_delta = 0; }
 }
 
+// The bulk cut at the transient's end.  The forms need stationary gains for K rows before the first bulk row, and the
+// head's plan already puts t0 = align(s_stat + W) with lag_K = W: rows [t0, LAG_A) are streamed only because the statistics stand at
+// the fixed cut LAG_A.  Where statistics for the cut t0 exist the head is window 0 alone.  Decided after the head plan as it stands,
+// and no other field moves: the transient window on a wave of its own (the latency plan's geometry), CTCRW, the option on, no forced
+// window count, no Hessian request, no plan that has given up; K < t0 (the forms read lags 0 .. K of statistics built for lags < t0).
+// A failed check boosts the warm-up, which moves t0 -- possibly off the list of cuts, and then the late cut runs.
+inline int head_early_cut(const WindowFacts& f, const WindowConsts& c, const WindowGeometry& g, bool gave_up, const WindowEval& e) {
+    if (!(f.lag_early && f.model == SSDE_MODEL_CTCRW && g.lag_K > 0 && g.t0 > 0 && g.t0_delta == 0 && !f.chunks_forced && !e.hess_req &&
+          !gave_up && g.lag_K < g.t0 && g.t0 < c.lag_a)) return c.lag_a;
+    const int k = g.t0 - f.lag_cut_min;
+    if (k < 0 || f.lag_cut_step < 1 || k % f.lag_cut_step != 0 || k / f.lag_cut_step >= 32) return c.lag_a;
+    return ((f.lag_cut_mask >> (k / f.lag_cut_step)) & 1u) ? g.t0 : c.lag_a;
+}
+
 inline WindowGeometry window_geometry(const WindowFacts& f, const WindowConsts& c, const WindowParams& a, const WindowPlan& first,
                                       int boost, bool gave_up, const WindowEval& e) {
     WindowGeometry g;
+    g.lag_cut = c.lag_a;
     g.plan = first;
     g.n_chunks = first.n_chunks; g.window = first.window;
     g.s_stat = stationary_row(e.gain_last, c.shared_u);
@@ -340,6 +360,7 @@ inline WindowGeometry window_geometry(const WindowFacts& f, const WindowConsts& 
     // ... except in the head of the lag-statistics path where a wave of its own is cheaper (t0 > 0 with t0_delta == 0, the meaning
     // the general kernel's balanced window 0 already has); a forced window count (SSDE_CHUNKS) keeps the throughput geometry: A/B
     if (g.lag_K > 0 && !f.chunks_forced) head_latency_plan(f, c, g);
+    g.lag_cut = head_early_cut(f, c, g, gave_up, e);
     if (!f.use_shared && !f.drift && g.n_chunks > 1) {
         const int t0 = balanced_window0(f.glen_max, g.n_chunks, g.window, e.can_derive, c.win_align);
         if (t0 > 0) { g.t0 = t0; g.t0_delta = 0; }

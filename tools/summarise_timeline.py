@@ -36,10 +36,10 @@ for r in rows("memory_copy_trace"):
     n = "copy H2D" if "HOST_TO_DEVICE" in dirn else "copy D2H" if "DEVICE_TO_HOST" in dirn else "copy " + dirn
     ev.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), n))
 ev.sort()
-HEADS = ("iso_shared_kernel", "iso_shared_wg_kernel")      # (the second: one workgroup per track group)
+HEADS = ("iso_shared_kernel", "iso_shared_wg_kernel", "iso_shared_cut_kernel")      # (the second: one workgroup per track group, the third: its waves the direction parts of window 0)
 heads = [i for i, e in enumerate(ev) if e[2] in HEADS]
 if not heads:
-    sys.exit("no iso_shared_kernel / iso_shared_wg_kernel dispatch in the trace")
+    sys.exit("no iso_shared_kernel / iso_shared_wg_kernel / iso_shared_cut_kernel dispatch in the trace")
 NEAR = 200000       # ns: a command further than this from the head launch belongs to something else
 evals = []
 for a, b in zip(heads, heads[1:] + [len(ev)]):
