@@ -9,7 +9,7 @@ namespace ssde {
 hipError_t launch_iso_shared_ctcrw(int d, const IsoArgs& a, const ReduceArgs& r, dim3 grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, bool deep, const HeadGain* hg);
 hipError_t launch_iso_shared_ou(int d, const IsoArgs& a, const ReduceArgs& r, dim3 grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, bool deep, const HeadGain* hg);
 hipError_t launch_iso_shared_bm(int d, const IsoArgs& a, const ReduceArgs& r, dim3 grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, bool deep, const HeadGain* hg);
-hipError_t launch_iso_shared_cut(int d, const IsoArgs& a, dim3 grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, const HeadGain* hg);     // k_iso_shared_cut.hip
+hipError_t launch_iso_shared_cut(int d, const IsoArgs& a, const HeadLead& lead, dim3 grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, const HeadGain* hg);     // k_iso_shared_cut.hip
 
 // host side: the stationary constants (layout in ssde_device.hpp)
 void fill_stat_consts(int model, int d, IsoArgs& a) {
@@ -52,7 +52,8 @@ void fill_stat_consts(int model, int d, IsoArgs& a) {
 
 // the shared path runs all directions in one part (n_parts == 1, mask = part_mask[0]).  r: the reduction's arguments, read by the kernel
 // only when a.fused (the finalising work inside this launch); a.fuse_items is set here
-hipError_t launch_iso_shared(int model, int d, const IsoArgs& a0, const ReduceArgs& r, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, const HeadGain* hg) {
+hipError_t launch_iso_shared(int model, int d, const IsoArgs& a0, const ReduceArgs& r, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, const HeadGain* hg,
+                             const HeadLead* lead) {
     if (a0.n_parts != 1) return hipErrorInvalidValue;
     IsoArgs a = a0;
     const int g8 = (a.tv.n_groups + 7) / 8;
@@ -65,7 +66,8 @@ hipError_t launch_iso_shared(int model, int d, const IsoArgs& a0, const ReduceAr
     if (a.wg_form == 2) {
         if (!(model == M_CTCRW && a.n_chunks == 1 && a.t0 == 0 && !a.fused && a.group_mode != 1)) return hipErrorInvalidValue;
         if (hg && hg->rows > HEAD_GAIN_ROWS) return hipErrorInvalidValue;
-        return launch_iso_shared_cut(d, a, dim3(g8 * 8), s, ev0, ev1, hg);
+        if (!lead) return hipErrorInvalidValue;
+        return launch_iso_shared_cut(d, a, *lead, dim3(g8 * 8), s, ev0, ev1, hg);
     }
     if (a.wg_form && !(a.n_chunks == WG_WAVES && a.t0 > 0 && a.t0_delta == 0 && !a.fused && a.group_mode != 1)) return hipErrorInvalidValue;
     if (hg && hg->rows > 0 && !(a.wg_form && hg->rows <= HEAD_GAIN_ROWS)) return hipErrorInvalidValue;      // (by value: that entry only)

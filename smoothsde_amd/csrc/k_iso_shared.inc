@@ -24,6 +24,19 @@
 
 namespace ssde {
 
+// -DSSDE_HEAD_STAMPS (a measuring build of k_iso_shared_cut.hip; off by default -- the default code object has none of this): where a
+// wave of the lag-path head spends its time.  stamp[0] the first row's data and gains have arrived, [1] end of the table rows, [2] end of
+// the stationary rows ([3], after the barrier, is the kernel's).  wall_clock64: 100 MHz, as SSDE_WAVE_CLOCK's own two stamps.
+#ifdef SSDE_HEAD_STAMPS
+#define SSDE_STAMP_PARAM , long long* stamp = nullptr
+#define SSDE_STAMP_ARG , stamp
+#define SSDE_STAMP(k) do { if (stamp) stamp[k] = wall_clock64(); } while (0)
+#else
+#define SSDE_STAMP_PARAM
+#define SSDE_STAMP_ARG
+#define SSDE_STAMP(k) do { } while (0)
+#endif
+
 // C = channels per step of the tile, c_obs = channel of the first obs column (a dt channel, if present, is not read).
 // nt (wave-uniform): non-temporal loads.  A batch that is streamed once per evaluation and is far larger than the 256 MB
 // Infinity Cache wants them (the headline batch, 1.6 GB: 0.259 against 0.274 ms with ordinary loads); a batch that FITS that
@@ -63,7 +76,8 @@ struct SharedCtcrw {
     double cx[D], cv[D], bmu[D];
     CtcrwTrans tr;
 
-    __device__ __forceinline__ void setup(const IsoArgs& A) {
+    template <class Args>      // (IsoArgs, or the cut kernel's HeadArgs: the same field names)
+    __device__ __forceinline__ void setup(const Args& A) {
         tr = A.ctr;
         const double* c = A.statc;   // static indices into the kernel argument block: scalar loads
         iF = c[0]; k1 = c[1]; k2 = c[2]; c1 = c[3]; t12 = c[4]; e = c[5]; dt12 = c[6]; de = c[7]; cb1 = c[8]; cb2 = c[9];
@@ -273,9 +287,16 @@ struct SharedSel<M_CTCRW, D, MASK, true> { typedef TfCtcrw<D, MASK> type; };
 constexpr int GAIN_SLAB_ROWS = 64;      // multiple of 2 * SHARED_U
 static_assert(GAIN_SLAB_ROWS % (2 * SHARED_U) == 0, "gain slab");
 
-__device__ __forceinline__ void stage_gain(const IsoArgs& A, double* slab, int row0) {
+// (iso_shared_cut_kernel reads a COPY of its argument block, k_iso_shared_cut.hip: a pointer out of the copy is a number to the compiler: said to point to global memory, as a kernel's pointer argument does, or every
+//  load through it would be a flat one)
+template <class T>
+__device__ __forceinline__ T* head_global(T* p) { return (T*)(__attribute__((address_space(1))) T*)(unsigned long long)p; }      // (through the integer: a cast pair alone is folded away)
+__device__ __forceinline__ const double* gain_table_ptr(const IsoArgs& A) { return A.gain; }
+__device__ __forceinline__ const double* gain_table_ptr(const HeadArgs& A) { return head_global(A.gain); }
+template <class Args>
+__device__ __forceinline__ void stage_gain(const Args& A, double* slab, int row0) {
     const int lane = threadIdx.x & 63, glast = A.gain_last;
-    const double* __restrict__ gain = A.gain;
+    const double* __restrict__ gain = gain_table_ptr(A);
 #pragma unroll 4
     for (int r = 0; r < GAIN_SLAB_ROWS; r += WAVE / GAIN_ROW) {          // 4 rows of 16 doubles per wave load
         const int rr = r + lane / GAIN_ROW;
@@ -289,23 +310,32 @@ __device__ __forceinline__ void stage_gain(const IsoArgs& A, double* slab, int r
 // The same slab from a table that came BY VALUE in the launch's argument block (HeadGain, ssde_gain_feed.hpp; iso_shared_wg_kernel): no
 // copy precedes the launch and no pointer is chased -- the lanes read the packed rows straight from the block, same lane -> slab
 // element map as above, rows past the last repeat it, the columns no model writes are zero.
-__device__ __forceinline__ void stage_gain_value(const HeadGain& G, double* slab, int row0) {
-    const int lane = threadIdx.x & 63, rows = G.rows;
-    constexpr int NL = GAIN_SLAB_ROWS / (WAVE / GAIN_ROW);
-    // every load of the slab is issued before the first store waits for one: one round trip to the block
-    double t[NL];
+// (rows: HeadGain.rows, which the cut kernel has in its hot block -- head_gain_rows.  In two halves: the cut kernel issues the first
+//  slab's loads with its first round of loads and stores when the rows begin.)
+constexpr int GAIN_SLAB_NL = GAIN_SLAB_ROWS / (WAVE / GAIN_ROW);      // loads per lane and slab
+__device__ __forceinline__ void gain_value_loads(const HeadGain& G, int rows, int row0, double (&t)[GAIN_SLAB_NL]) {
+    const int lane = threadIdx.x & 63;
 #pragma unroll
-    for (int i = 0; i < NL; i++) t[i] = head_gain_slab_at(G.v, rows, row0 + i * (WAVE / GAIN_ROW) + lane / GAIN_ROW, lane % GAIN_ROW);
+    for (int i = 0; i < GAIN_SLAB_NL; i++) t[i] = head_gain_slab_at(G.v, rows, row0 + i * (WAVE / GAIN_ROW) + lane / GAIN_ROW, lane % GAIN_ROW);
+}
+__device__ __forceinline__ void gain_value_stores(const double (&t)[GAIN_SLAB_NL], double* slab) {
+    const int lane = threadIdx.x & 63;
 #pragma unroll
-    for (int i = 0; i < NL; i++) slab[(i * (WAVE / GAIN_ROW) + lane / GAIN_ROW) * GAIN_ROW + (lane % GAIN_ROW)] = t[i];
+    for (int i = 0; i < GAIN_SLAB_NL; i++) slab[(i * (WAVE / GAIN_ROW) + lane / GAIN_ROW) * GAIN_ROW + (lane % GAIN_ROW)] = t[i];
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
+__device__ __forceinline__ void stage_gain_value(const HeadGain& G, int rows, double* slab, int row0) {
+    // every load of the slab is issued before the first store waits for one: one round trip to the block
+    double t[GAIN_SLAB_NL];
+    gain_value_loads(G, rows, row0, t);
+    gain_value_stores(t, slab);
+}
 
 // rows [s0, s0 + SHARED_U) from a register block; `grow` = the slab row of s0 (table phase)
-template <bool STAT, int D, class Lane>
-__device__ __forceinline__ void run_block(Lane& S, const IsoArgs& A, const double (&blk)[SHARED_U][D], int s0, int ns,
+template <bool STAT, int D, class Lane, class Args>
+__device__ __forceinline__ void run_block(Lane& S, const Args& A, const double (&blk)[SHARED_U][D], int s0, int ns,
                                           int ns_min, const double* mu, const double* grow) {
     if (s0 + SHARED_U <= ns_min) {
         // every lane's track covers the whole block: no per-row predication
@@ -328,9 +358,18 @@ __device__ __forceinline__ void run_block(Lane& S, const IsoArgs& A, const doubl
 // rows [sa, sb) of the lane's window; STAT = stationary gains.  sa is a multiple of SHARED_U.
 // Two register blocks in ping-pong: while one is consumed the other is in flight (no copies).
 // WG: the waves of the workgroup run the windows of ONE group (iso_shared_wg_kernel) -- only wave 0 walks table rows: one gain slab.
-template <bool STAT, int D, bool DEEP, bool WG, class Lane>
-__device__ __forceinline__ void run_segment(Lane& S, const IsoArgs& A, const double* base, int sa, int sb, int ns,
-                                            int ns_min, const double* mu, const HeadGain* G = nullptr) {
+// PRE (iso_shared_cut_kernel): the caller issued the loads of the segment's first TWO blocks and of its first gain slab (by value) with
+// its own first round of loads; `pre` holds them.
+template <int D>
+struct HeadPre {
+    double a[SHARED_U][D], b[SHARED_U][D];
+    double gt[GAIN_SLAB_NL];         // (gain_rows > 0 only)
+};
+__device__ __forceinline__ int head_gain_rows(const IsoArgs&, const HeadGain& G) { return G.rows; }
+__device__ __forceinline__ int head_gain_rows(const HeadArgs& A, const HeadGain&) { return A.gain_rows; }
+template <bool STAT, int D, bool DEEP, bool WG, class Lane, class Args, bool PRE = false>
+__device__ __forceinline__ void run_segment(Lane& S, const Args& A, const double* base, int sa, int sb, int ns,
+                                            int ns_min, const double* mu, const HeadGain* G = nullptr, const HeadPre<D>* pre = nullptr SSDE_STAMP_PARAM) {
     const int C = A.tv.C, c_obs = A.tv.c_obs;
     const bool nt = A.stream_nt != 0;
     if (sa >= sb) return;
@@ -363,14 +402,22 @@ __device__ __forceinline__ void run_segment(Lane& S, const IsoArgs& A, const dou
         }
         return;
     }
-    load_obs_block<D>(bufA, SSDE_ROWPTR(sa), C, c_obs, nt);
+    if constexpr (PRE) {
+#pragma unroll
+        for (int u = 0; u < SHARED_U; u++)
+#pragma unroll
+            for (int a = 0; a < D; a++) { bufA[u][a] = pre->a[u][a]; bufB[u][a] = pre->b[u][a]; }
+    } else load_obs_block<D>(bufA, SSDE_ROWPTR(sa), C, c_obs, nt);
     for (int s0 = sa; s0 < sb; s0 += 2 * SHARED_U) {
         // TILE_SPARE (>= 3 blocks) keeps the look-ahead loads inside the allocation
-        load_obs_block<D>(bufB, SSDE_ROWPTR(s0 + SHARED_U), C, c_obs, nt);
+        if (!(PRE && s0 == sa)) load_obs_block<D>(bufB, SSDE_ROWPTR(s0 + SHARED_U), C, c_obs, nt);
         const int srow = (s0 - sa) % GAIN_SLAB_ROWS;
         if (!STAT && srow == 0) {
-            if (WG && G->rows > 0) stage_gain_value(*G, slab, s0);
+            const int grows = WG ? head_gain_rows(A, *G) : 0;
+            if (PRE && s0 == sa && grows > 0) gain_value_stores(pre->gt, slab);
+            else if (WG && grows > 0) stage_gain_value(*G, grows, slab, s0);
             else stage_gain(A, slab, s0);
+            if (s0 == 0) SSDE_STAMP(0);
         }
         run_block<STAT, D>(S, A, bufA, s0, ns, ns_min, mu, slab + srow * GAIN_ROW);
         load_obs_block<D>(bufA, SSDE_ROWPTR(s0 + 2 * SHARED_U), C, c_obs, nt);

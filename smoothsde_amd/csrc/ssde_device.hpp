@@ -301,6 +301,72 @@ __host__ __device__ constexpr inline int cut_part_of(int mask, int bit) {
         if (cut_part_mask(mask, p) & bit) return p;
     return 0;
 }
+// ---- the argument block of iso_shared_cut_kernel (k_iso_shared_cut.hip) --------------------------------------------------------------
+// Everything the lane code of that entry reads before and during its rows, in ONE contiguous block at the front of its by-value
+// arguments, in the order of use -- IsoArgs has the same values spread over 2 KB (tv at 0x0, statc at 0xe0, ctr at 0x2b0, mbx past
+// 0x800), each a cold line of the scalar cache at every launch and a round trip of its own.  The field names are IsoArgs', so the lane
+// code of k_iso_shared.inc takes either block; IsoArgs keeps its fields for every other kernel.  Filled by head_args_fill from the
+// IsoArgs of the launch: nothing here is computed twice.
+//   lead_n, lead_stride: groups g < lead_n lie at g * lead_stride doubles (as long as the leading groups are equally long their offsets
+//     are multiples of the first one's size: head_lead_groups) -- their first rows are fetched without waiting for group_off[g];
+//   ns_min[g]: the smallest lane_nsteps of the group over its lanes WITH a track (INT32_MAX: none), at this launch's cut
+//     (head_ns_min) -- what the lanes used to find with six shuffles after lane_nsteps had arrived.
+constexpr int HEAD_STATC = 26;               // CTCRW's stationary constants: statc[0 .. 25) (see IsoArgs.statc), padded to whole 16-byte pairs
+struct HeadLead {                            // what create knows about the batch and the cut (ssde_engine_build.hip)
+    const int32_t* ns_min;
+    int64_t lead_stride;
+    int lead_n;
+};
+struct HeadArgs {
+    TileView tv;                             // 64 bytes: one line
+    const int32_t* ns_min;
+    int64_t lead_stride;
+    int lead_n;
+    int n_chunks, window, t0, t0_delta;      // (the engine launches this entry with ONE window from row 0: window_bounds' first line)
+    int gain_last;
+    int gain_rows;                           // HeadGain.rows
+    int stream_nt;
+    double gain_stat0;                       // gain_stat[0]
+    const double* gain;                      // the copied table (gain_rows == 0)
+    double mu[2];
+    CtcrwTrans ctr;
+    double statc[HEAD_STATC];
+    // the ways out
+    double* mbx;
+    unsigned long long mbx_seq;
+    double* partials;
+    double* chk;
+    double* chk_out;
+    double* wave_clock;
+};
+static_assert(sizeof(HeadArgs) <= 9 * 64, "the hot block: nine 64-byte lines");
+static_assert(sizeof(HeadArgs) + sizeof(HeadGain) <= HEAD_ARG_BLOCK, "a launch's argument block");
+// (plain host code: tests/hostsim/hostsim_headargs.cpp compares every field)
+inline void head_args_fill(HeadArgs& o, const IsoArgs& a, const HeadLead& lead, int gain_rows) {
+    o.tv = a.tv;
+    o.ns_min = lead.ns_min; o.lead_stride = lead.lead_stride; o.lead_n = lead.lead_n;
+    o.n_chunks = a.n_chunks; o.window = a.window; o.t0 = a.t0; o.t0_delta = a.t0_delta;
+    o.gain_last = a.gain_last; o.gain_rows = gain_rows; o.stream_nt = a.stream_nt;
+    o.gain_stat0 = a.gain_stat[0]; o.gain = a.gain;
+    o.mu[0] = a.mu[0]; o.mu[1] = a.mu[1];
+    o.ctr = a.ctr;
+    for (int i = 0; i < HEAD_STATC; i++) o.statc[i] = a.statc[i];
+    o.mbx = a.mbx; o.mbx_seq = a.mbx_seq; o.partials = a.partials; o.chk = a.chk; o.chk_out = a.chk_out; o.wave_clock = a.wave_clock;
+}
+// groups g < the result lie at g * (glen[0] * C * WAVE) doubles: the leading groups of one length, and the first group after them
+inline int head_lead_groups(const int32_t* glen, int n_groups) {
+    int n = 0;
+    while (n < n_groups && glen[n] == glen[0]) n++;
+    return n < n_groups ? n + 1 : n;
+}
+// ns_min[g] of lane_nsteps [n_groups][WAVE]: run_lane_shared's definition
+inline void head_ns_min(const int32_t* lane_ns, int n_groups, int32_t* out) {
+    for (int g = 0; g < n_groups; g++) {
+        int32_t m = INT32_MAX;
+        for (int l = 0; l < WAVE; l++) { const int32_t ns = lane_ns[(size_t)g * WAVE + l]; if (ns > 0 && ns < m) m = ns; }
+        out[g] = m;
+    }
+}
 hipError_t launch_iso(int model, int d, const IsoArgs& a, bool any_dirty, hipStream_t s);
 // blocks of iso_block_rows() rows in which some lane of a group misses an observation: bits [n_groups][nwords] (k_iso.hip)
 int iso_block_rows(int model);
@@ -308,8 +374,9 @@ hipError_t launch_nan_blocks(const TileView& tv, int d, int block_rows, unsigned
 // ev0 / ev1 (may be NULL): stamped with the kernel's own begin / end
 struct ReduceArgs;
 // hg: the gain table by value (a.wg_form launches with hg->rows > 0; a.gain is then not read), or NULL
+// (lead: iso_shared_cut_kernel's -- wg_form == 2 -- and required there)
 hipError_t launch_iso_shared(int model, int d, const IsoArgs& a, const ReduceArgs& r, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1,
-                             const HeadGain* hg = nullptr);
+                             const HeadGain* hg = nullptr, const HeadLead* lead = nullptr);
 // shared-covariance lanes with a streamed row-varying drift (k_iso_drift.hip); partials [n_chunks][4 + d + drift_k][n_groups]
 hipError_t launch_iso_drift(int model, int d, const IsoArgs& a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 int drift_nstate(int model, int d, int k);

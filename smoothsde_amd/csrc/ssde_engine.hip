@@ -73,7 +73,7 @@ void release_device(ssde_handle* h) {
     destroy_dist(h);
     h->bnd.release(); h->chk.release(); h->group_flags.release(); h->gain_ring.release(); h->pad_pos.release(); h->pad_row.release(); h->dirty_groups.release(); h->lap_out.release(); h->nan_bits.release(); h->quiet_flag.release();
     h->lag_M.release(); h->lag_s.release(); h->lag_glen.release(); h->lag_ns.release();
-    for (int c = 0; c < LAG_NCUT; c++) { h->lag_cut_M[c].release(); h->lag_cut_s[c].release(); h->lag_cut_glen[c].release(); h->lag_cut_ns[c].release(); }
+    for (int c = 0; c < LAG_NCUT; c++) { h->lag_cut_M[c].release(); h->lag_cut_s[c].release(); h->lag_cut_glen[c].release(); h->lag_cut_ns[c].release(); h->lag_cut_nsmin[c].release(); }
     h->lag_cut_mask = 0; h->lag_early = false;
     if (h->gain_pinned) (void)hipHostFree(h->gain_pinned);
     for (int i = 0; i < 2; i++) { if (h->aux[i]) (void)hipStreamDestroy(h->aux[i]); if (h->ev_join[i]) (void)hipEventDestroy(h->ev_join[i]); }

@@ -330,6 +330,9 @@ struct ssde_handle {
     int64_t lag_cut_rows[ssde::LAG_NCUT] = {};
     DevBuf<double> lag_cut_M[ssde::LAG_NCUT], lag_cut_s[ssde::LAG_NCUT];          // the device copies (ssde_lagstats_read_cut)
     DevBuf<int32_t> lag_cut_glen[ssde::LAG_NCUT], lag_cut_ns[ssde::LAG_NCUT];     // group_len / lane_nsteps capped at the cut
+    DevBuf<int32_t> lag_cut_nsmin[ssde::LAG_NCUT];   // [n_groups] the smallest lag_cut_ns of a group over its lanes with a track (head_ns_min)
+    int lag_lead_n = 0;                    // groups g < lag_lead_n lie at g * lag_lead_stride doubles of the tiles (head_lead_groups)
+    int64_t lag_lead_stride = 0;
     std::vector<int32_t> lag_host_glen, lag_host_ns;   // the uncapped lengths, kept for a later build of the early cuts
     int last_lag_cut = 0;                  // first bulk row of the last evaluation (0: streamed)
     int last_cut_parts = 0;                // > 0: its head ran as this many direction parts per group, one workgroup per padded group (iso_shared_cut_kernel)

@@ -161,6 +161,10 @@ int build_lagstats_early(ssde_handle* h) {
     }
     std::vector<double> host(sums.n), dM(NN);
     unsigned mask = 0;
+    // the head's first rows without group_off (ssde_device.hpp, HeadArgs): facts of the tiling, the same for every cut -- set before
+    // any cut is built, so that whichever cuts stand after an error below have them
+    h->lag_lead_n = head_lead_groups(h->lag_host_glen.data(), G);
+    h->lag_lead_stride = (int64_t)h->lag_host_glen[0] * h->C * WAVE;
     for (int c = 0; c < LAG_NCUT; c++) {
         const int cut = LAG_CUT_MIN + c * LAG_CUT_STEP;
         if (h->lag_cut_mask & (1u << c)) continue;
@@ -185,9 +189,14 @@ int build_lagstats_early(ssde_handle* h) {
         if (e == hipSuccess && !h->lag_cut_s[c].p) e = h->lag_cut_s[c].upload(sv);
         if (e == hipSuccess && !h->lag_cut_glen[c].p) e = h->lag_cut_glen[c].upload(cg);
         if (e == hipSuccess && !h->lag_cut_ns[c].p) e = h->lag_cut_ns[c].upload(cn);
+        if (e == hipSuccess && !h->lag_cut_nsmin[c].p) {
+            std::vector<int32_t> cm(G);
+            head_ns_min(cn.data(), G, cm.data());
+            e = h->lag_cut_nsmin[c].upload(cm);
+        }
         if (e != hipSuccess) {                               // (no room for the copies: the cuts built so far stand, the others keep the late cut)
             (void)hipGetLastError();
-            h->lag_cut_M[c].release(); h->lag_cut_s[c].release(); h->lag_cut_glen[c].release(); h->lag_cut_ns[c].release();
+            h->lag_cut_M[c].release(); h->lag_cut_s[c].release(); h->lag_cut_glen[c].release(); h->lag_cut_ns[c].release(); h->lag_cut_nsmin[c].release();
             break;
         }
         h->hbm_bytes += (int64_t)(NN + 2 * LAG_N) * 8;

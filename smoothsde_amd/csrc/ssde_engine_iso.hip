@@ -521,6 +521,8 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
     }
     HeadGain gv;
     gv.rows = 0;
+    HeadLead lead = {nullptr, 0, 0};
+    if (cut_wg) { lead.ns_min = h->lag_cut_nsmin[lag_cut_index(lag_cut)].p; lead.lead_stride = h->lag_lead_stride; lead.lead_n = h->lag_lead_n; }
     if (gain_deferred) {
         const int st = feed_gain_table(h, a, wg, s, gv);
         if (st) return st;
@@ -574,7 +576,7 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
             // while the head runs (below), for its finalize launch
             if (lag_K > 0 && fused) { const int st = lag_forms_into(h, a, order, lag_K, a.n_chunks, ra, lag_cut); if (st) return st; }
             HIPCHK(h, launch_iso_shared(h->model, h->d, b, ra, s, h->stamps ? h->ev_k0 : nullptr, h->stamps ? h->ev_k1 : nullptr,
-                                        gv.rows > 0 ? &gv : nullptr));
+                                        gv.rows > 0 ? &gv : nullptr, cut_wg ? &lead : nullptr));
         }
         h->last_kernel_id = h->drift ? SSDE_KERNEL_ISO_DRIFT : any_dirty ? SSDE_KERNEL_ISO_MIXED : SSDE_KERNEL_ISO_SHARED;
         h->ev_k_valid = h->stamps;
