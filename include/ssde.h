@@ -31,6 +31,9 @@
  *                         reference gets by rebuilding the data with NA rows at the wanted times
  *   ssde_path_stats    <- (new) summaries of those draws reduced on the device: path length, net displacement and weighted time
  *                         inside up to eight boxes per track and draw, without a draw leaving the device
+ *   ssde_path_speed    <- (new) the speed |v| along those draws of a CTCRW reduced on the device: integral, maximum and its row,
+ *                         heading resultant and weighted time at or below up to eight speeds per track and draw, and per row the
+ *                         number of draws at or below each speed
  *   ssde_path_occupancy <- (new) the weighted time those draws spend in every cell of a regular grid, pooled over draws and over
  *                         groups of tracks: a utilisation distribution, summed on the device as integers and so bitwise reproducible
  *   ssde_predict_draws <- (new) those draws' states at any time between or after the rows: the same paths as ssde_smooth_draws,
@@ -423,6 +426,38 @@ int ssde_predict_draws(ssde_handle *h, const double *par, int32_t n_par_full, co
 #define SSDE_PATH_MAX_REGIONS 8
 int ssde_path_stats(ssde_handle *h, const double *par, int32_t n_par_full, uint64_t seed, int64_t draw0, int32_t n_draws,
                     const double *regions, int32_t n_regions, const double *weight, double *stats, uint32_t flags);
+
+/* Speed along posterior state paths at `par`, reduced on the device (definitions: DESIGN.md §3.17).  Draws, state rows and weights are
+ * exactly those of ssde_path_stats: draw q is draw number draw0 + q of the stream `seed`, the path ssde_smooth_draws returns; a track's
+ * state rows are the CALLER's rows first + 1 .. last (a lattice-padded handle samples its padded rows, which take part in nothing);
+ * weight [n] host memory by the caller's row, or NULL for w_j = 1, not validated.  A CTCRW only: v_a is state column 2a + 1 of response
+ * column a, and the speed at a state row is s = |v_1| for n_dim = 1 and s = sqrt(v_1^2 + v_2^2) for n_dim = 2.
+ *   stats [n_tracks x n_stat x n_draws], n_stat = 5 + n_thr: element (t, k, q) at t + n_tracks * (k + n_stat * q), t the ID segment's
+ *   ordinal in the caller's data.
+ *     k = 0      sum over state rows j of w_j s_j: with dt weights the integral of speed; divided by sum w_j the mean speed
+ *     k = 1      max over j of s_j
+ *     k = 2      the caller's row (0-based, as a double) that attains the maximum; a tie gives the smallest row
+ *     k = 3, 4   the resultant sum over j of w_j v_jc / s_j for c = 1, 2; a row with s_j = 0 adds nothing; for n_dim = 1, k = 3 is
+ *                sum w_j sign(v_j) and k = 4 is 0.  |resultant| / sum w_j is the usual measure of directional persistence
+ *     k = 5 + r  sum over j of w_j 1[s_j <= thr[r]]
+ *   row_below [n x n_thr] uint32: element (j, r) at j + n * r, j the caller's row: the number of the call's draws with a finite
+ *   s_j <= thr[r]; 0 on rows without a state (a track's first row, one-row tracks).  The call overwrites it.  Counts of disjoint draw
+ *   ranges add up exactly on the host.
+ * Either output may be NULL, not both; row_below must be NULL when n_thr = 0.  thr [n_thr] host memory: each >= 0, +inf allowed, in
+ * any order.
+ * NaN in every statistic of every draw of a track without a state row, and in every statistic of a (track, draw) with a non-finite
+ * velocity column on a state row; a non-finite s_j is counted in no row_below entry.
+ * SSDE_ERR_ARG for NULL h / par, stats and row_below both NULL, n_draws < 1, draw0 < 0, draw0 + n_draws >= 2^28, n_thr outside
+ * 0 .. SSDE_SPEED_MAX_THR, thr NULL with n_thr > 0, a threshold that is NaN or < 0, row_below non-NULL with n_thr = 0, flags != 0.
+ * SSDE_ERR_MODEL for OU_SSM and BM_SSM (their state holds no velocity) and wherever ssde_path_stats gives it (the direct families,
+ * ESEAL_SSM, n_dim > 2).  Every check runs before anything touches the device.  Multi-device handles, lattice-padded handles, PATH_TV
+ * handles, SSDE_FLAG_FORCE_DENSE, per-row H_array and a general P0 are served.  Leaves the memo, the window state, the TV records,
+ * n_evals / n_memo_hits and every later result of every other call as they were.  The result is bitwise independent of
+ * SSDE_OPT_SMOOTH_BUDGET_MB, the devices, how the draws are batched and repeated calls; stats of a draw range cut over calls is bitwise
+ * the whole range's, and stats / row_below are the same numbers whether asked for alone or together. */
+#define SSDE_SPEED_MAX_THR 8
+int ssde_path_speed(ssde_handle *h, const double *par, int32_t n_par_full, uint64_t seed, int64_t draw0, int32_t n_draws,
+                    const double *thr, int32_t n_thr, const double *weight, double *stats, uint32_t *row_below, uint32_t flags);
 
 /* Occupancy grids of posterior state paths at `par`, summed on the device (definitions: DESIGN.md §3.13).  Draws, state rows and
  * position columns are exactly those of ssde_path_stats: draw q is draw number draw0 + q of the stream `seed`, the path

@@ -504,6 +504,9 @@ def load_library():
     lib.ssde_predict_draws.restype = C.c_int
     lib.ssde_path_stats.argtypes = [C.c_void_p, _dp, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, _dp, C.c_int32, _dp, _dp, C.c_uint32]
     lib.ssde_path_stats.restype = C.c_int
+    lib.ssde_path_speed.argtypes = [C.c_void_p, _dp, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, _dp, C.c_int32, _dp, _dp,
+                                    C.POINTER(C.c_uint32), C.c_uint32]
+    lib.ssde_path_speed.restype = C.c_int
     lib.ssde_path_occupancy.argtypes = [C.c_void_p, _dp, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.POINTER(SsdeOccGrid), _dp,
                                         C.POINTER(C.c_int32), C.c_int32, _dp, _dp, C.c_uint32]
     lib.ssde_path_occupancy.restype = C.c_int
@@ -598,6 +601,7 @@ class EngineError(RuntimeError):
 
 
 PATH_MAX_REGIONS = 8   # SSDE_PATH_MAX_REGIONS (include/ssde.h)
+SPEED_MAX_THR = 8      # SSDE_SPEED_MAX_THR: the most thresholds of one ssde_path_speed
 DRAWS_DEVICE_OUT = 1   # ssde_smooth_draws flag: `draws` is an HBM pointer on the handle's device (include/ssde.h)
 OCC_FORCE_GLOBAL = 1   # ssde_path_occupancy flag: every wavefront group runs the global form (SSDE_OCC_FORCE_GLOBAL)
 PROX_MAX_RADII = 8     # SSDE_PROX_MAX_RADII: the most radii of one ssde_path_proximity
@@ -607,7 +611,7 @@ WINDOW_TOL = 1e-11  # largest tolerated relative hand-over disagreement between 
 
 EXPORTED_SYMBOLS = ("ssde_create", "ssde_eval", "ssde_eval_device", "ssde_penalty", "ssde_report", "ssde_widen_windows", "ssde_relax_windows",
                     "ssde_info", "ssde_destroy", "ssde_last_error", "ssde_abi_version", "ssde_comm_unique_id", "ssde_comm_init_rank", "ssde_forget", "ssde_laplace_eval", "ssde_last_kernel_ms", "ssde_kernel_ms_history",
-                    "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth", "ssde_smooth_draws", "ssde_predict", "ssde_predict_draws", "ssde_path_stats", "ssde_path_occupancy", "ssde_last_occupancy_form", "ssde_path_occupancy_fine", "ssde_last_occupancy_points", "ssde_last_hess_plan", "ssde_path_proximity", "ssde_last_proximity_plan",
+                    "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth", "ssde_smooth_draws", "ssde_predict", "ssde_predict_draws", "ssde_path_stats", "ssde_path_speed", "ssde_path_occupancy", "ssde_last_occupancy_form", "ssde_path_occupancy_fine", "ssde_last_occupancy_points", "ssde_last_hess_plan", "ssde_path_proximity", "ssde_last_proximity_plan",
                     "ssde_lagstats_host_m", "ssde_lagstats_read_m", "ssde_lagforms_host_m", "ssde_reduce_host", "ssde_last_finish_form", "ssde_last_gain_feed", "ssde_last_gain_rows",
                     "ssde_lagstats_host_cut", "ssde_lagstats_read_cut", "ssde_last_lag_cut")
 
@@ -1086,6 +1090,37 @@ class Engine:
                                              reg.ctypes.data_as(_dp) if len(reg) else None, len(reg),
                                              None if w is None else w.ctypes.data_as(_dp), buf.ctypes.data_as(_dp), 0))
         return buf.transpose(0, 2, 1)
+
+    def path_speed(self, par, n_draws: int, seed: int = 0, draw0: int = 0, thresholds=None, weight=None, rows: bool = True):
+        """Speed along posterior state paths of a CTCRW at `par`, reduced on the device (ssde_path_speed):
+        (stats, row_below).  stats has shape (n_draws, n_tracks, n_stat), n_stat = 5 + n_thr -- the weighted sum of the speeds over
+        the track's state rows, the largest speed, the row of the data (0-based) that attains it, the two components of the
+        resultant sum of w v / |v|, then per threshold the sum of `weight` over the state rows with a speed at or below it.
+        row_below has shape (n, n_thr), dtype uint32: per row of the data the number of the call's draws with a finite speed at or
+        below each threshold (0 on rows without a state); None when `rows` is False or there is no threshold.  Draw k is draw
+        number draw0 + k of the stream `seed`, the path smooth_draws returns for it.  `thresholds`: at most SPEED_MAX_THR numbers
+        >= 0 (+inf allowed) or None; `weight`: one number per row of the data, or None for 1.  NaN for a one-row track and for a
+        (track, draw) with a non-finite velocity."""
+        par = np.ascontiguousarray(par, dtype=np.float64)
+        if par.shape != (self.n_par_full,):
+            raise ValueError(f"par must have length {self.n_par_full}")
+        thr = np.zeros(0) if thresholds is None else np.ascontiguousarray(thresholds, dtype=np.float64)
+        if thr.ndim != 1:
+            raise ValueError("thresholds must be a list of numbers")
+        w = None
+        if weight is not None:
+            w = np.ascontiguousarray(weight, dtype=np.float64)
+            if w.shape != (self.problem.n,):
+                raise ValueError("weight must hold one number per row of the data")
+        n_stat = 5 + len(thr)
+        n, n_trk = self.problem.n, self.problem.n_seg
+        buf = np.zeros((max(int(n_draws), 0), n_stat, n_trk))                          # element (t, k, q) at t + n_tracks (k + n_stat q)
+        cnt = np.zeros((len(thr), n), dtype=np.uint32) if (rows and len(thr)) else None   # element (j, r) at j + n r
+        self._check(self.lib.ssde_path_speed(self._h, par.ctypes.data_as(_dp), self.n_par_full, int(seed), int(draw0), int(n_draws),
+                                             thr.ctypes.data_as(_dp) if len(thr) else None, len(thr),
+                                             None if w is None else w.ctypes.data_as(_dp), buf.ctypes.data_as(_dp),
+                                             None if cnt is None else cnt.ctypes.data_as(C.POINTER(C.c_uint32)), 0))
+        return buf.transpose(0, 2, 1), (None if cnt is None else cnt.T)
 
     def path_occupancy(self, par, n_draws: int, grid, seed: int = 0, draw0: int = 0, weight=None, group=None, n_groups=None,
                        force_global: bool = False):

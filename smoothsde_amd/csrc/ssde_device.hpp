@@ -729,6 +729,26 @@ struct PathArgs {
     double regions[SSDE_PATH_MAX_REGIONS * 4];   // lo_1, hi_1, lo_2, hi_2 per region
 };
 hipError_t launch_path_stats(const PathArgs& a, hipStream_t s);
+// ---- speed along the drawn paths (k_path_speed.hip, ssde_speed.hpp) ----
+// The draws of a DrawArgs `d` (its out / draw_stride are not read; a CTCRW of one or two response columns), reduced in registers to
+// n_stat = 5 + n_thr numbers per (track, draw), placed as PathArgs' statistics, and counted per row: the batch's draws with a finite
+// speed <= thr[r] at the caller's row j ADDED to row_below + j + n_rows * r.  Either output may be NULL.  The thresholds travel by
+// value (64 B of uniform operands).
+#ifndef SSDE_SPEED_MAX_THR
+#define SSDE_SPEED_MAX_THR 8
+#endif
+struct SpeedArgs {
+    DrawArgs d;
+    const int64_t* row_map;      // as PathArgs
+    const double* weight;        // as PathArgs
+    double* stats;               // [n_trk x n_stat x n_draws] or NULL
+    uint32_t* row_below;         // [n_rows x n_thr], zeroed once per call, or NULL
+    int64_t n_trk;               // the handle's ID segments
+    int64_t n_rows;              // the caller's rows
+    int n_thr;
+    double thr[SSDE_SPEED_MAX_THR];
+};
+hipError_t launch_path_speed(const SpeedArgs& a, hipStream_t s);
 // map[pos[i]] = i for the caller's rows i < n, -1 on the other lattice rows (np of them)
 hipError_t launch_path_row_map(const int64_t* pos, int64_t n, int64_t np, int64_t* map, hipStream_t s);
 // ---- occupancy grids of the drawn paths (k_path_occ.hip, ssde_occ.hpp) ----

@@ -3,7 +3,8 @@
 // state between and after the rows from them, and ssde_path_stats / ssde_path_occupancy: reductions of the drawn paths
 // on the device, and ssde_predict_draws: the drawn paths refined between and after the rows,
 // and ssde_path_occupancy_fine: the occupancy grids of the refined paths, and ssde_path_proximity: those states of
-// two tracks paired and reduced per pair and draw.
+// two tracks paired and reduced per pair and draw, and ssde_path_speed: the speed along the drawn paths of a CTCRW
+// reduced per track and draw and counted per row.
 //
 // A forward pass in record mode (dense_kernel MODE 2 on the tiled routes, smooth_tv_record_kernel on PATH_TV) writes every state
 // row's record, smooth_back_kernel walks them back and writes the smoothed mean, covariance and whitened innovation in the long
@@ -311,6 +312,90 @@ int path_sharded(ssde_handle* parent, const double* par, uint64_t seed, int64_t 
         int st = path_single(sh, par, seed, draw0, n_draws, regions, n_regions, weight ? weight + lo : nullptr, t.data(), track0);
         if (st) { parent->err = sh->err; return st; }
         for (int64_t q = 0; q < (int64_t)n_stat * n_draws; q++) memcpy(stats + (size_t)N * q + track0, t.data() + (size_t)m * q, (size_t)m * 8);
+        track0 += m;
+    }
+    return SSDE_OK;
+}
+
+// ---- ssde_path_speed ----------------------------------------------------------------------------------------------------------
+// One engine's speed statistics [n_seg x n_stat x n_draws] and per-row counts [n x n_thr] into host memory (either may be NULL):
+// path_single's run -- the same records, batches under the same budget rule, weights and lattice map -- with k_path_speed.hip's
+// kernel.  The counts are one device table of the engine's own caller rows, zeroed once per call, added to by every chunk and batch
+// and copied home once; its bytes are taken off the budget before the batches are sized.
+int speed_single(ssde_handle* h, const double* par, uint64_t seed, int64_t draw0, int n_draws, const double* thr, int n_thr,
+                 const double* weight, double* stats, uint32_t* row_below, int64_t track0) {
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(0));
+    RecordRun run;
+    if (int st = run.setup(h, par, "ssde_path_speed")) return st;
+    const int64_t nt = run.nt, n = h->n, n_trk = h->n_seg;
+    const int n_stat = 5 + n_thr;
+    if ((int64_t)h->lane_seg.n < run.n_lanes) { h->err = "ssde_path_speed: the handle holds no track ordinals for its lanes"; return SSDE_ERR_ARG; }
+    if (n_trk == 0 || n == 0) return SSDE_OK;
+    DevBuf<double> sb, wb;
+    DevBuf<uint32_t> cb;
+    DevBuf<int64_t> map;
+    Release guard(sb, wb, cb, map);
+    const size_t n_cnt = row_below ? (size_t)n * n_thr : 0;
+    // draws per batch: what fits the run's budget beside the records and the counts, in whole waves of DRAW_CH draws (one wave's
+    // draws always go); a call without statistics keeps nothing per draw
+    const size_t per_draw = stats ? (size_t)n_trk * n_stat : 0;
+    const int64_t left = std::max<int64_t>(run.budget - (int64_t)((n_cnt * 4 + 7) / 8), 0);
+    const int nb_cap = batch_cap(left, (int64_t)per_draw, DRAW_CH, DRAW_CH, n_draws);
+    if (stats) HIPCHK(h, sb.alloc(per_draw * nb_cap));
+    if (n_cnt) { HIPCHK(h, cb.alloc(n_cnt)); HIPCHK(h, hipMemset(cb.p, 0, n_cnt * 4)); }
+    if (weight) HIPCHK(h, wb.upload(std::vector<double>(weight, weight + n)));
+    SpeedArgs a;
+    memset(&a, 0, sizeof(a));
+    if (nt != n) {                                                      // the caller's row OF each lattice row
+        HIPCHK(h, map.alloc((size_t)nt));
+        HIPCHK(h, launch_path_row_map(h->pad_row.p, n, nt, map.p, 0));
+        a.row_map = map.p;
+    }
+    a.d.lane_trk = h->lane_seg.p; a.d.track0 = track0; a.d.seed = seed; a.d.col0 = 0;
+    a.weight = weight ? wb.p : nullptr;
+    a.stats = stats ? sb.p : nullptr; a.row_below = n_cnt ? cb.p : nullptr;
+    a.n_trk = n_trk; a.n_rows = n; a.n_thr = n_thr;
+    for (int k = 0; k < n_thr; k++) a.thr[k] = thr[k];
+    for (int k0 = 0; k0 < n_draws; k0 += nb_cap) {
+        const int nb = std::min(nb_cap, n_draws - k0);
+        if (stats) HIPCHK(h, hipMemset(sb.p, 0xff, per_draw * nb * 8));   // NaN (all bits set) where no lane writes
+        a.d.draw0 = (uint32_t)(draw0 + k0); a.d.n_draws = nb;
+        for (size_t c = 0; c < run.n_chunks(); c++) {
+            if (int st = run.produce_for_batch(c)) return st;
+            a.d.s = run.s;
+            HIPCHK(h, launch_path_speed(a, 0));
+        }
+        if (stats) HIPCHK(h, hipMemcpy(stats + per_draw * k0, sb.p, per_draw * nb * 8, hipMemcpyDeviceToHost));
+    }
+    if (n_cnt) HIPCHK(h, hipMemcpy(row_below, cb.p, n_cnt * 4, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipStreamSynchronize(0));
+    return SSDE_OK;
+}
+
+// the track shards' speeds: each shard reads its own slice of the weights, counts its deviates by the GLOBAL track ordinal and lands
+// at its tracks' places in the parent's statistics and at its rows' places in the parent's counts; the row of a maximum, which a
+// shard counts in its own rows, is moved to the parent's rows
+int speed_sharded(ssde_handle* parent, const double* par, uint64_t seed, int64_t draw0, int n_draws, const double* thr, int n_thr,
+                  const double* weight, double* stats, uint32_t* row_below) {
+    const int64_t N = parent->n_seg, n = parent->n;
+    const int n_stat = 5 + n_thr;
+    if (stats) std::fill(stats, stats + (size_t)N * n_stat * n_draws, std::numeric_limits<double>::quiet_NaN());
+    if (row_below) std::fill(row_below, row_below + (size_t)n * n_thr, 0u);
+    int64_t track0 = 0;
+    for (size_t k = 0; k < parent->shards.size(); k++) {
+        ssde_handle* sh = parent->shards[k];
+        const int64_t lo = parent->shard_row0[k], m = sh->n_seg, mr = sh->n;
+        std::vector<double> t(stats ? (size_t)m * n_stat * n_draws : 0);
+        std::vector<uint32_t> tc(row_below ? (size_t)mr * n_thr : 0, 0u);
+        int st = speed_single(sh, par, seed, draw0, n_draws, thr, n_thr, weight ? weight + lo : nullptr, stats ? t.data() : nullptr,
+                              row_below ? tc.data() : nullptr, track0);
+        if (st) { parent->err = sh->err; return st; }
+        for (int64_t q = 0; stats && q < (int64_t)n_stat * n_draws; q++) memcpy(stats + (size_t)N * q + track0, t.data() + (size_t)m * q, (size_t)m * 8);
+        // (the row of the maximum was counted in the shard's rows: whole numbers below 2^53, so adding the shard's first row is exact)
+        for (int q = 0; stats && q < n_draws; q++)
+            for (int64_t i = 0; i < m; i++) stats[(size_t)N * (2 + (size_t)n_stat * q) + track0 + i] += (double)lo;
+        for (int r = 0; row_below && r < n_thr; r++) memcpy(row_below + (size_t)n * r + lo, tc.data() + (size_t)mr * r, (size_t)mr * 4);
         track0 += m;
     }
     return SSDE_OK;
@@ -1049,6 +1134,32 @@ int ssde_path_stats(ssde_handle* h, const double* par, int32_t n_par_full, uint6
     }
     if (!h->shards.empty()) return path_sharded(h, par, seed, draw0, n_draws, regions, n_regions, weight, stats);
     return path_single(h, par, seed, draw0, n_draws, regions, n_regions, weight, stats, 0);
+}
+
+int ssde_path_speed(ssde_handle* h, const double* par, int32_t n_par_full, uint64_t seed, int64_t draw0, int32_t n_draws,
+                    const double* thr, int32_t n_thr, const double* weight, double* stats, uint32_t* row_below, uint32_t flags) {
+    if (!h || !par || (!stats && !row_below)) { if (h) h->err = "ssde_path_speed: no parameter vector, or no output"; return SSDE_ERR_ARG; }
+    if (int st = check_par_len(h, n_par_full)) return st;
+    if (n_draws < 1 || draw0 < 0 || draw0 + (int64_t)n_draws >= ((int64_t)1 << 28)) {
+        h->err = "ssde_path_speed: n_draws >= 1, draw0 >= 0 and draw0 + n_draws < 2^28 are required";
+        return SSDE_ERR_ARG;
+    }
+    if (n_thr < 0 || n_thr > SSDE_SPEED_MAX_THR || (n_thr > 0 && !thr)) {
+        h->err = "ssde_path_speed: 0 <= n_thr <= SSDE_SPEED_MAX_THR, with a table of thresholds when there are any";
+        return SSDE_ERR_ARG;
+    }
+    for (int k = 0; k < n_thr; k++)
+        if (std::isnan(thr[k]) || thr[k] < 0.0) { h->err = "ssde_path_speed: a threshold that is NaN or negative"; return SSDE_ERR_ARG; }
+    if (row_below && n_thr == 0) { h->err = "ssde_path_speed: per-row counts need a threshold"; return SSDE_ERR_ARG; }
+    if (flags != 0) { h->err = "ssde_path_speed: unknown flag"; return SSDE_ERR_ARG; }
+    if (int st = check_kalman(h)) return st;
+    if (h->model != SSDE_MODEL_CTCRW) { h->err = "ssde_path_speed: the state of OU_SSM and BM_SSM holds no velocity (a CTCRW's does)"; return SSDE_ERR_MODEL; }
+    if (h->d > 2) {
+        h->err = "ssde_path_speed: a response of three or more columns is not served, as column pairs or as one coupled filter (a speed needs the velocity columns in one lane)";
+        return SSDE_ERR_MODEL;
+    }
+    if (!h->shards.empty()) return speed_sharded(h, par, seed, draw0, n_draws, thr, n_thr, weight, stats, row_below);
+    return speed_single(h, par, seed, draw0, n_draws, thr, n_thr, weight, stats, row_below, 0);
 }
 
 // what ssde_path_occupancy and ssde_path_occupancy_fine check alike, before anything touches the device; wmax: the largest weight (1

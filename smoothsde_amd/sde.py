@@ -575,6 +575,34 @@ class SDE:
         st = self.engine_.path_stats(self._current_par_full(), n_draws, seed=seed, regions=regions, weight=weight)
         return {"length": st[:, :, 0], "displacement": st[:, :, 1], "in_region": st[:, :, 2:]}
 
+    def speed_summary(self, n_draws, seed=0, thresholds=None, weight="dt"):
+        """The speed |v| along the posterior state paths of a CTCRW at the current parameters, reduced on the device
+        (ssde_path_speed): no draw comes home.  {"mean_speed": (n_draws, n_tracks) the weighted mean of the speed
+        over the track's state rows, "max_speed": (n_draws, n_tracks), "max_row": (n_draws, n_tracks) the row of the data that
+        attains it, "persistence": (n_draws, n_tracks) the length of the weighted resultant of the headings over the sum of the
+        weights (1: one heading throughout), "time_below": (n_draws, n_tracks, n_thr) weighted rows at or below each threshold,
+        "p_below": (n, n_thr) per row of the data the share of the draws at or below each threshold, NaN on rows without a state}.
+        `weight` as path_summary's: "dt" makes mean_speed a time average and time_below a time.  The draws are those of
+        sample_states(n_draws, seed).  A model other than the CTCRW raises the engine's model error: no other state holds a
+        velocity."""
+        if isinstance(weight, str):
+            if weight != "dt":
+                raise ValueError('weight must be "dt", an array or None')
+            weight = self._dt_weights()
+        thr = np.zeros(0) if thresholds is None else np.asarray(thresholds, dtype=np.float64).ravel()
+        st, below = self.engine_.path_speed(self._current_par_full(), n_draws, seed=seed, thresholds=thr, weight=weight)
+        pb = self.problem_
+        w = np.ones(pb.n) if weight is None else np.asarray(weight, dtype=np.float64)
+        has_state = np.ones(pb.n, dtype=bool)
+        has_state[np.asarray(pb.seg_start, dtype=np.int64)] = False
+        wsum = np.add.reduceat(np.where(has_state, w, 0.0), np.asarray(pb.seg_start, dtype=np.int64))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            p_below = np.full((pb.n, len(thr)), np.nan)
+            if below is not None:
+                p_below[has_state] = below[has_state] / float(n_draws)
+            return {"mean_speed": st[:, :, 0] / wsum[None, :], "max_speed": st[:, :, 1], "max_row": st[:, :, 2],
+                    "persistence": np.hypot(st[:, :, 3], st[:, :, 4]) / wsum[None, :], "time_below": st[:, :, 5:], "p_below": p_below}
+
     def _dt_weights(self):
         """the time from a row to its track's next row, 0 at a track's last row"""
         ids, t = np.asarray(self.data_["ID"]), np.asarray(self.data_["time"], dtype=np.float64)
