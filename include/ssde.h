@@ -723,6 +723,64 @@ typedef struct ssde_sim_desc {
 } ssde_sim_desc;
 int ssde_simulate(const ssde_sim_desc *desc, double *id_dev, double *times_dev, double *obs_dev, void *stream);
 
+/* Confidence bands of the SDE parameters (SDE$post_par / CI_pointwise / CI_simultaneous, R/sde.R:941-1180) from a table of
+ * posterior coefficient draws, reduced on the device: the n x n_post matrix of a parameter's draws is never built.
+ * A descriptor call like ssde_simulate: no handle.
+ *   n rows and n_par parameters.  Parameter j has a fixed-effect block x_fe[j] (n x ncol_fe[j], column-major; NULL with
+ *   ncol_fe[j] == 1 = a column of ones) and a random-effect block x_re[j] (n x ncol_re[j], NULL for 0 columns): the block
+ *   convention of ssde_desc.  K_j = ncol_fe[j] + ncol_re[j], n_coef = sum_j K_j.
+ *   coeff     [(1 + n_post) x n_coef] row-major, host memory: row 0 the point estimate, rows 1 .. n_post the draws; parameter j's
+ *             K_j entries contiguous, fixed effects first
+ *   link[j]   0 identity, 1 log.  level in (0, 1), alpha = (1 - level) / 2; z = the caller's qnorm((1 + level) / 2).
+ * lp(i, j, k) = sum_c X_j[i, c] coeff[k, off_j + c], summed in column order (fixed-effect columns, then random-effect columns) as
+ * one fma chain.  Q(x, p) is R's type-7 quantile of the sorted x[0 .. m): h = (m - 1) p, lo = floor(h), hi = min(lo + 1, m - 1),
+ * Q = x[lo] + (h - lo)(x[hi] - x[lo]) (x[lo] itself where x[hi] == x[lo]); equal values count with their multiplicity.
+ * Outputs, each n x n_par column-major, each may be NULL:
+ *   est               lp(i, j, 0), through the inverse link when resp != 0
+ *   pw_low, pw_upp    Q at alpha and 1 - alpha of {g(lp(i, j, k))}, k = 1 .. n_post; g the inverse link when resp != 0 (applied to
+ *                     the two order statistics before the interpolation), else the identity
+ *   sim_low, sim_upp  g(lp(i, j, 0) -+ crit[j] se(i, j)) with se = (lp(i, j, 0) - Q_lp(alpha)) / z on the link scale
+ * and, always host memory, may be NULL:
+ *   max_dev  [n_par x n_post] row-major: max_i |dev(i, j, k) / se(i, j)|, dev the dot product with coeff[k] - coeff[0]; 0 / 0 counts
+ *            as 0, x / 0 = inf is kept (R/sde.R:1155-1159)
+ *   crit     [n_par]: Q(max_dev[j, .], level), NaN -> 0
+ * ONE table serves se and the deviations; the reference draws twice inside CI_simultaneous (R/sde.R:1112, 1119).
+ * Where any lp(i, j, k), k = 0 .. n_post, is not finite every output of (i, j) is NaN and the row adds nothing to max_dev.
+ * Each tail needs floor((n_post - 1) alpha) + 2 order statistics (the upper one the mirror count); both must be <=
+ * SSDE_BANDS_MAX_TAIL.  With sim_low, sim_upp, crit and max_dev all NULL only the first pass runs.
+ * Host blocks are uploaded in chunks of whole rows under budget_mb MiB (0 = a quarter of the free device memory); the result is
+ * bitwise independent of the chunking.  Synchronous; one device.
+ * SSDE_ERR_ARG -- before anything touches the device; the text through ssde_last_error(NULL) -- for a NULL desc, every output NULL,
+ * a wrong abi_version, n < 1, n_par outside 1 .. SSDE_BANDS_MAX_PAR, a K_j outside 1 .. SSDE_BANDS_MAX_COLS, a NULL block that is
+ * not the intercept case, a link other than 0 / 1, n_post < 2, level outside (0, 1), z not finite or <= 0, a tail over the cap, a
+ * coeff entry that is not finite, an unknown flag. */
+#define SSDE_BANDS_MAX_TAIL 64
+#define SSDE_BANDS_MAX_COLS 64     /* K_j */
+#define SSDE_BANDS_MAX_PAR  16     /* n_par */
+#define SSDE_BANDS_DEVICE_DATA 1u  /* x_fe / x_re blocks are HBM pointers on `device` */
+#define SSDE_BANDS_DEVICE_OUT  2u  /* the n x n_par outputs are HBM pointers; crit / max_dev are always host */
+typedef struct ssde_bands_desc {
+    int32_t  abi_version;     /* SSDE_ABI_VERSION */
+    int32_t  n_par;
+    int64_t  n;
+    const int32_t *ncol_fe;
+    const double *const *x_fe;
+    const int32_t *ncol_re;
+    const double *const *x_re;
+    const uint8_t *link;
+    const double *coeff;
+    int32_t  n_post;
+    int32_t  resp;
+    double   level;
+    double   z;
+    int32_t  device;          /* HIP device ordinal, -1 = current device */
+    int32_t  budget_mb;
+    uint32_t flags;
+    uint32_t reserved;
+} ssde_bands_desc;
+int ssde_par_bands(const ssde_bands_desc *d, double *est, double *pw_low, double *pw_upp,
+                   double *sim_low, double *sim_upp, double *crit, double *max_dev);
+
 void ssde_destroy(ssde_handle *h);
 
 /* Message of the last failure on this handle (or of the last failed ssde_create when h == NULL). */

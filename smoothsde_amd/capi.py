@@ -77,6 +77,14 @@ class SsdeSimDesc(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class SsdeBandsDesc(C.Structure):
+    _fields_ = [("abi_version", C.c_int32), ("n_par", C.c_int32), ("n", C.c_int64),
+                ("ncol_fe", C.POINTER(C.c_int32)), ("x_fe", C.POINTER(C.c_void_p)), ("ncol_re", C.POINTER(C.c_int32)),
+                ("x_re", C.POINTER(C.c_void_p)), ("link", C.POINTER(C.c_uint8)), ("coeff", C.POINTER(C.c_double)),
+                ("n_post", C.c_int32), ("resp", C.c_int32), ("level", C.c_double), ("z", C.c_double),
+                ("device", C.c_int32), ("budget_mb", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 OPT_KERNEL_STAMPS, OPT_COMM_DEFER, OPT_SMOOTH_BUDGET_MB, OPT_LAG_EARLY = 1, 2, 3, 4
 LAG_CUTS = tuple(range(32, 129, 16))   # the early cuts of the lag statistics (csrc/ssde_lagstats.hpp)
 # ssde_info_t.kernel_id (include/ssde.h: SSDE_KERNEL_*): the kernel family that ran the rows of the last evaluation
@@ -581,6 +589,8 @@ def load_library():
     lib.ssde_comm_init_rank.restype = C.c_int
     lib.ssde_simulate.argtypes = [C.POINTER(SsdeSimDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ssde_simulate.restype = C.c_int
+    lib.ssde_par_bands.argtypes = [C.POINTER(SsdeBandsDesc)] + [C.c_void_p] * 7
+    lib.ssde_par_bands.restype = C.c_int
     lib.ssde_hess.argtypes = [C.c_void_p, _dp, C.c_int32, _ip, C.c_int32, _dp]
     lib.ssde_hess.restype = C.c_int
     lib.ssde_set_option.argtypes = [C.c_void_p, C.c_int32, C.c_int64]
@@ -605,13 +615,15 @@ SPEED_MAX_THR = 8      # SSDE_SPEED_MAX_THR: the most thresholds of one ssde_pat
 DRAWS_DEVICE_OUT = 1   # ssde_smooth_draws flag: `draws` is an HBM pointer on the handle's device (include/ssde.h)
 OCC_FORCE_GLOBAL = 1   # ssde_path_occupancy flag: every wavefront group runs the global form (SSDE_OCC_FORCE_GLOBAL)
 PROX_MAX_RADII = 8     # SSDE_PROX_MAX_RADII: the most radii of one ssde_path_proximity
+BANDS_MAX_TAIL, BANDS_MAX_COLS, BANDS_MAX_PAR = 64, 64, 16   # SSDE_BANDS_MAX_*: order statistics of a tail, columns of a parameter, parameters
+BANDS_DEVICE_DATA, BANDS_DEVICE_OUT = 1, 2                  # ssde_par_bands flags: the blocks / the n x q outputs are HBM pointers
 OCC_MAX_SUB = 64       # SSDE_OCC_MAX_SUB: the most sub-steps ssde_path_occupancy_fine cuts an interval into
 
 WINDOW_TOL = 1e-11  # largest tolerated relative hand-over disagreement between time windows
 
 EXPORTED_SYMBOLS = ("ssde_create", "ssde_eval", "ssde_eval_device", "ssde_penalty", "ssde_report", "ssde_widen_windows", "ssde_relax_windows",
                     "ssde_info", "ssde_destroy", "ssde_last_error", "ssde_abi_version", "ssde_comm_unique_id", "ssde_comm_init_rank", "ssde_forget", "ssde_laplace_eval", "ssde_last_kernel_ms", "ssde_kernel_ms_history",
-                    "ssde_simulate", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth", "ssde_smooth_draws", "ssde_predict", "ssde_predict_draws", "ssde_path_stats", "ssde_path_speed", "ssde_path_occupancy", "ssde_last_occupancy_form", "ssde_path_occupancy_fine", "ssde_last_occupancy_points", "ssde_last_hess_plan", "ssde_path_proximity", "ssde_last_proximity_plan",
+                    "ssde_simulate", "ssde_par_bands", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth", "ssde_smooth_draws", "ssde_predict", "ssde_predict_draws", "ssde_path_stats", "ssde_path_speed", "ssde_path_occupancy", "ssde_last_occupancy_form", "ssde_path_occupancy_fine", "ssde_last_occupancy_points", "ssde_last_hess_plan", "ssde_path_proximity", "ssde_last_proximity_plan",
                     "ssde_lagstats_host_m", "ssde_lagstats_read_m", "ssde_lagforms_host_m", "ssde_reduce_host", "ssde_last_finish_form", "ssde_last_gain_feed", "ssde_last_gain_rows",
                     "ssde_lagstats_host_cut", "ssde_lagstats_read_cut", "ssde_last_lag_cut")
 
@@ -781,6 +793,108 @@ def simulate_device(model: str, n_tracks: int, n_steps: int, n_dim: int = 2, *, 
         msg = lib.ssde_last_error(None)
         raise EngineError(f"ssde_simulate failed ({st}): {msg.decode() if msg else ''}")
     return ID, times, obs.t()
+
+
+
+def par_bands(X_fe, X_re, link, coeff, level=0.95, resp=True, simultaneous=True, device_out=False, budget_mb=0, *, z=None,
+              want=None, device=None):
+    """ssde_par_bands: pointwise and simultaneous confidence bands of the SDE parameters from a table of posterior
+    coefficient draws, reduced on the device.  `X_fe`, `X_re`: one block per parameter, (n, k) numpy arrays or device tensors (all of
+    one kind) or None (the intercept / no random effects); `link`: 0 identity, 1 log per parameter; `coeff`: (1 + n_post, n_coef),
+    row 0 the point estimate, parameter j's columns contiguous, fixed effects first.  Returns {"est", "pw_low", "pw_upp"} (n, q) and,
+    with `simultaneous`, {"sim_low", "sim_upp"} (n, q), "crit" (q,), "max_dev" (q, n_post); the (n, q) entries are device tensors
+    with `device_out`.  `want`: the names of the outputs to compute (None: all that `simultaneous` allows).  `z` defaults to the
+    normal quantile of (1 + level) / 2."""
+    import statistics
+    lib = load_library()
+    q = len(X_fe)
+    if len(X_re) != q or len(link) != q:
+        raise ValueError("par_bands: one entry per parameter in X_fe, X_re and link")
+    blocks = [b for b in list(X_fe) + list(X_re) if b is not None]
+    on_dev = [hasattr(b, "data_ptr") for b in blocks]
+    if any(on_dev) and not all(on_dev):
+        raise ValueError("par_bands: the blocks are all numpy arrays or all device tensors")
+    dev_data = bool(blocks) and all(on_dev)
+    torch = None
+    if dev_data or device_out:
+        import torch
+    keep, n = [], None
+
+    def block(b):
+        nonlocal n
+        if b is None:
+            return None, 0
+        if dev_data:
+            if b.dtype != torch.float64 or b.dim() != 2:
+                raise ValueError("par_bands: device blocks are 2-d float64 tensors")
+            t = b.t().contiguous()                       # column-major (n, k) = row-major (k, n)
+            keep.append(t)
+            rows, cols, p = int(b.shape[0]), int(b.shape[1]), t.data_ptr()
+        else:
+            a = np.asfortranarray(np.asarray(b, dtype=np.float64))
+            if a.ndim != 2:
+                raise ValueError("par_bands: a block is an (n, k) array")
+            keep.append(a)
+            rows, cols, p = a.shape[0], a.shape[1], a.ctypes.data
+        if n is not None and rows != n:
+            raise ValueError("par_bands: blocks with different numbers of rows")
+        n = rows
+        return p, cols
+
+    pf = [block(b) for b in X_fe]
+    pr = [block(b) for b in X_re]
+    cf = np.ascontiguousarray(coeff, dtype=np.float64)
+    if cf.ndim != 2:
+        raise ValueError("par_bands: coeff is (1 + n_post, n_coef)")
+    if n is None:
+        n = 1                                              # intercepts only: one row says it all
+    kf = np.array([1 if p is None else k for p, k in pf], dtype=np.int32)
+    kr = np.array([k for _, k in pr], dtype=np.int32)
+    if int(kf.sum() + kr.sum()) != cf.shape[1]:
+        raise ValueError("par_bands: coeff has not one column per design column")
+    xf = (C.c_void_p * q)(*[p for p, _ in pf])
+    xr = (C.c_void_p * q)(*[(p if k else None) for p, k in pr])
+    lk = np.ascontiguousarray(link, dtype=np.uint8)
+    d = SsdeBandsDesc()
+    d.abi_version, d.n_par, d.n = ABI_VERSION, q, n
+    d.ncol_fe, d.x_fe = kf.ctypes.data_as(C.POINTER(C.c_int32)), xf
+    d.ncol_re, d.x_re = kr.ctypes.data_as(C.POINTER(C.c_int32)), xr
+    d.link, d.coeff = lk.ctypes.data_as(C.POINTER(C.c_uint8)), cf.ctypes.data_as(_dp)
+    d.n_post, d.resp, d.level = cf.shape[0] - 1, 1 if resp else 0, float(level)
+    d.z = float(z) if z is not None else (statistics.NormalDist().inv_cdf((1.0 + float(level)) / 2.0) if 0.0 < float(level) < 1.0 else float("nan"))
+    d.budget_mb = int(budget_mb)
+    d.flags = (BANDS_DEVICE_DATA if dev_data else 0) | (BANDS_DEVICE_OUT if device_out else 0)
+    if torch is not None:
+        dv = blocks[0].device if dev_data else (torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device))
+        d.device = int(dv.index or 0)
+    else:
+        d.device = -1 if device is None else int(device)
+    row_names = ["est", "pw_low", "pw_upp"] + (["sim_low", "sim_upp"] if simultaneous else [])
+    names = row_names + (["crit", "max_dev"] if simultaneous else [])
+    if want is not None:
+        if any(w not in names for w in want):
+            raise ValueError(f"par_bands: want is a subset of {names}")
+        names = [w for w in names if w in want]
+    out, ptrs = {}, {}
+    for nm in names:
+        if nm == "crit":
+            out[nm] = np.zeros(q)
+        elif nm == "max_dev":
+            out[nm] = np.zeros((q, max(d.n_post, 0)))
+        elif device_out:
+            out[nm] = torch.empty((q, n), dtype=torch.float64, device=dv)
+        else:
+            out[nm] = np.zeros((q, n))
+        ptrs[nm] = out[nm].data_ptr() if hasattr(out[nm], "data_ptr") else out[nm].ctypes.data
+    if torch is not None:
+        torch.cuda.synchronize(dv)
+    st = lib.ssde_par_bands(C.byref(d), *[ptrs.get(nm) for nm in ("est", "pw_low", "pw_upp", "sim_low", "sim_upp", "crit", "max_dev")])
+    if st != 0:
+        msg = lib.ssde_last_error(None)
+        err = EngineError(f"ssde_par_bands failed ({st}): {msg.decode() if msg else ''}")
+        err.status = st
+        raise err
+    return {nm: (v if nm in ("crit", "max_dev") else (v.t() if device_out else v.T)) for nm, v in out.items()}
 
 
 class Engine:

@@ -801,3 +801,82 @@ class SDE:
                 lp = lp + d.X_re @ self.coeff_re_[re_off[j]:re_off[j + 1]]
             out[nm] = lp if (nm.startswith("mu") and self.type_ != "CIR") else np.exp(lp)
         return out
+
+    # -- uncertainty of the SDE parameters (R/sde.R:941-1180) -----------------------------------------------------------------
+    def _links(self):
+        """0 identity (mu*, except CIR), 1 log: the inverse link par() applies"""
+        return np.array([0 if (nm.startswith("mu") and self.type_ != "CIR") else 1 for nm in self.names_], dtype=np.uint8)
+
+    def _band_table(self, n_post, seed=None, term=None):
+        """The coefficient table of ssde_par_bands: row 0 the estimates, rows 1 .. n_post the draws of post_coeff(n_post, seed);
+        parameter j's fixed-effect coefficients, then its random-effect coefficients.  The coefficients of a fixed parameter keep
+        their value in every draw (R/sde.R:904-915).  `term`: the coefficients whose name does not contain it are zeroed in every
+        row (the reference's substring rule, R/utility.R:137-144)."""
+        ncol_fe, ncol_re = self.terms_["ncol_fe"], self.terms_["ncol_re_par"]
+        fe_off = np.concatenate([[0], np.cumsum(ncol_fe)]).astype(int)
+        re_off = np.concatenate([[0], np.cumsum(ncol_re)]).astype(int)
+        post = self.post_coeff(n_post, seed=seed)
+        fe = np.tile(self.coeff_fe_, (int(n_post), 1))
+        fixed = set(self.fixpar_ or [])
+        est = np.array([k for j, nm in enumerate(self.names_) if nm not in fixed for k in range(fe_off[j], fe_off[j + 1])], dtype=int)
+        if post["coeff_fe"].shape[1] != len(est) or post["coeff_re"].shape[1] != len(self.coeff_re_):
+            raise ValueError("post_coeff does not match the model's free coefficients")
+        fe[:, est] = post["coeff_fe"]
+        fe = np.vstack([self.coeff_fe_, fe])
+        re_ = np.vstack([self.coeff_re_, post["coeff_re"]])
+        if term is not None:
+            for j, d in enumerate(self.designs_):
+                nf = d.names_fe if d.names_fe is not None else ["(Intercept)"] + [""] * (ncol_fe[j] - 1)
+                nr = d.names_re if d.names_re is not None else [""] * ncol_re[j]
+                fe[:, fe_off[j]:fe_off[j + 1]] *= np.array([term in nm for nm in nf], dtype=float)
+                re_[:, re_off[j]:re_off[j + 1]] *= np.array([term in nm for nm in nr], dtype=float)
+        return np.hstack([np.hstack([fe[:, fe_off[j]:fe_off[j + 1]], re_[:, re_off[j]:re_off[j + 1]]]) for j in range(len(self.names_))])
+
+    def _band_blocks(self, t=None, designs=None):
+        """the design blocks of the rows `t` (None: row 0 of the fitted data, or every row of `designs` when given; "all": every
+        row; else row indices, 0-based) as ssde_par_bands takes them"""
+        if t is None:
+            t = "all" if designs is not None else [0]
+        designs = self.designs_ if designs is None else list(designs)
+        if len(designs) != len(self.names_):
+            raise ValueError("designs: one Design per SDE parameter")
+        rows = slice(None) if isinstance(t, str) and t == "all" else np.atleast_1d(np.asarray(t, dtype=int))
+        X_fe = [None if d.X_fe is None else np.asarray(d.X_fe, dtype=np.float64)[rows] for d in designs]
+        X_re = [None if d.X_re is None else np.asarray(d.X_re, dtype=np.float64)[rows] for d in designs]
+        for j, (a, b) in enumerate(zip(X_fe, X_re)):
+            if (1 if a is None else a.shape[1]) != self.terms_["ncol_fe"][j] or (0 if b is None else b.shape[1]) != self.terms_["ncol_re_par"][j]:
+                raise ValueError(f"designs: the blocks of {self.names_[j]} have not the fitted model's columns")
+        return X_fe, X_re
+
+    def post_par(self, n_post=100, resp=True, term=None, seed=None):
+        """Posterior draws of the SDE parameters on the fitted rows (R/sde.R:941-962): an (n, n_par, n_post) array.  It is the
+        matrix CI_pointwise and CI_simultaneous never build -- numpy, for small n."""
+        tab = self._band_table(n_post, seed=seed, term=term)
+        X_fe, X_re = self._band_blocks("all")
+        link, off = self._links(), 0
+        out = np.zeros((self.n_, len(self.names_), int(n_post)))
+        for j in range(len(self.names_)):
+            X = np.hstack([np.ones((self.n_, 1)) if X_fe[j] is None else X_fe[j]] + ([] if X_re[j] is None else [X_re[j]]))
+            lp = X @ tab[1:, off:off + X.shape[1]].T
+            out[:, j, :] = np.exp(lp) if (resp and link[j] == 1) else lp
+            off += X.shape[1]
+        return out
+
+    def _bands(self, simultaneous, t, designs, level, n_post, resp, term, seed):
+        X_fe, X_re = self._band_blocks(t, designs)
+        tab = self._band_table(n_post, seed=seed, term=term)
+        want = ("sim_low", "sim_upp") if simultaneous else ("pw_low", "pw_upp")
+        out = capi.par_bands(X_fe, X_re, self._links(), tab, level=level, resp=resp, simultaneous=simultaneous, want=want)
+        return {"low": out[want[0]], "upp": out[want[1]], "names": list(self.names_)}
+
+    def CI_pointwise(self, t=None, designs=None, level=0.95, n_post=1000, resp=True, term=None, seed=None):
+        """Pointwise confidence intervals of the SDE parameters by posterior simulation (R/sde.R:1003-1043), reduced on the device
+        (ssde_par_bands): {"low", "upp"} (n_t, n_par) arrays in the order of "names".  `t`: rows of the fitted
+        data, 0-based (None: row 0; "all": every row); `designs`: one Design per parameter in place of the fitted blocks (the
+        reference's new_data; then t defaults to "all"); `term`: only the coefficients whose name contains it."""
+        return self._bands(False, t, designs, level, n_post, resp, term, seed)
+
+    def CI_simultaneous(self, t=None, designs=None, level=0.95, n_post=1000, resp=True, term=None, seed=None):
+        """Simultaneous confidence intervals (R/sde.R:1079-1180; Ruppert et al. 2003, §6.5), arguments and result as
+        CI_pointwise.  One table of draws serves the standard errors and the deviations (the reference draws twice)."""
+        return self._bands(True, t, designs, level, n_post, resp, term, seed)
