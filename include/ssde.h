@@ -781,6 +781,80 @@ typedef struct ssde_bands_desc {
 int ssde_par_bands(const ssde_bands_desc *d, double *est, double *pw_low, double *pw_upp,
                    double *sim_low, double *sim_upp, double *crit, double *max_dev);
 
+/* Replicate data sets simulated on the data's own rows, and their check statistics (SDE$simulate / SDE$check_post,
+ * R/sde.R:1395-1508, 1259-1306).  A descriptor call like ssde_par_bands: no handle, synchronous, one device.
+ *   model     BM, OU, CTCRW, BM_SSM, OU_SSM; every other model is SSDE_ERR_MODEL with the reference's message (R/sde.R:1496) -- CIR
+ *             too: the reference's CIR branch cannot run (an undefined `n` at R/sde.R:1487)
+ *   n rows in n_tracks ID segments: track t owns rows [row0[t], row0[t + 1]), row0 [n_tracks + 1] in host memory, row0[0] == 0,
+ *   non-decreasing, row0[n_tracks] == n; an empty track produces nothing.  times [n], host memory; inside a track every step
+ *   dt_i = times[i] - times[i - 1] is finite and > 0.
+ *   Parameter blocks as ssde_bands_desc's (a NULL fixed-effect block with ncol_fe == 1 = a column of ones; device pointers with
+ *   SSDE_SIMROWS_DEVICE_DATA), the same fma chain.  The parameters are mu_1 .. mu_d, then sigma (BM, BM_SSM: n_par = n_dim + 1), tau
+ *   and kappa (OU, OU_SSM) or tau and nu (CTCRW: n_par = n_dim + 2); parameter = g(lp), g = exp where link[j] == 1.
+ *   coeff     [n_coeff_rows x n_coef] row-major, host, n_coeff_rows 1 or n_rep, every entry finite: replicate k of the call uses row k
+ *             (row 0 with one row: the reference's posterior = FALSE); n_coef = sum_j K_j <= SSDE_SIMROWS_MAX_COEF
+ *   sigma_obs NULL or [n_coeff_rows], host, finite and >= 0: the sd of an N(0, sigma^2) error added to every written observation of
+ *             the replicate, whatever the model (the reference's simulator has none)
+ *   z0[c]     the first value of every track in column c (finite); a CTCRW velocity starts at 0 (R/sde.R:1451)
+ *   seed, rep0, n_rep: replicate k is replicate NUMBER rep0 + k of the stream `seed`; rep0 >= 0, n_rep >= 1, rep0 + n_rep < 2^28;
+ *             n_tracks < 2^32 and every track shorter than 2^32 rows
+ *   thr       [n_thr] host, n_thr in 0 .. SSDE_SIMROWS_MAX_THR, each >= 0 (+inf allowed)
+ * The transition into row i of a track uses the parameters of row i - 1 and dt_i (sub_par[i - 1, ], R/sde.R:1434-1478); the exact
+ * forms -- expm1 for 1 - e, a series for the CTCRW position variance at small dt / tau, every fma -- are csrc/ssde_simrows.hpp's.
+ * Deviates: Philox4x32-10 + Box-Muller as in ssde_simulate with the counter (row position in the track, track ordinal, replicate
+ * number, stream) and the key (seed low, seed high); stream 2c gives (transition, error) of column c, for a CTCRW (na, nb) and the
+ * first deviate of stream 2c + 1 the error.  A replicate is a pure function of seed, track ordinal, row position, replicate number,
+ * its coefficient row and its sigma_obs: not of n_rep, of rep0's cut over calls, of budget_mb, of the outputs asked for or of the
+ * other tracks.
+ * Outputs (either may be NULL, not both):
+ *   obs_rep   [n x n_dim x n_rep], element (i, c, k) at i + n (c + n_dim k); host memory, or HBM with SSDE_SIMROWS_DEVICE_OUT
+ *   stats     [n_tracks x n_stat x n_rep], element (t, s, k) at t + n_tracks (s + n_stat k), n_stat = 3 n_dim + 2 + n_thr; always
+ *             host memory.  From the written observations y (error included), D_{i,c} = y_{i,c} - y_{i-1,c} over the track's rows
+ *             from its second on, in row order: s = 3c sum D, 3c + 1 sum D^2, 3c + 2 sum D_i D_{i-1} (rows with both increments in
+ *             the track); then with L_i = sqrt(sum_c D_{i,c}^2): sum L, max L, and per threshold the number of i with L_i <= thr[r]
+ *             (a double).  NaN in every statistic of a track with fewer than two rows and of a (track, replicate) with a y or a
+ *             parameter of a used row that is not finite.
+ * Replicates run in batches under budget_mb MiB of staged outputs (0 = a quarter of the free device memory); both outputs are bitwise
+ * independent of the batching.
+ * SSDE_ERR_ARG -- before anything touches the device; the text through ssde_last_error with a NULL handle -- for every constraint
+ * above, NULL pointers, a wrong abi_version, both outputs NULL, an n_par or n_coef that does not fit the model and the blocks, a
+ * K_j outside 1 .. SSDE_BANDS_MAX_COLS, a link other than 0 / 1, an unknown flag. */
+#define SSDE_SIMROWS_MAX_THR  8
+#define SSDE_SIMROWS_MAX_COEF 128   /* n_coef: 64 lanes' rows are 64 KiB of LDS */
+#define SSDE_SIMROWS_DEVICE_DATA 1u /* x_fe / x_re blocks are HBM pointers on `device` */
+#define SSDE_SIMROWS_DEVICE_OUT  2u /* obs_rep is an HBM pointer on `device` */
+typedef struct ssde_simrows_desc {
+    int32_t  abi_version;     /* SSDE_ABI_VERSION */
+    int32_t  device;          /* HIP device ordinal, -1 = current device */
+    int32_t  budget_mb;
+    uint32_t flags;
+    uint32_t reserved;
+    int32_t  model;           /* SSDE_MODEL_* */
+    int32_t  n_dim;
+    int32_t  n_par;
+    int64_t  n;
+    int64_t  n_tracks;
+    const int64_t *row0;
+    const double *times;
+    const int32_t *ncol_fe;
+    const double *const *x_fe;
+    const int32_t *ncol_re;
+    const double *const *x_re;
+    const uint8_t *link;
+    const double *coeff;
+    int32_t  n_coeff_rows;
+    int32_t  n_coef;
+    const double *sigma_obs;
+    double   z0[8];
+    uint64_t seed;
+    int64_t  rep0;
+    int64_t  n_rep;
+    const double *thr;
+    int32_t  n_thr;
+    int32_t  reserved2;
+} ssde_simrows_desc;
+int ssde_simulate_rows(const ssde_simrows_desc *d, double *obs_rep, double *stats);
+
 void ssde_destroy(ssde_handle *h);
 
 /* Message of the last failure on this handle (or of the last failed ssde_create when h == NULL). */

@@ -85,6 +85,17 @@ class SsdeBandsDesc(C.Structure):
                 ("device", C.c_int32), ("budget_mb", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class SsdeSimrowsDesc(C.Structure):
+    _fields_ = [("abi_version", C.c_int32), ("device", C.c_int32), ("budget_mb", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+                ("model", C.c_int32), ("n_dim", C.c_int32), ("n_par", C.c_int32), ("n", C.c_int64), ("n_tracks", C.c_int64),
+                ("row0", C.POINTER(C.c_int64)), ("times", C.POINTER(C.c_double)),
+                ("ncol_fe", C.POINTER(C.c_int32)), ("x_fe", C.POINTER(C.c_void_p)), ("ncol_re", C.POINTER(C.c_int32)),
+                ("x_re", C.POINTER(C.c_void_p)), ("link", C.POINTER(C.c_uint8)), ("coeff", C.POINTER(C.c_double)),
+                ("n_coeff_rows", C.c_int32), ("n_coef", C.c_int32), ("sigma_obs", C.POINTER(C.c_double)), ("z0", C.c_double * 8),
+                ("seed", C.c_uint64), ("rep0", C.c_int64), ("n_rep", C.c_int64), ("thr", C.POINTER(C.c_double)),
+                ("n_thr", C.c_int32), ("reserved2", C.c_int32)]
+
+
 OPT_KERNEL_STAMPS, OPT_COMM_DEFER, OPT_SMOOTH_BUDGET_MB, OPT_LAG_EARLY = 1, 2, 3, 4
 LAG_CUTS = tuple(range(32, 129, 16))   # the early cuts of the lag statistics (csrc/ssde_lagstats.hpp)
 # ssde_info_t.kernel_id (include/ssde.h: SSDE_KERNEL_*): the kernel family that ran the rows of the last evaluation
@@ -591,6 +602,8 @@ def load_library():
     lib.ssde_simulate.restype = C.c_int
     lib.ssde_par_bands.argtypes = [C.POINTER(SsdeBandsDesc)] + [C.c_void_p] * 7
     lib.ssde_par_bands.restype = C.c_int
+    lib.ssde_simulate_rows.argtypes = [C.POINTER(SsdeSimrowsDesc), C.c_void_p, C.c_void_p]
+    lib.ssde_simulate_rows.restype = C.c_int
     lib.ssde_hess.argtypes = [C.c_void_p, _dp, C.c_int32, _ip, C.c_int32, _dp]
     lib.ssde_hess.restype = C.c_int
     lib.ssde_set_option.argtypes = [C.c_void_p, C.c_int32, C.c_int64]
@@ -617,13 +630,15 @@ OCC_FORCE_GLOBAL = 1   # ssde_path_occupancy flag: every wavefront group runs th
 PROX_MAX_RADII = 8     # SSDE_PROX_MAX_RADII: the most radii of one ssde_path_proximity
 BANDS_MAX_TAIL, BANDS_MAX_COLS, BANDS_MAX_PAR = 64, 64, 16   # SSDE_BANDS_MAX_*: order statistics of a tail, columns of a parameter, parameters
 BANDS_DEVICE_DATA, BANDS_DEVICE_OUT = 1, 2                  # ssde_par_bands flags: the blocks / the n x q outputs are HBM pointers
+SIMROWS_MAX_THR, SIMROWS_MAX_COEF = 8, 128                  # SSDE_SIMROWS_MAX_*: thresholds of one ssde_simulate_rows, coefficients of one row
+SIMROWS_DEVICE_DATA, SIMROWS_DEVICE_OUT = 1, 2              # ssde_simulate_rows flags: the blocks / obs_rep are HBM pointers
 OCC_MAX_SUB = 64       # SSDE_OCC_MAX_SUB: the most sub-steps ssde_path_occupancy_fine cuts an interval into
 
 WINDOW_TOL = 1e-11  # largest tolerated relative hand-over disagreement between time windows
 
 EXPORTED_SYMBOLS = ("ssde_create", "ssde_eval", "ssde_eval_device", "ssde_penalty", "ssde_report", "ssde_widen_windows", "ssde_relax_windows",
                     "ssde_info", "ssde_destroy", "ssde_last_error", "ssde_abi_version", "ssde_comm_unique_id", "ssde_comm_init_rank", "ssde_forget", "ssde_laplace_eval", "ssde_last_kernel_ms", "ssde_kernel_ms_history",
-                    "ssde_simulate", "ssde_par_bands", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth", "ssde_smooth_draws", "ssde_predict", "ssde_predict_draws", "ssde_path_stats", "ssde_path_speed", "ssde_path_occupancy", "ssde_last_occupancy_form", "ssde_path_occupancy_fine", "ssde_last_occupancy_points", "ssde_last_hess_plan", "ssde_path_proximity", "ssde_last_proximity_plan",
+                    "ssde_simulate", "ssde_par_bands", "ssde_simulate_rows", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth", "ssde_smooth_draws", "ssde_predict", "ssde_predict_draws", "ssde_path_stats", "ssde_path_speed", "ssde_path_occupancy", "ssde_last_occupancy_form", "ssde_path_occupancy_fine", "ssde_last_occupancy_points", "ssde_last_hess_plan", "ssde_path_proximity", "ssde_last_proximity_plan",
                     "ssde_lagstats_host_m", "ssde_lagstats_read_m", "ssde_lagforms_host_m", "ssde_reduce_host", "ssde_last_finish_form", "ssde_last_gain_feed", "ssde_last_gain_rows",
                     "ssde_lagstats_host_cut", "ssde_lagstats_read_cut", "ssde_last_lag_cut")
 
@@ -895,6 +910,120 @@ def par_bands(X_fe, X_re, link, coeff, level=0.95, resp=True, simultaneous=True,
         err.status = st
         raise err
     return {nm: (v if nm in ("crit", "max_dev") else (v.t() if device_out else v.T)) for nm, v in out.items()}
+
+
+def simulate_rows(model, n_dim, row0, times, X_fe, X_re, link, coeff, *, sigma_obs=None, z0=0.0, seed=0, rep0=0, n_rep=1,
+                  thresholds=None, want=("obs", "stats"), device_out=False, budget_mb=0, device=None):
+    """ssde_simulate_rows: `n_rep` replicate data sets simulated on the rows the arguments describe -- the reference's
+    SDE$simulate with row-varying parameters, dt = diff(time) and the ID segments as tracks -- and the check statistics of every
+    (track, replicate).  `row0`: (n_tracks + 1,) first row of every track; `times`: (n,); `X_fe`, `X_re`, `link` as par_bands'
+    (parameters mu_1 .. mu_d, then sigma | tau, kappa | tau, nu); `coeff`: (1, n_coef) or (n_rep, n_coef), replicate k uses row k;
+    `sigma_obs`: None, a number or one per coefficient row; replicate k is replicate number rep0 + k of the stream `seed`.
+    Returns {"obs": (n_rep, n, d), "stats": (n_rep, n_tracks, 3 d + 2 + n_thr)} with the entries `want` names; "obs" is a device
+    tensor with `device_out`.  Raises EngineError (with .status) where the C call fails; without a GPU every call that passes the
+    argument checks raises: there is no CPU fallback."""
+    lib = load_library()
+    if model not in MODEL_CODES:
+        raise ValueError("Unknown SDE type")
+    want = tuple(want)
+    if any(w not in ("obs", "stats") for w in want):
+        raise ValueError('simulate_rows: want is a subset of ("obs", "stats")')
+    q = len(X_fe)
+    if len(X_re) != q or len(link) != q:
+        raise ValueError("simulate_rows: one entry per parameter in X_fe, X_re and link")
+    r0 = np.ascontiguousarray(row0, dtype=np.int64)
+    tm = np.ascontiguousarray(times, dtype=np.float64)
+    if r0.ndim != 1 or r0.size < 1 or tm.ndim != 1:
+        raise ValueError("simulate_rows: row0 is (n_tracks + 1,) and times (n,)")
+    n, M, d = int(tm.size), int(r0.size) - 1, int(n_dim)
+    blocks = [b for b in list(X_fe) + list(X_re) if b is not None]
+    on_dev = [hasattr(b, "data_ptr") for b in blocks]
+    if any(on_dev) and not all(on_dev):
+        raise ValueError("simulate_rows: the blocks are all numpy arrays or all device tensors")
+    dev_data = bool(blocks) and all(on_dev)
+    torch = None
+    if dev_data or device_out:
+        import torch
+    keep = []
+
+    def block(b):
+        if b is None:
+            return None, 0
+        if dev_data:
+            if b.dtype != torch.float64 or b.dim() != 2:
+                raise ValueError("simulate_rows: device blocks are 2-d float64 tensors")
+            t = b.t().contiguous()                       # column-major (n, k) = row-major (k, n)
+            keep.append(t)
+            rows, cols, p = int(b.shape[0]), int(b.shape[1]), t.data_ptr()
+        else:
+            a = np.asfortranarray(np.asarray(b, dtype=np.float64))
+            if a.ndim != 2:
+                raise ValueError("simulate_rows: a block is an (n, k) array")
+            keep.append(a)
+            rows, cols, p = a.shape[0], a.shape[1], a.ctypes.data
+        if rows != n:
+            raise ValueError("simulate_rows: a block has not one row per time")
+        return p, cols
+
+    pf = [block(b) for b in X_fe]
+    pr = [block(b) for b in X_re]
+    cf = np.ascontiguousarray(np.atleast_2d(np.asarray(coeff, dtype=np.float64)))
+    if cf.ndim != 2:
+        raise ValueError("simulate_rows: coeff is (1, n_coef) or (n_rep, n_coef)")
+    kf = np.array([1 if p is None else k for p, k in pf], dtype=np.int32)
+    kr = np.array([k for _, k in pr], dtype=np.int32)
+    xf = (C.c_void_p * q)(*[p for p, _ in pf])
+    xr = (C.c_void_p * q)(*[(p if k else None) for p, k in pr])
+    lk = np.ascontiguousarray(link, dtype=np.uint8)
+    so = None
+    if sigma_obs is not None:
+        so = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma_obs, dtype=np.float64), (cf.shape[0],)))
+    thr = np.zeros(0) if thresholds is None else np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).ravel())
+    ds = SsdeSimrowsDesc()
+    ds.abi_version, ds.budget_mb, ds.model, ds.n_dim, ds.n_par = ABI_VERSION, int(budget_mb), MODEL_CODES[model], d, q
+    ds.n, ds.n_tracks = n, M
+    ds.row0, ds.times = r0.ctypes.data_as(C.POINTER(C.c_int64)), tm.ctypes.data_as(_dp)
+    ds.ncol_fe, ds.x_fe = kf.ctypes.data_as(C.POINTER(C.c_int32)), xf
+    ds.ncol_re, ds.x_re = kr.ctypes.data_as(C.POINTER(C.c_int32)), xr
+    ds.link, ds.coeff = lk.ctypes.data_as(C.POINTER(C.c_uint8)), cf.ctypes.data_as(_dp)
+    ds.n_coeff_rows, ds.n_coef = cf.shape[0], cf.shape[1]
+    if so is not None:
+        ds.sigma_obs = so.ctypes.data_as(_dp)
+    for k, v in enumerate(np.broadcast_to(np.asarray(z0, dtype=np.float64), (min(max(d, 0), 8),))):
+        ds.z0[k] = float(v)
+    ds.seed, ds.rep0, ds.n_rep = int(seed) & 0xFFFFFFFFFFFFFFFF, int(rep0), int(n_rep)
+    if thr.size:
+        ds.thr = thr.ctypes.data_as(_dp)
+    ds.n_thr = int(thr.size)
+    ds.flags = (SIMROWS_DEVICE_DATA if dev_data else 0) | (SIMROWS_DEVICE_OUT if device_out else 0)
+    dv = None
+    if torch is not None:
+        dv = blocks[0].device if dev_data else (torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device))
+        ds.device = int(dv.index or 0)
+    else:
+        ds.device = -1 if device is None else int(device)
+    n_stat = 3 * d + 2 + int(thr.size)
+    R = max(int(n_rep), 0)
+    obs = stats = None
+    if "obs" in want:
+        obs = torch.empty((R, max(d, 0), n), dtype=torch.float64, device=dv) if device_out else np.zeros((R, max(d, 0), n))
+    if "stats" in want:
+        stats = np.zeros((R, max(n_stat, 0), M))
+    if torch is not None:
+        torch.cuda.synchronize(dv)
+    st = lib.ssde_simulate_rows(C.byref(ds), None if obs is None else (obs.data_ptr() if device_out else obs.ctypes.data),
+                                None if stats is None else stats.ctypes.data)
+    if st != 0:
+        msg = lib.ssde_last_error(None)
+        err = EngineError(f"ssde_simulate_rows failed ({st}): {msg.decode() if msg else ''}")
+        err.status = st
+        raise err
+    out = {}
+    if obs is not None:
+        out["obs"] = obs.permute(0, 2, 1) if device_out else obs.transpose(0, 2, 1)
+    if stats is not None:
+        out["stats"] = stats.transpose(0, 2, 1)
+    return out
 
 
 class Engine:

@@ -18,6 +18,7 @@
 #include <string>
 
 #include "../../include/ssde.h"
+#include "ssde_philox.hpp"
 
 namespace ssde_engine { extern thread_local std::string g_create_error; }   // what ssde_last_error(NULL) returns
 #define g_sim_error ssde_engine::g_create_error
@@ -39,27 +40,9 @@ struct SimArgs {
     double* obs;
 };
 
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&o)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
-
-// two independent N(0, 1) deviates of (track, row, stream)
+// two independent N(0, 1) deviates of (track, row, stream): the generator is ssde_philox.hpp's, shared with k_sim_rows.hip
 __device__ __forceinline__ void normal_pair(const SimArgs& A, uint64_t track, uint32_t row, uint32_t stream, double& n1, double& n2) {
-    uint32_t o[4];
-    philox4x32_10(row, (uint32_t)track, (uint32_t)(track >> 32), stream, A.k0, A.k1, o);
-    const double u1 = ((double)((((uint64_t)o[0] << 32) | o[1]) >> 11) + 0.5) * 0x1.0p-53;     // (0, 1)
-    const double u2 = ((double)((((uint64_t)o[2] << 32) | o[3]) >> 11) + 0.5) * 0x1.0p-53;
-    const double r = sqrt(-2.0 * log(u1));
-    double s, c;
-    sincospi(2.0 * u2, &s, &c);
-    n1 = r * c; n2 = r * s;
+    ssde::philox_normal_pair(A.k0, A.k1, row, (uint32_t)track, (uint32_t)(track >> 32), stream, n1, n2);
 }
 
 constexpr int SIM_TT = 32;     // rows per LDS tile

@@ -880,3 +880,145 @@ class SDE:
         """Simultaneous confidence intervals (R/sde.R:1079-1180; Ruppert et al. 2003, §6.5), arguments and result as
         CI_pointwise.  One table of draws serves the standard errors and the deviations (the reference draws twice)."""
         return self._bands(True, t, designs, level, n_post, resp, term, seed)
+
+    # -- simulation and posterior checks (R/sde.R:1395-1508, 1259-1306) -------------------------------------------------------
+    def _coeff_estimate(self):
+        """row 0 of _band_table without the draws: parameter j's fixed-effect, then its random-effect coefficients"""
+        fe_off = np.concatenate([[0], np.cumsum(self.terms_["ncol_fe"])]).astype(int)
+        re_off = np.concatenate([[0], np.cumsum(self.terms_["ncol_re_par"])]).astype(int)
+        return np.concatenate([np.concatenate([self.coeff_fe_[fe_off[j]:fe_off[j + 1]], self.coeff_re_[re_off[j]:re_off[j + 1]]])
+                               for j in range(len(self.names_))])[None, :]
+
+    def _sim_rows(self, designs=None, ID=None, time=None):
+        """(row0, ID, time, X_fe, X_re) of the rows a simulation runs on: the fitted rows, or those of `designs`, `ID`, `time`; row0 the
+        first row of every run of equal IDs"""
+        if designs is None:
+            if ID is not None or time is not None:
+                raise ValueError("simulate: new rows need designs, ID and time together")
+            ID, time = self.data_["ID"], self.data_["time"]
+        elif time is None:
+            raise ValueError("'data' should have a column named 'time'")                 # R/sde.R:1397-1399
+        time = np.asarray(time, dtype=np.float64).ravel()
+        ids = np.ones(len(time)) if ID is None else np.asarray(ID).ravel()               # R/sde.R:1400-1402
+        if len(ids) != len(time):
+            raise ValueError("ID and time must have the same length")
+        X_fe, X_re = self._band_blocks("all", designs)
+        for b in list(X_fe) + list(X_re):
+            if b is not None and b.shape[0] != len(time):
+                raise ValueError("designs: one row per time")
+        # an intercept-only block is passed as "no column", as _problem does: the device then evaluates the parameter once
+        X_fe = [None if (b is None or (b.shape[1] == 1 and np.all(b == 1.0))) else b for b in X_fe]
+        row0 = np.r_[0, np.nonzero(ids[1:] != ids[:-1])[0] + 1, len(ids)].astype(np.int64) if len(ids) else np.zeros(1, dtype=np.int64)
+        return row0, ids, time, X_fe, X_re
+
+    def _sim_sigma_obs(self, n_rows, seed, posterior):
+        """sigma_obs of the replicates: exp(log_sigma_obs) of a fitted state-space model (its posterior draws with `posterior`)"""
+        ls = getattr(self, "log_sigma_obs_", None)
+        if ls is None:
+            return None
+        if not posterior:
+            return np.full(n_rows, np.exp(ls))
+        post = self.post_coeff(n_rows, seed=seed)                                         # the draws _band_table(n_rows, seed) holds
+        if "log_sigma_obs" not in post or post["log_sigma_obs"].shape[1] != 1:
+            return np.full(n_rows, np.exp(ls))
+        return np.exp(post["log_sigma_obs"][:, 0])
+
+    def simulate(self, z0=0, posterior=False, seed=0, designs=None, ID=None, time=None):
+        """One data set simulated from the model on the fitted rows (R/sde.R:1395-1508) by the device (ssde_simulate_rows, DESIGN.md
+        §3.19): an (n, d) array.  With `designs` (one Design per parameter, as in CI_pointwise), `ID` and `time` it runs on new rows
+        -- the reference's `data` argument.  `posterior`: the coefficients are one posterior draw, row 1 of _band_table(1, seed);
+        else the estimates.  A fitted state-space model (BM_SSM, OU_SSM, CTCRW) adds its observation error, sd exp(log_sigma_obs), to
+        what it writes: the reference has no such branch (its simulator writes the latent path), but the data these models are
+        fitted to carry that error.  Models other than BM, OU, CTCRW, BM_SSM, OU_SSM raise the engine's model error."""
+        row0, _, tm, X_fe, X_re = self._sim_rows(designs, ID, time)
+        coeff = self._band_table(1, seed)[1:] if posterior else self._coeff_estimate()
+        out = capi.simulate_rows(self.type_, len(self.response_), row0, tm, X_fe, X_re, self._links(), coeff,
+                                 sigma_obs=self._sim_sigma_obs(1, seed, posterior), z0=z0, seed=seed, n_rep=1, want=("obs",))
+        return np.ascontiguousarray(out["obs"][0])
+
+    @staticmethod
+    def _check_names(d, n_thr):
+        cols = [""] if d == 1 else [str(c + 1) for c in range(d)]
+        return ([f"{s}{c}" for c in cols for s in ("mean_incr", "sd_incr", "acf1_incr")] + ["mean_step", "max_step"]
+                + [f"share_below_{r + 1}" for r in range(n_thr)])
+
+    @staticmethod
+    def _pool_check_stats(stats, row0, d, n_thr):
+        """The built-in check statistics of every replicate from ssde_simulate_rows' per-track sums, pooled over the tracks in track
+        order: stats (n_rep, n_tracks, 3 d + 2 + n_thr) -> (3 d + 2 + n_thr, n_rep).  N the increments of all tracks with two or
+        more rows, N2 the pairs of successive increments inside a track: mean = S1 / N, var = (S2 - S1 mean) / (N - 1), sd =
+        sqrt(var), acf1 = (S11 / N2 - mean^2) / (var (N - 1) / N), mean_step = SL / N, max_step = the largest of the tracks' maxima,
+        share = count / N.  A NaN track makes its replicate NaN."""
+        ln = np.diff(np.asarray(row0, dtype=np.int64))
+        use = ln >= 2
+        N, N2 = float(np.sum(ln[use] - 1)), float(np.sum(ln[use] - 2))
+        out = np.full((3 * d + 2 + n_thr, stats.shape[0]), np.nan)
+        if N < 1:
+            return out
+        st = stats[:, use, :]
+        tot = np.zeros((stats.shape[0], stats.shape[2]))
+        for t in range(st.shape[1]):                                                     # in track order
+            tot += st[:, t, :]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            for c in range(d):
+                s1, s2, s11 = tot[:, 3 * c], tot[:, 3 * c + 1], tot[:, 3 * c + 2]
+                mean = s1 / N
+                var = (s2 - s1 * mean) / (N - 1.0) if N > 1 else np.full_like(s1, np.nan)
+                out[3 * c], out[3 * c + 1] = mean, np.sqrt(var)
+                # lag-1 autocorrelation of the increments about the pooled mean, over the pairs inside a track, by the pooled variance
+                out[3 * c + 2] = (s11 / N2 - mean * mean) / (var * (N - 1.0) / N) if N2 >= 1 else np.nan
+            out[3 * d] = tot[:, 3 * d] / N
+            out[3 * d + 1] = np.max(st[:, :, 3 * d + 1], axis=1)                          # (np.max hands a NaN on)
+            for r in range(n_thr):
+                out[3 * d + 2 + r] = tot[:, 3 * d + 2 + r] / N
+        return out
+
+    @staticmethod
+    def _track_check_sums(obs, row0, thr):
+        """ssde_simulate_rows' per-track statistics of one data set in numpy: (n_tracks, 3 d + 2 + n_thr)"""
+        obs = np.asarray(obs, dtype=np.float64)
+        d, M = obs.shape[1], len(row0) - 1
+        out = np.full((M, 3 * d + 2 + len(thr)), np.nan)
+        for t in range(M):
+            y = obs[row0[t]:row0[t + 1]]
+            if len(y) < 2 or not np.all(np.isfinite(y)):
+                continue
+            D = np.diff(y, axis=0)
+            L = np.sqrt(np.sum(D * D, axis=1))
+            for c in range(d):
+                out[t, 3 * c:3 * c + 3] = [np.sum(D[:, c]), np.sum(D[:, c] ** 2), np.sum(D[1:, c] * D[:-1, c])]
+            out[t, 3 * d], out[t, 3 * d + 1] = np.sum(L), np.max(L)
+            out[t, 3 * d + 2:] = [np.sum(L <= r) for r in thr]
+        return out
+
+    def check_post(self, check_fn=None, n_sims=100, seed=0, thresholds=None, posterior=True, budget_mb=256):
+        """Posterior predictive check (R/sde.R:1259-1306): `n_sims` replicate data sets simulated on the fitted rows, each with its
+        own posterior coefficient draw -- the rows _band_table(n_sims, seed)[1:]; the estimates throughout with posterior=False --
+        and a statistic of each against the data's.  {"obs_stat": (n_stat,), "stats": (n_stat, n_sims), "names"}: the reference's
+        list without the plot.  check_fn=None: the built-in statistics, reduced on the device without a replicate ever coming home
+        -- per column the mean, sd and lag-1 autocorrelation of the increments, the mean and the largest step length, the share of
+        steps at or below each of `thresholds` -- pooled over the tracks; the same definition in numpy gives obs_stat.  A callable
+        receives (ID, time, obs) of the data and of every replicate and returns a vector; the replicates then come home in batches
+        of at most `budget_mb` MiB."""
+        row0, ids, tm, X_fe, X_re = self._sim_rows()
+        d, n_sims = len(self.response_), int(n_sims)
+        coeff = self._band_table(n_sims, seed)[1:] if posterior else self._coeff_estimate()
+        so = self._sim_sigma_obs(n_sims if posterior else 1, seed, posterior)
+        if check_fn is None:
+            thr = np.zeros(0) if thresholds is None else np.asarray(thresholds, dtype=np.float64).ravel()
+            st = capi.simulate_rows(self.type_, d, row0, tm, X_fe, X_re, self._links(), coeff, sigma_obs=so, seed=seed, n_rep=n_sims,
+                                    thresholds=thr, want=("stats",))["stats"]
+            stats = self._pool_check_stats(st, row0, d, len(thr))
+            obs_stat = self._pool_check_stats(self._track_check_sums(self.obs(), row0, thr)[None], row0, d, len(thr))[:, 0]
+            return {"obs_stat": obs_stat, "stats": stats, "names": self._check_names(d, len(thr))}
+        obs_stat = np.atleast_1d(np.asarray(check_fn(ids, tm, self.obs()), dtype=np.float64))
+        stats = np.zeros((len(obs_stat), n_sims))
+        per = max(1, int((int(budget_mb) << 20) // max(8 * len(tm) * d, 1)))
+        for k0 in range(0, n_sims, per):
+            nk = min(per, n_sims - k0)
+            rows = slice(k0, k0 + nk) if posterior else slice(0, 1)
+            obs = capi.simulate_rows(self.type_, d, row0, tm, X_fe, X_re, self._links(), coeff[rows], sigma_obs=None if so is None else so[rows],
+                                     seed=seed, rep0=k0, n_rep=nk, want=("obs",), budget_mb=budget_mb)["obs"]
+            for k in range(nk):
+                stats[:, k0 + k] = check_fn(ids, tm, np.ascontiguousarray(obs[k]))
+        return {"obs_stat": obs_stat, "stats": stats, "names": [f"statistic {k + 1}" for k in range(len(obs_stat))]}
