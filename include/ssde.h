@@ -25,6 +25,8 @@
  *                                                nllk_ou_ssm.hpp:215, nllk_bm_ssm.hpp:177)
  *   ssde_smooth        <- (new) fixed-interval Kalman smoother and whitened innovations of the state-space families: what
  *                         the reference's SDE$residuals() stops at (R/sde.R:1186-1228) and aest_all does not give
+ *   ssde_smooth_loo    <- (new) leave-one-fix-out predictions of every fix from the rest of its track: deletion residuals, exact
+ *                         leave-one-out log predictive densities and per-track outlier counts, from the smoother's own recursion
  *   ssde_smooth_draws  <- (new) joint posterior draws of the whole state path (backward sampling over the smoother's records):
  *                         what speed, distance travelled, time in a region or multiple imputation are computed from
  *   ssde_predict       <- (new) the smoothed state at any time between or after the rows, from the smoother's records: what the
@@ -351,6 +353,35 @@ int ssde_report(ssde_handle *h, const double *par, int32_t n_par_full, double *a
  * state and every later ssde_eval result as they were; the per-row records live in a buffer of the call's own, capped by
  * SSDE_OPT_SMOOTH_BUDGET_MB (tracks are processed in chunks of whole wavefront groups; the result does not depend on it). */
 int ssde_smooth(ssde_handle *h, const double *par, int32_t n_par_full, double *a_smooth, double *P_smooth, double *resid);
+
+/* Leave-one-out (deletion) residuals and predictive densities of the Kalman families at `par` (definitions: DESIGN.md §3.20): what
+ * every OTHER fix of the track says about fix j, from the smoother's own records and backward recursion -- no refit, no new forward
+ * pass.  With r, N the smoother's backward quantities BEFORE row j is folded in, w_j = F_j^-1 v_j - K_j' r and
+ * M_j = F_j^-1 + K_j' N K_j (at a track's last state row F_j^-1 v_j and F_j^-1), y_j | y_-j ~ N(y_j - D_j w_j, D_j) with D_j = M_j^-1
+ * (de Jong 1989).  A SERVED row is a state row whose record took an update (resid of ssde_smooth is not NaN) and whose M_j is
+ * positive definite.  Per-row outputs, each may be NULL, indexed by the caller's row:
+ *   loo_mean  [n x n_dim]          column-major: E[y_j | every other fix of the track]
+ *   loo_cov   [n x n_dim x n_dim]  element (i, r, c) at i + n * (r + n_dim * c): D_j, symmetrised
+ *   loo_resid [n x n_dim]          z_j = C_j^-1 (y_j - loo_mean_j), C_j the lower Cholesky factor of D_j (resid's convention).  N(0, I)
+ *                                  under the model at every row, but -- unlike resid -- NOT independent between rows: two deletion
+ *                                  residuals of one track share all the other fixes
+ *   lpd       [n]                  log p(y_j | y_-j) = -(n_dim log 2 pi + log det D_j + q_j) / 2, q_j = z_j' z_j
+ * NaN on every row that is not served (a track's first row, one-row tracks, NA rows, detF <= 0); where only the Cholesky factor of
+ * D_j fails (a pivot <= 0 or not finite) loo_mean and loo_cov are kept, loo_resid and lpd are NaN and the row enters no statistic.
+ *   stats [n_tracks x n_stat], element (t, k) at t + n_tracks * k, n_stat = 4 + n_thr, t the ID segment's ordinal in the caller's
+ *   data, or NULL:  0 the served rows; 1 the sum of lpd_j (the track's leave-one-out score); 2 max q_j; 3 the caller's 0-based row
+ *   attaining it (the smallest of a tie: ssde_path_speed's convention); 4 + r the served rows with q_j > thr[r].  A track without a
+ *   served row: 0, 0, NaN, NaN and zero counts.
+ *   thr [n_thr] host memory, every entry finite and >= 0, on the q scale (the caller's chi-square_{n_dim} quantiles).
+ * Every handle layout ssde_smooth serves is served.  An uncoupled wide response (column pairs) serves loo_mean, loo_cov (cross-pair
+ * blocks exactly 0) and loo_resid; lpd and stats need a per-row sum across the pair handles there: SSDE_ERR_MODEL.  SSDE_ERR_MODEL
+ * for the direct families and ESEAL_SSM.  SSDE_ERR_ARG: all five outputs NULL, n_thr outside 0 .. SSDE_LOO_MAX_THR, thr NULL with
+ * n_thr > 0, a threshold that is not finite or < 0, n_thr > 0 without stats, flags != 0.  Isolation, chunking and buffers as
+ * ssde_smooth; the result is bitwise independent of the chunking and of the devices. */
+#define SSDE_LOO_MAX_THR 8
+int ssde_smooth_loo(ssde_handle *h, const double *par, int32_t n_par_full,
+                    double *loo_mean, double *loo_cov, double *loo_resid, double *lpd,
+                    const double *thr, int32_t n_thr, double *stats, uint32_t flags);
 
 /* Joint posterior draws of the whole state path at `par` (definitions: DESIGN.md §3.10): backward sampling over the smoother's own
  * forward records, so a draw carries the dependence BETWEEN rows that the row-wise a_smooth / P_smooth leave out.

@@ -514,6 +514,8 @@ def load_library():
     lib.ssde_report.restype = C.c_int
     lib.ssde_smooth.argtypes = [C.c_void_p, _dp, C.c_int32, _dp, _dp, _dp]
     lib.ssde_smooth.restype = C.c_int
+    lib.ssde_smooth_loo.argtypes = [C.c_void_p, _dp, C.c_int32, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, C.c_uint32]
+    lib.ssde_smooth_loo.restype = C.c_int
     lib.ssde_smooth_draws.argtypes = [C.c_void_p, _dp, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.c_void_p, C.c_uint32]
     lib.ssde_smooth_draws.restype = C.c_int
     lib.ssde_predict.argtypes = [C.c_void_p, _dp, C.c_int32, C.POINTER(C.c_int64), _dp, C.c_int64, _dp, _dp]
@@ -625,6 +627,7 @@ class EngineError(RuntimeError):
 
 PATH_MAX_REGIONS = 8   # SSDE_PATH_MAX_REGIONS (include/ssde.h)
 SPEED_MAX_THR = 8      # SSDE_SPEED_MAX_THR: the most thresholds of one ssde_path_speed
+LOO_MAX_THR = 8        # SSDE_LOO_MAX_THR: the most thresholds of one ssde_smooth_loo
 DRAWS_DEVICE_OUT = 1   # ssde_smooth_draws flag: `draws` is an HBM pointer on the handle's device (include/ssde.h)
 OCC_FORCE_GLOBAL = 1   # ssde_path_occupancy flag: every wavefront group runs the global form (SSDE_OCC_FORCE_GLOBAL)
 PROX_MAX_RADII = 8     # SSDE_PROX_MAX_RADII: the most radii of one ssde_path_proximity
@@ -638,7 +641,7 @@ WINDOW_TOL = 1e-11  # largest tolerated relative hand-over disagreement between 
 
 EXPORTED_SYMBOLS = ("ssde_create", "ssde_eval", "ssde_eval_device", "ssde_penalty", "ssde_report", "ssde_widen_windows", "ssde_relax_windows",
                     "ssde_info", "ssde_destroy", "ssde_last_error", "ssde_abi_version", "ssde_comm_unique_id", "ssde_comm_init_rank", "ssde_forget", "ssde_laplace_eval", "ssde_last_kernel_ms", "ssde_kernel_ms_history",
-                    "ssde_simulate", "ssde_par_bands", "ssde_simulate_rows", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth", "ssde_smooth_draws", "ssde_predict", "ssde_predict_draws", "ssde_path_stats", "ssde_path_speed", "ssde_path_occupancy", "ssde_last_occupancy_form", "ssde_path_occupancy_fine", "ssde_last_occupancy_points", "ssde_last_hess_plan", "ssde_path_proximity", "ssde_last_proximity_plan",
+                    "ssde_simulate", "ssde_par_bands", "ssde_simulate_rows", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth", "ssde_smooth_loo", "ssde_smooth_draws", "ssde_predict", "ssde_predict_draws", "ssde_path_stats", "ssde_path_speed", "ssde_path_occupancy", "ssde_last_occupancy_form", "ssde_path_occupancy_fine", "ssde_last_occupancy_points", "ssde_last_hess_plan", "ssde_path_proximity", "ssde_last_proximity_plan",
                     "ssde_lagstats_host_m", "ssde_lagstats_read_m", "ssde_lagforms_host_m", "ssde_reduce_host", "ssde_last_finish_form", "ssde_last_gain_feed", "ssde_last_gain_rows",
                     "ssde_lagstats_host_cut", "ssde_lagstats_read_cut", "ssde_last_lag_cut")
 
@@ -1245,6 +1248,33 @@ class Engine:
         self._check(self.lib.ssde_smooth(self._h, par.ctypes.data_as(_dp), self.n_par_full, mean.ctypes.data_as(_dp),
                                          P.ctypes.data_as(_dp) if cov else None, e.ctypes.data_as(_dp) if resid else None))
         return {"mean": mean, "cov": P, "resid": e}
+
+    def smooth_loo(self, par, cov: bool = True, thresholds=None, lpd: bool = True, stats: bool = True) -> dict:
+        """Leave-one-out residuals and predictive densities at `par` (ssde_smooth_loo): what every OTHER fix of the
+        track says about fix j.  {"mean": (n x d) E[y_j | y_-j], "cov": (n x d x d) its covariance or None, "resid": (n x d) the
+        whitened deletion residuals (N(0, I) at every row, but not independent between rows), "lpd": (n,) log p(y_j | y_-j) or None,
+        "stats": (n_tracks, 4 + n_thr) or None -- per track the served rows, the sum of lpd (its leave-one-out score), the largest
+        q_j = |resid_j|^2, the row of the data (0-based) attaining it, then per threshold the served rows with q_j above it}.  NaN
+        on rows that are not served (a track's first row, NA rows, rows without an update).  `thresholds`: at most LOO_MAX_THR finite
+        numbers >= 0 on the q scale (chi-square quantiles with d degrees of freedom) or None.  An uncoupled wide response (column
+        pairs) serves neither "lpd" nor "stats": pass lpd=False, stats=False there."""
+        par = np.ascontiguousarray(par, dtype=np.float64)
+        if par.shape != (self.n_par_full,):
+            raise ValueError(f"par must have length {self.n_par_full}")
+        thr = np.zeros(0) if thresholds is None else np.ascontiguousarray(thresholds, dtype=np.float64)
+        if thr.ndim != 1:
+            raise ValueError("thresholds must be a list of numbers")
+        n, d, n_trk = self.problem.n, self.problem.n_dim, self.problem.n_seg
+        mean = np.zeros((n, d), order="F")
+        V = np.zeros((n, d, d), order="F") if cov else None
+        e = np.zeros((n, d), order="F")
+        lp = np.zeros(n) if lpd else None
+        st = np.zeros((4 + len(thr), n_trk)) if stats else None                          # element (t, k) at t + n_tracks k
+        self._check(self.lib.ssde_smooth_loo(self._h, par.ctypes.data_as(_dp), self.n_par_full, mean.ctypes.data_as(_dp),
+                                             V.ctypes.data_as(_dp) if cov else None, e.ctypes.data_as(_dp),
+                                             lp.ctypes.data_as(_dp) if lpd else None, thr.ctypes.data_as(_dp) if len(thr) else None,
+                                             len(thr), st.ctypes.data_as(_dp) if stats else None, 0))
+        return {"mean": mean, "cov": V, "resid": e, "lpd": lp, "stats": None if st is None else st.T}
 
     def smooth_draws(self, par, n_draws: int, seed: int = 0, draw0: int = 0, out=None):
         """Joint posterior draws of the whole state path at `par` (ssde_smooth_draws): an array of shape

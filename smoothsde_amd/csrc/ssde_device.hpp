@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/ssde.h"      // SSDE_LOO_MAX_THR: the one definition
 #include "ssde_gain_feed.hpp"
 #include "ssde_math.hpp"
 #include "ssde_occ.hpp"
@@ -696,6 +697,24 @@ struct SmoothArgs {
 int smooth_rec_doubles(int model, int d);
 hipError_t launch_smooth_back(const SmoothArgs& a, hipStream_t s);
 hipError_t launch_smooth_tv_record(const TvArgs& t, const SmoothArgs& a, hipStream_t s);   // PATH_TV: lane = track, long-format rows
+// ---- leave-one-out residuals and predictive densities (k_smooth_loo.hip, ssde_loo.hpp) ----
+// The records, groups and lanes of a SmoothArgs `s` (its outputs are not read), walked back once.  Per-row outputs in the long layout
+// of s.n_out rows, each may be NULL; per-track statistics (n_stat = 4 + n_thr) at stats + lane_trk[l] + n_trk * k, preset by the
+// caller, written once per lane.  The thresholds travel by value (64 B of uniform operands).
+struct LooArgs {
+    SmoothArgs s;
+    const int64_t* lane_trk;     // [groups * 64]: the lane's ID segment in the handle's data (ssde_handle::lane_seg)
+    const int64_t* row_map;      // as PathArgs
+    double* mean;                // [n_out x d] or NULL
+    double* cov;                 // [n_out x d x d] or NULL
+    double* resid;               // [n_out x d] or NULL
+    double* lpd;                 // [n_out] or NULL
+    double* stats;               // [n_trk x n_stat] or NULL
+    int64_t n_trk;               // the handle's ID segments
+    int n_thr;
+    double thr[SSDE_LOO_MAX_THR];
+};
+hipError_t launch_smooth_loo(const LooArgs& a, hipStream_t s);
 // ---- joint posterior draws of the state path (k_smooth_draws.hip, ssde_draws.hpp) ----
 // The records, groups and lanes of a SmoothArgs `s` (its outputs are not read); a batch of n_draws draws, number draw0 + k of the
 // stream `seed`, draw k one [n_out x sdim] matrix at out + k * draw_stride (n_out * sdim, or more where the columns sit inside a wider

@@ -4,7 +4,8 @@
 // on the device, and ssde_predict_draws: the drawn paths refined between and after the rows,
 // and ssde_path_occupancy_fine: the occupancy grids of the refined paths, and ssde_path_proximity: those states of
 // two tracks paired and reduced per pair and draw, and ssde_path_speed: the speed along the drawn paths of a CTCRW
-// reduced per track and draw and counted per row.
+// reduced per track and draw and counted per row, and ssde_smooth_loo: the leave-one-out residuals and predictive
+// densities of every fix, from the records walked back once.
 //
 // A forward pass in record mode (dense_kernel MODE 2 on the tiled routes, smooth_tv_record_kernel on PATH_TV) writes every state
 // row's record, smooth_back_kernel walks them back and writes the smoothed mean, covariance and whitened innovation in the long
@@ -399,6 +400,81 @@ int speed_sharded(ssde_handle* parent, const double* par, uint64_t seed, int64_t
         track0 += m;
     }
     return SSDE_OK;
+}
+
+// ---- ssde_smooth_loo ----------------------------------------------------------------------------------------------------------
+// One engine's leave-one-out outputs into host memory (each may be NULL): smooth_single's run -- the same records, chunks of whole
+// groups under the same budget, outputs preset to NaN by a 0xff memset, the lattice gather through pad_row -- with
+// k_smooth_loo.hip's kernel walking the records back.  The statistics [n_seg x n_stat] are preset to what a track without a served
+// row gives (0, 0, NaN, NaN, zero counts) and written once per track by the lane that owns it; on a lattice-padded handle the row of
+// a maximum is the caller's through the lattice row -> caller row map of ssde_path_speed.
+int loo_single(ssde_handle* h, const double* par, double* loo_mean, double* loo_cov, double* loo_resid, double* lpd, const double* thr,
+               int n_thr, double* stats) {
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(0));
+    const int d = h->d;
+    const int64_t nt = RecordRun::rows(h), n = h->n, n_trk = h->n_seg;
+    const int n_stat = 4 + n_thr;
+    DevBuf<double> mb, cb, eb, lb, sb;
+    DevBuf<int64_t> map;
+    Release guard(mb, cb, eb, lb, sb, map);
+    // the outputs, NaN (all bits set) where no served row writes; before the run's set-up, whose default budget is what they leave free
+    auto preset = [&](double* want, DevBuf<double>& b, size_t ncol) -> int {
+        if (!want) return SSDE_OK;
+        HIPCHK(h, b.alloc(std::max<size_t>((size_t)nt * ncol, 1)));
+        if (nt > 0) HIPCHK(h, hipMemset(b.p, 0xff, (size_t)nt * ncol * 8));
+        return SSDE_OK;
+    };
+    if (int st = preset(loo_mean, mb, (size_t)d)) return st;
+    if (int st = preset(loo_cov, cb, (size_t)d * d)) return st;
+    if (int st = preset(loo_resid, eb, (size_t)d)) return st;
+    if (int st = preset(lpd, lb, 1)) return st;
+    if (stats && n_trk > 0) {
+        HIPCHK(h, sb.alloc((size_t)n_trk * n_stat));
+        HIPCHK(h, hipMemset(sb.p, 0, (size_t)n_trk * n_stat * 8));
+        HIPCHK(h, hipMemset(sb.p + (size_t)n_trk * 2, 0xff, (size_t)n_trk * 2 * 8));
+    }
+    RecordRun run;
+    if (int st = run.setup(h, par, "ssde_smooth_loo")) return st;
+    if (stats && (int64_t)h->lane_seg.n < run.n_lanes) { h->err = "ssde_smooth_loo: the handle holds no track ordinals for its lanes"; return SSDE_ERR_ARG; }
+    LooArgs a;
+    memset(&a, 0, sizeof(a));
+    if (nt != n) {                                                      // the caller's row OF each lattice row
+        HIPCHK(h, map.alloc((size_t)nt));
+        HIPCHK(h, launch_path_row_map(h->pad_row.p, n, nt, map.p, 0));
+        a.row_map = map.p;
+    }
+    a.lane_trk = h->lane_seg.p;
+    a.mean = mb.p; a.cov = cb.p; a.resid = eb.p; a.lpd = lb.p;
+    a.stats = (stats && n_trk > 0) ? sb.p : nullptr; a.n_trk = n_trk; a.n_thr = n_thr;
+    for (int k = 0; k < n_thr; k++) a.thr[k] = thr[k];
+    for (size_t c = 0; c < run.n_chunks(); c++) {
+        int st = run.produce(c);
+        if (st) return st;
+        a.s = run.s;
+        HIPCHK(h, launch_smooth_loo(a, 0));
+    }
+    // back to the caller's rows (a lattice-padded handle: the lattice row OF each caller row), then to the host
+    auto fetch = [&](DevBuf<double>& src, int ncol, double* dst) -> int {
+        if (!dst || n == 0) return SSDE_OK;
+        if (nt != n) {
+            DevBuf<double> rows;
+            Release g2(rows);
+            HIPCHK(h, rows.alloc((size_t)n * ncol));
+            HIPCHK(h, launch_lattice_gather(h->pad_row.p, src.p, n, nt, ncol, rows.p, 0));
+            HIPCHK(h, hipMemcpy(dst, rows.p, (size_t)n * ncol * 8, hipMemcpyDeviceToHost));
+        } else {
+            HIPCHK(h, hipMemcpy(dst, src.p, (size_t)n * ncol * 8, hipMemcpyDeviceToHost));
+        }
+        return SSDE_OK;
+    };
+    int st = fetch(mb, d, loo_mean);
+    if (!st) st = fetch(cb, d * d, loo_cov);
+    if (!st) st = fetch(eb, d, loo_resid);
+    if (!st) st = fetch(lb, 1, lpd);
+    if (!st && stats && n_trk > 0) HIPCHK(h, hipMemcpy(stats, sb.p, (size_t)n_trk * n_stat * 8, hipMemcpyDeviceToHost));
+    if (!st) HIPCHK(h, hipStreamSynchronize(0));
+    return st;
 }
 
 // ---- ssde_path_occupancy ------------------------------------------------------------------------------------------------------
@@ -1058,6 +1134,55 @@ int smooth_sharded(ssde_handle* parent, const double* par, double* a_smooth, dou
     return SSDE_OK;
 }
 
+// the shards' and column pairs' leave-one-out outputs, placed as smooth_sharded places the smoother's: a pair's columns (and its
+// diagonal block of the covariance; the cross-pair blocks are exactly zero) in the parent's wider layout, a track shard's rows and
+// tracks at their places.  lpd and stats are asked of track shards only (the entry refuses them on column pairs); the row of a
+// maximum, which a shard counts in its own rows, is moved to the parent's rows.
+int loo_sharded(ssde_handle* parent, const double* par, double* loo_mean, double* loo_cov, double* loo_resid, double* lpd,
+                const double* thr, int n_thr, double* stats) {
+    const int64_t n = parent->n, NT = parent->n_seg;
+    const int D = parent->d, per = parent->model == SSDE_MODEL_CTCRW ? 2 : 1, n_stat = 4 + n_thr;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    if (loo_mean) std::fill(loo_mean, loo_mean + (size_t)n * D, nan);
+    if (loo_cov) std::fill(loo_cov, loo_cov + (size_t)n * D * D, 0.0);           // cross-pair blocks: zero
+    if (loo_resid) std::fill(loo_resid, loo_resid + (size_t)n * D, nan);
+    if (lpd) std::fill(lpd, lpd + (size_t)n, nan);
+    std::vector<char> any(loo_cov ? (size_t)n : 0, 0);                           // rows some engine served
+    int64_t track0 = 0;
+    for (size_t k = 0; k < parent->shards.size(); k++) {
+        ssde_handle* sh = parent->shards[k];
+        const int64_t lo = parent->shard_row0[k], m = parent->shard_nrows[k], mt = sh->n_seg;
+        const int d = sh->d, r0 = parent->shard_col0[k] / per;
+        std::vector<double> tm(loo_mean ? (size_t)m * d : 0), tc(loo_cov ? (size_t)m * d * d : 0), te(loo_resid ? (size_t)m * d : 0),
+            tl(lpd ? (size_t)m : 0), ts(stats ? (size_t)mt * n_stat : 0);
+        int st = ssde_smooth_loo(sh, par, parent->L.n_full, loo_mean ? tm.data() : nullptr, loo_cov ? tc.data() : nullptr,
+                                 loo_resid ? te.data() : nullptr, lpd ? tl.data() : nullptr, thr, n_thr, stats ? ts.data() : nullptr, 0);
+        if (st) { parent->err = sh->err; return st; }
+        for (int c = 0; c < d && loo_mean; c++) memcpy(loo_mean + (size_t)(r0 + c) * n + lo, tm.data() + (size_t)c * m, (size_t)m * 8);
+        for (int c = 0; c < d && loo_resid; c++) memcpy(loo_resid + (size_t)(r0 + c) * n + lo, te.data() + (size_t)c * m, (size_t)m * 8);
+        if (lpd) memcpy(lpd + lo, tl.data(), (size_t)m * 8);
+        if (loo_cov) {
+            for (int c = 0; c < d; c++)
+                for (int r = 0; r < d; r++)
+                    memcpy(loo_cov + (size_t)n * ((r0 + r) + (size_t)D * (r0 + c)) + lo, tc.data() + (size_t)m * (r + (size_t)d * c), (size_t)m * 8);
+            for (int64_t i = 0; i < m; i++)
+                if (!std::isnan(tc[i])) any[(size_t)(lo + i)] = 1;
+        }
+        if (stats) {
+            for (int q = 0; q < n_stat; q++) memcpy(stats + (size_t)NT * q + track0, ts.data() + (size_t)mt * q, (size_t)mt * 8);
+            // (whole numbers below 2^53, so adding the shard's first row is exact; NaN stays NaN)
+            for (int64_t i = 0; i < mt; i++) stats[(size_t)NT * 3 + track0 + i] += (double)lo;
+            track0 += mt;
+        }
+    }
+    // a row no engine served has no covariance at all; where the pairs disagree, the blocks of those that did not serve it are NaN
+    // already (their own preset), the cross-pair zeros stand
+    for (int64_t i = 0; loo_cov && i < n; i++)
+        if (!any[(size_t)i])
+            for (int q = 0; q < D * D; q++) loo_cov[(size_t)n * q + i] = nan;
+    return SSDE_OK;
+}
+
 // the shards' and column pairs' draws, each counted by the GLOBAL track ordinal and state column, placed in the parent's layout
 int draws_sharded(ssde_handle* parent, const double* par, uint64_t seed, int64_t draw0, int n_draws, double* draws, bool dev_out) {
     const int64_t n = parent->n;
@@ -1406,6 +1531,32 @@ int ssde_smooth(ssde_handle* h, const double* par, int32_t n_par_full, double* a
     if (int st = check_kalman(h)) return st;
     if (!h->shards.empty()) return smooth_sharded(h, par, a_smooth, P_smooth, resid);
     return smooth_single(h, par, a_smooth, P_smooth, resid);
+}
+
+int ssde_smooth_loo(ssde_handle* h, const double* par, int32_t n_par_full, double* loo_mean, double* loo_cov, double* loo_resid,
+                    double* lpd, const double* thr, int32_t n_thr, double* stats, uint32_t flags) {
+    if (!h || !par || (!loo_mean && !loo_cov && !loo_resid && !lpd && !stats)) {
+        if (h) h->err = "ssde_smooth_loo: no parameter vector, or no output asked for";
+        return SSDE_ERR_ARG;
+    }
+    if (int st = check_par_len(h, n_par_full)) return st;
+    if (n_thr < 0 || n_thr > SSDE_LOO_MAX_THR || (n_thr > 0 && !thr)) {
+        h->err = "ssde_smooth_loo: 0 <= n_thr <= SSDE_LOO_MAX_THR, with a table of thresholds when there are any";
+        return SSDE_ERR_ARG;
+    }
+    for (int k = 0; k < n_thr; k++)
+        if (!std::isfinite(thr[k]) || thr[k] < 0.0) { h->err = "ssde_smooth_loo: a threshold that is not finite or negative"; return SSDE_ERR_ARG; }
+    if (n_thr > 0 && !stats) { h->err = "ssde_smooth_loo: thresholds are counted in the statistics, which were not asked for"; return SSDE_ERR_ARG; }
+    if (flags != 0) { h->err = "ssde_smooth_loo: unknown flag"; return SSDE_ERR_ARG; }
+    if (int st = check_kalman(h)) return st;
+    if (!h->shards.empty()) {
+        if ((lpd || stats) && std::max(h->n_dim_parts, 1) > 1) {
+            h->err = "ssde_smooth_loo: lpd and stats are not served for an uncoupled wide response run as column pairs (they need a per-row sum across the pair handles); loo_mean, loo_cov and loo_resid are";
+            return SSDE_ERR_MODEL;
+        }
+        return loo_sharded(h, par, loo_mean, loo_cov, loo_resid, lpd, thr, n_thr, stats);
+    }
+    return loo_single(h, par, loo_mean, loo_cov, loo_resid, lpd, thr, n_thr, stats);
 }
 
 }  // extern "C"

@@ -483,6 +483,37 @@ class SDE:
         out = self.engine_.smooth(self._current_par_full(), cov=cov, resid=False)
         return {"mean": out["mean"], "cov": out["cov"]}
 
+    def loo(self, thresholds=None):
+        """Leave-one-out check of a state-space model (CTCRW, OU_SSM, BM_SSM) at the current parameters (ssde_smooth_loo, DESIGN.md
+        §3.20): every fix predicted from all the OTHER fixes of its track, without a refit.  Returns {"mean": n x d, "cov": n x d x d,
+        "resid": n x d whitened deletion residuals, "lpd": n log predictive densities, "stats": n_tracks x (4 + n_thr), "elpd": the
+        sum of the tracks' leave-one-out scores (stats column 1) -- a cross-validation score that compares the three models on
+        the same data}.  NaN on rows without a fix to leave out (a track's first row, missing rows)."""
+        if self.type_ not in ("CTCRW", "OU_SSM", "BM_SSM"):
+            raise NotImplementedError(f"loo: no latent state in the model {self.type_!r}")
+        out = self.engine_.smooth_loo(self._current_par_full(), cov=True, thresholds=thresholds)
+        out["elpd"] = float(np.sum(out["stats"][:, 1]))
+        return out
+
+    def outliers(self, level=0.999):
+        """The rows of the data whose deletion residual is improbably large: q_j = |resid_j|^2 of loo() above the chi-square
+        quantile `level` with d degrees of freedom.  Returns {"rows": their 0-based rows, ascending, "q": their q_j, "threshold":
+        the quantile, "counts": per track the number of such rows}.  The rows come from q_j formed here from "resid", the counts from
+        the q_j the device formed in its own arithmetic (the last bit may differ): a q_j within rounding of the quantile can be in one
+        and not in the other."""
+        if self.type_ not in ("CTCRW", "OU_SSM", "BM_SSM"):
+            raise NotImplementedError(f"outliers: no latent state in the model {self.type_!r}")
+        if not 0.0 < level < 1.0:
+            raise ValueError("level must lie strictly between 0 and 1")
+        from scipy.stats import chi2
+        d = self.engine_.problem.n_dim
+        thr = float(chi2.ppf(level, d))
+        out = self.engine_.smooth_loo(self._current_par_full(), cov=False, thresholds=[thr])
+        q = np.sum(out["resid"] ** 2, axis=1)
+        with np.errstate(invalid="ignore"):
+            rows = np.nonzero(q > thr)[0]
+        return {"rows": rows, "q": q[rows], "threshold": thr, "counts": out["stats"][:, 4].astype(np.int64)}
+
     def _rows_and_offsets(self, ID, time):
         """(rows, offsets) of the queries (ID[k], time[k]): the last row of track ID[k] with a time stamp <= time[k] and the time past
         it; row -1 for an unknown ID, a time that is not finite or one before the track's first time stamp."""
