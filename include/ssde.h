@@ -712,8 +712,14 @@ int ssde_comm_init_rank(ssde_handle *h, int32_t n_ranks, int32_t rank, const voi
  *       statistics built for that cut (every multiple of 16 from 32 to 128).  Setting it builds those statistics, synchronously, on a
  *       handle that holds the late ones and not yet these; a handle without lag statistics ignores it.  0 = the cut at row 256 only.
  *       Default: 1 exactly when ssde_create built the early cuts -- where its dispatch rule itself built the lag statistics and the response
- *       has two coordinates --, else 0 (with one coordinate the head of the late cut is the faster launch: DESIGN.md §3.3d). */
-enum { SSDE_OPT_KERNEL_STAMPS = 1, SSDE_OPT_COMM_DEFER = 2, SSDE_OPT_SMOOTH_BUDGET_MB = 3, SSDE_OPT_LAG_EARLY = 4 };
+ *       has two coordinates --, else 0 (with one coordinate the head of the late cut is the faster launch: DESIGN.md §3.3d).
+ *   SSDE_OPT_LAG_HEAD_HOST: 1 = a synchronous single-device ssde_eval whose bulk is cut early forms the head's accumulators on the host,
+ *       from Gram statistics of the first 128 rows of every track, and launches nothing (ssde_last_head_form).  Setting it
+ *       builds those statistics, synchronously, on a handle that holds lag statistics and not yet these (CTCRW, two coordinates, every
+ *       track at least 128 rows; any other handle ignores it).  0 = the head stays a launch.  Every other caller (ssde_eval_device, stamped
+ *       evaluations, shards, a communicator) keeps the launch whatever the option says.  Default: 1 exactly when ssde_create built
+ *       those statistics -- where it built the early cuts by its own dispatch rule --, else 0. */
+enum { SSDE_OPT_KERNEL_STAMPS = 1, SSDE_OPT_COMM_DEFER = 2, SSDE_OPT_SMOOTH_BUDGET_MB = 3, SSDE_OPT_LAG_EARLY = 4, SSDE_OPT_LAG_HEAD_HOST = 5 };
 int ssde_set_option(ssde_handle *h, int32_t option, int64_t value);
 
 /* Sum buf_dev[0 .. count) (doubles, HBM) over the ranks of the communicator `h` joined, in place, on `stream` (enqueue only:
@@ -965,6 +971,26 @@ int ssde_lagstats_read_cut(const ssde_handle *h, int32_t cut, double *M, double 
 /* The first bulk row of the handle's last evaluation: 256 or an early cut where rows came from the lag statistics, 0 where every row
    was streamed.  A multi-device parent reports its first shard; -1 for NULL. */
 int ssde_last_lag_cut(const ssde_handle *h);
+/* The Gram statistics of the head's rows (129 components, the count in *n_comp): per track and coordinate
+   w = (x0 - y_0, v0, y_1 - y_0, .., y_127 - y_126) of the tiled rows y and the track's a0 row; G = sum w w' [129][129] over tracks and
+   coordinates, s [2][129] = sum w per coordinate, n = the tracks.  ssde_headstats_host: the host reference, track by track (y:
+   [track][row][coordinate], rows[track] rows each, one track after the other; a0: [track][2 d]); *built = 0 and nothing summed where a
+   track has fewer than 128 rows; y == NULL: only *n_comp is written.  ssde_headstats_read: what the handle built on the device (at
+   create, or at ssde_set_option(SSDE_OPT_LAG_HEAD_HOST, 1)); SSDE_ERR_ARG where it holds none (also a multi-device parent: ask its shards). */
+int ssde_headstats_host(const double *y, const int64_t *rows, const double *a0, int64_t n_tracks, int d, double *G, double *s, double *n,
+                        int32_t *built, int32_t *n_comp);
+int ssde_headstats_read(const ssde_handle *h, double *G, double *s, double *n);
+/* The head's 4 + d accumulators of one evaluation from those statistics, on the host (csrc/ssde_headforms.hpp): CTCRW, d = 2, on a regular
+   grid of step dt at theta = (log sigma_obs, mu_1, mu_2, log tau, log nu), rows [0, cut) of every track, cut 1 .. 128; p0: the initial
+   covariance (p11, p12, p22) or NULL for (1, 0, 1); mask: DIR_* bits of the directions wanted, < 0 for all; full_probes != 0: every column
+   of the response by its own run instead of the shifted-column shortcut (the same numbers: a test).  acc: [6].  gain_out (or NULL):
+   [cut][16] the gain row of every head row; trans_out (or NULL): e, t12, b1, b2, de, dt12 of the step; n_probe (or NULL): the columns
+   that ran.  SSDE_ERR_ARG: a NULL pointer, d != 2, a cut outside the range, a table row that is not scored. */
+int ssde_headforms_host(const double *G, const double *s, double n_tracks, int32_t d, const double *theta, double dt, const double *p0,
+                        int32_t cut, int32_t mask, int32_t full_probes, double *acc, double *gain_out, double *trans_out, int32_t *n_probe);
+/* The head of the handle's last evaluation: 0 a launch, 1 the statistics on the host (SSDE_OPT_LAG_HEAD_HOST).  A multi-device parent
+   reports its first shard; -1 for NULL. */
+int ssde_last_head_form(const ssde_handle *h);
 
 #ifdef __cplusplus
 }

@@ -96,7 +96,7 @@ class SsdeSimrowsDesc(C.Structure):
                 ("n_thr", C.c_int32), ("reserved2", C.c_int32)]
 
 
-OPT_KERNEL_STAMPS, OPT_COMM_DEFER, OPT_SMOOTH_BUDGET_MB, OPT_LAG_EARLY = 1, 2, 3, 4
+OPT_KERNEL_STAMPS, OPT_COMM_DEFER, OPT_SMOOTH_BUDGET_MB, OPT_LAG_EARLY, OPT_LAG_HEAD_HOST = 1, 2, 3, 4, 5
 LAG_CUTS = tuple(range(32, 129, 16))   # the early cuts of the lag statistics (csrc/ssde_lagstats.hpp)
 # ssde_info_t.kernel_id (include/ssde.h: SSDE_KERNEL_*): the kernel family that ran the rows of the last evaluation
 KERNEL_NAMES = {0: "none", 1: "direct_kernel", 2: "direct_fast_kernel", 3: "iso_shared_kernel", 4: "iso_mask_kernel",
@@ -573,6 +573,15 @@ def load_library():
     lib.ssde_lagstats_host_cut.restype = C.c_int
     lib.ssde_lagstats_read_cut.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _dp]
     lib.ssde_lagstats_read_cut.restype = C.c_int
+    lib.ssde_headstats_host.argtypes = [_dp, C.POINTER(C.c_int64), _dp, C.c_int64, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.ssde_headstats_host.restype = C.c_int
+    lib.ssde_headstats_read.argtypes = [C.c_void_p, _dp, _dp, _dp]
+    lib.ssde_headstats_read.restype = C.c_int
+    lib.ssde_headforms_host.argtypes = [_dp, _dp, C.c_double, C.c_int32, _dp, C.c_double, _dp, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp,
+                                        C.POINTER(C.c_int32)]
+    lib.ssde_headforms_host.restype = C.c_int
+    lib.ssde_last_head_form.argtypes = [C.c_void_p]
+    lib.ssde_last_head_form.restype = C.c_int
     lib.ssde_last_lag_cut.argtypes = [C.c_void_p]
     lib.ssde_last_lag_cut.restype = C.c_int
     lib.ssde_lagforms_host_m.argtypes = [C.c_int32, _dp, _dp, C.c_double, _dp, C.c_int32, _dp, C.c_double, _dp, C.c_int32, C.c_int32,
@@ -643,7 +652,8 @@ EXPORTED_SYMBOLS = ("ssde_create", "ssde_eval", "ssde_eval_device", "ssde_penalt
                     "ssde_info", "ssde_destroy", "ssde_last_error", "ssde_abi_version", "ssde_comm_unique_id", "ssde_comm_init_rank", "ssde_forget", "ssde_laplace_eval", "ssde_last_kernel_ms", "ssde_kernel_ms_history",
                     "ssde_simulate", "ssde_par_bands", "ssde_simulate_rows", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth", "ssde_smooth_loo", "ssde_smooth_draws", "ssde_predict", "ssde_predict_draws", "ssde_path_stats", "ssde_path_speed", "ssde_path_occupancy", "ssde_last_occupancy_form", "ssde_path_occupancy_fine", "ssde_last_occupancy_points", "ssde_last_hess_plan", "ssde_path_proximity", "ssde_last_proximity_plan",
                     "ssde_lagstats_host_m", "ssde_lagstats_read_m", "ssde_lagforms_host_m", "ssde_reduce_host", "ssde_last_finish_form", "ssde_last_gain_feed", "ssde_last_gain_rows",
-                    "ssde_lagstats_host_cut", "ssde_lagstats_read_cut", "ssde_last_lag_cut")
+                    "ssde_lagstats_host_cut", "ssde_lagstats_read_cut", "ssde_last_lag_cut",
+                    "ssde_headstats_host", "ssde_headstats_read", "ssde_headforms_host", "ssde_last_head_form")
 
 
 def reduce_host(sums, group_chk, n_out, map_, lag_acc=None, lag_chk=0.0, add=None, add_slot=None):
@@ -711,6 +721,52 @@ def lagstats_host_cut(tracks, cut):
     if st != 0:
         raise ValueError(f"ssde_lagstats_host_cut: status {st}")
     return M, s, float(n[0])
+
+
+def head_components():
+    """components of the head's Gram statistics (129: the two of a0 and the 127 increments of the first 128 rows)"""
+    nc = C.c_int32(0)
+    load_library().ssde_headstats_host(None, None, None, 0, 2, None, None, None, None, C.byref(nc))
+    return int(nc.value)
+
+
+def headstats_host(tracks, a0):
+    """The Gram statistics of the head's rows on the host: `tracks` a list of (rows x d) arrays of tiled rows, `a0`
+    (tracks x 2 d) their initial states.  Returns (G, s, n), or None where a track is shorter than the statistics' 128 rows (not built)."""
+    lib = load_library()
+    nw = head_components()
+    d = int(tracks[0].shape[1])
+    y = np.ascontiguousarray(np.concatenate([np.asarray(t, dtype=np.float64) for t in tracks]))
+    rows = np.array([t.shape[0] for t in tracks], dtype=np.int64)
+    a0 = np.ascontiguousarray(a0, dtype=np.float64)
+    if a0.shape != (len(tracks), 2 * d):
+        raise ValueError("headstats_host: a0 is tracks x 2 d")
+    G = np.zeros((nw, nw)); s = np.zeros((2, nw)); n = np.zeros(1); built = C.c_int32(0)
+    st = lib.ssde_headstats_host(y.ctypes.data_as(_dp), rows.ctypes.data_as(C.POINTER(C.c_int64)), a0.ctypes.data_as(_dp), len(tracks), d,
+                                 G.ctypes.data_as(_dp), s.ctypes.data_as(_dp), n.ctypes.data_as(_dp), C.byref(built), None)
+    if st != 0:
+        raise ValueError(f"ssde_headstats_host: status {st}")
+    return (G, s, float(n[0])) if built.value else None
+
+
+def headforms_host(G, s, n_tracks, theta, dt, cut, p0=None, mask=-1, full_probes=False):
+    """The head's accumulators of one evaluation from its Gram statistics, on the host: CTCRW, d = 2, theta =
+    (log sigma_obs, mu_1, mu_2, log tau, log nu), rows [0, cut).  Returns a dict: acc (6), gain (cut x 16: the gain row of every head
+    row), trans (e, t12, b1, b2, de, dt12), n_probe (the response columns that ran as probes)."""
+    lib = load_library()
+    G = np.ascontiguousarray(G, dtype=np.float64); s = np.ascontiguousarray(s, dtype=np.float64)
+    theta = np.ascontiguousarray(theta, dtype=np.float64)
+    nw = head_components()
+    if G.shape != (nw, nw) or s.shape != (2, nw) or theta.size != 5:
+        raise ValueError("headforms_host: shapes")
+    p0a = None if p0 is None else np.ascontiguousarray(np.atleast_1d(p0), dtype=np.float64)
+    acc = np.zeros(6); gain = np.zeros((int(cut), 16)); trans = np.zeros(6); npb = C.c_int32(0)
+    st = lib.ssde_headforms_host(G.ctypes.data_as(_dp), s.ctypes.data_as(_dp), float(n_tracks), 2, theta.ctypes.data_as(_dp), float(dt),
+                                 None if p0a is None else p0a.ctypes.data_as(_dp), int(cut), int(mask), 1 if full_probes else 0,
+                                 acc.ctypes.data_as(_dp), gain.ctypes.data_as(_dp), trans.ctypes.data_as(_dp), C.byref(npb))
+    if st != 0:
+        raise ValueError(f"ssde_headforms_host: status {st}")
+    return {"acc": acc, "gain": gain, "trans": trans, "n_probe": int(npb.value)}
 
 
 def lagforms_host(M, s, n_bulk, theta, dt, K, d=None, p0=None, mask=-1, taps=None, model="CTCRW", ref=None):
@@ -1189,6 +1245,17 @@ class Engine:
 
     def set_option(self, option: int, value: int):
         self._check(self.lib.ssde_set_option(self._h, option, value))
+
+    def last_head_form(self) -> int:
+        """the head of the last evaluation: 0 a launch, 1 its Gram statistics on the host (OPT_LAG_HEAD_HOST)"""
+        return int(self.lib.ssde_last_head_form(self._h))
+
+    def headstats(self):
+        """(G, s, n) of the head's Gram statistics the handle built (ssde_headstats_read; the host reference is headstats_host)"""
+        nw = head_components()
+        G = np.zeros((nw, nw)); s = np.zeros((2, nw)); n = np.zeros(1)
+        self._check(self.lib.ssde_headstats_read(self._h, G.ctypes.data_as(_dp), s.ctypes.data_as(_dp), n.ctypes.data_as(_dp)))
+        return G, s, float(n[0])
 
     def last_finish_form(self) -> int:
         """What finished the last evaluation: 0 a finalize launch, 1 the main launch itself, 2 the host."""

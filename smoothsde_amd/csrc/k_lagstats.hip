@@ -4,6 +4,7 @@
 // compile-time modes: the increments y_t - y_{t-1} (CTCRW, BM_SSM) and the levels y_t - ref (OU_SSM).
 #include "ssde_device.hpp"
 #include "ssde_lagstats.hpp"
+#include "ssde_headforms.hpp"
 
 namespace ssde {
 
@@ -186,6 +187,52 @@ __global__ __launch_bounds__(WG_WAVES * WAVE) void lag_ends_kernel(const TileVie
         for (int a = 0; a < 2; a++) sg[((int64_t)g * 2 + a) * LAG_N + p] = a < d ? sacc[a] : 0.0;
 }
 
+// The Gram statistics of the head's rows (ssde_headforms.hpp): per (track, coordinate) the vector w = (x0 - y_0, v0, the increments of
+// rows 1 .. HEAD_C - 1), HEAD_NW components; G_pq = sum w_p w_q of one group for 64 rows p x 64 columns q, in lag_ends_kernel's
+// geometry and layout (LAG_N x LAG_N per group, zeros past HEAD_NW): one wave per (group, p block, q block), lane = p, the group's
+// tracks and coordinates one after the other (fixed order), column q's values broadcast from the lane that loaded them.  The
+// q block 0 waves also sum s_{a,p} = sum w_{a,p}.  A lane whose track has fewer than HEAD_C rows contributes nothing (the engine
+// builds these statistics only where there is none: rows 0 .. HEAD_C - 1 of every track that is read lie inside it).
+__global__ __launch_bounds__(WG_WAVES * WAVE) void head_gram_kernel(const TileView tv, int d, double* Dg, double* sg) {
+    static_assert(HEAD_NW <= LAG_N, "the head's statistics fit the per-group temporaries of the lag statistics");
+    constexpr int PB = LAG_N / 64;
+    const int id = blockIdx.x * WG_WAVES + (threadIdx.x >> 6);
+    const int g = id / (PB * PB), pb = (id / PB) % PB, qb = id % PB;
+    if (g >= tv.n_groups) return;
+    const int lane = threadIdx.x & 63;
+    const int p = pb * 64 + lane, q = qb * 64 + lane;
+    const int C = tv.C, c_obs = tv.c_obs, SD = 2 * d;
+    const int64_t rs = (int64_t)C * WAVE;
+    double acc[64], sacc[2] = {0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < 64; k++) acc[k] = 0.0;
+    const bool any = pb * 64 < HEAD_NW && qb * 64 < HEAD_NW;          // (wave-uniform)
+    for (int m = 0; any && m < WAVE; m++) {
+        if (tv.lane_nsteps[g * WAVE + m] < HEAD_C) continue;
+        const double* bm = tv.tiles + tv.group_off[g] + m;
+        for (int a = 0; a < d; a++) {
+            const double* y = bm + (int64_t)(c_obs + a) * WAVE;
+            const double* a0 = tv.a0 + ((int64_t)g * SD + 2 * a) * WAVE + m;
+            // component i of w: rows <= i - 1 <= HEAD_C - 1 of the track
+            auto w = [&](int i) -> double {
+                if (i >= HEAD_NW) return 0.0;
+                if (i == 0) return a0[0] - y[0];
+                if (i == 1) return a0[WAVE];
+                return y[(int64_t)(i - 1) * rs] - y[(int64_t)(i - 2) * rs];
+            };
+            const double wp = w(p), wq = w(q);
+#pragma unroll
+            for (int k = 0; k < 64; k++) acc[k] = fma(wp, readlane_d(wq, k), acc[k]);
+            if (qb == 0) sacc[a] += wp;
+        }
+    }
+    double* o = Dg + ((int64_t)g * LAG_N + p) * LAG_N + qb * 64;
+#pragma unroll
+    for (int k = 0; k < 64; k++) o[k] = acc[k];
+    if (qb == 0)
+        for (int a = 0; a < 2; a++) sg[((int64_t)g * 2 + a) * LAG_N + p] = a < d ? sacc[a] : 0.0;
+}
+
 // dst[e] = sum over g (in order) of src[g * n + e]
 __global__ __launch_bounds__(256) void lag_group_sum_kernel(const double* src, int64_t n, int G, double* dst) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -236,6 +283,18 @@ hipError_t launch_lagstats_cut(const TileView& tv, int d, int cut, double* Qg, d
     hipLaunchKernelGGL((lag_toeplitz_kernel<false, true>), grid_t, block, 0, st, tv, d, Qg, ref, (double*)nullptr, cut);
     hipLaunchKernelGGL((lag_ends_kernel<false, true>), grid_e, block, 0, st, tv, d, Dg, sg, ref, cut);
     hipLaunchKernelGGL(lag_group_sum_kernel, dim3((unsigned)((LAG_N + 255) / 256)), dim3(256), 0, st, Qg, (int64_t)LAG_N, G, Q);
+    hipLaunchKernelGGL(lag_group_sum_kernel, dim3((unsigned)(((int64_t)LAG_N * LAG_N + 255) / 256)), dim3(256), 0, st, Dg, (int64_t)LAG_N * LAG_N, G, D);
+    hipLaunchKernelGGL(lag_group_sum_kernel, dim3((unsigned)((2 * LAG_N + 255) / 256)), dim3(256), 0, st, sg, (int64_t)2 * LAG_N, G, s);
+    return hipGetLastError();
+}
+
+// The Gram statistics of the head's rows (ssde_headforms.hpp) in the lag statistics' per-group temporaries: Dg [G][LAG_N][LAG_N] and
+// sg [G][2][LAG_N], summed over the groups in order into D [LAG_N][LAG_N] and s [2][LAG_N] (the leading HEAD_NW entries; zeros past them).
+hipError_t launch_headstats(const TileView& tv, int d, double* Dg, double* sg, double* D, double* s, hipStream_t st) {
+    const int G = tv.n_groups;
+    constexpr int PB = LAG_N / 64;
+    const dim3 grid_e((G * PB * PB + WG_WAVES - 1) / WG_WAVES), block(WG_WAVES * WAVE);
+    hipLaunchKernelGGL(head_gram_kernel, grid_e, block, 0, st, tv, d, Dg, sg);
     hipLaunchKernelGGL(lag_group_sum_kernel, dim3((unsigned)(((int64_t)LAG_N * LAG_N + 255) / 256)), dim3(256), 0, st, Dg, (int64_t)LAG_N * LAG_N, G, D);
     hipLaunchKernelGGL(lag_group_sum_kernel, dim3((unsigned)((2 * LAG_N + 255) / 256)), dim3(256), 0, st, sg, (int64_t)2 * LAG_N, G, s);
     return hipGetLastError();

@@ -407,6 +407,8 @@ hipError_t launch_lagstats(const TileView& tv, int d, double* Qg, double* Dg, do
                            const double* levels_ref = nullptr, double* s0g = nullptr, double* s0 = nullptr);
 // ... and of the head rows' own contribution to an early cut (CTCRW; the same buffers, the entries below the cut)
 hipError_t launch_lagstats_cut(const TileView& tv, int d, int cut, double* Qg, double* Dg, double* sg, double* Q, double* D, double* s, hipStream_t st);
+// the Gram statistics of the head's rows (ssde_headforms.hpp) in the same per-group temporaries: D [LAG_N][LAG_N], s [2][LAG_N]
+hipError_t launch_headstats(const TileView& tv, int d, double* Dg, double* sg, double* D, double* s, hipStream_t st);
 void fill_stat_consts(int model, int d, IsoArgs& a);
 int iso_nstate(int model, int d);
 

@@ -5,6 +5,7 @@
 // for the reference (/root/reference/src/init.c:6-8, R/sde.R:656-669, 694-697).
 // There is no CPU evaluation path in this library: without a gfx950 device ssde_create fails.
 #include "ssde_engine.hpp"
+#include "ssde_headforms.hpp"
 
 #include <chrono>
 #include <limits>
@@ -67,14 +68,15 @@ void release_device(ssde_handle* h) {
     h->hs_partials.release(); h->hs_hess.release(); h->hs_i16.release();
     if (h->knobs.trace && h->trace_n > 0)
         fprintf(stderr, "[ssde trace] %lld isotropic evaluations, host us per evaluation: plan %.1f | gain table %.1f | main launch %.1f | "
-                        "finalize launch %.1f | read-back (blocks until the GPU is done) %.1f\n", (long long)h->trace_n,
+                        "finalize launch %.1f | read-back (blocks until the GPU is done) %.1f | head forms %.1f\n", (long long)h->trace_n,
                 h->trace_us[0] / h->trace_n, h->trace_us[1] / h->trace_n, h->trace_us[2] / h->trace_n, h->trace_us[3] / h->trace_n,
-                h->trace_us[4] / h->trace_n);
+                h->trace_us[4] / h->trace_n, h->trace_us[5] / h->trace_n);
     destroy_dist(h);
     h->bnd.release(); h->chk.release(); h->group_flags.release(); h->gain_ring.release(); h->pad_pos.release(); h->pad_row.release(); h->dirty_groups.release(); h->lap_out.release(); h->nan_bits.release(); h->quiet_flag.release();
     h->lag_M.release(); h->lag_s.release(); h->lag_glen.release(); h->lag_ns.release();
     for (int c = 0; c < LAG_NCUT; c++) { h->lag_cut_M[c].release(); h->lag_cut_s[c].release(); h->lag_cut_glen[c].release(); h->lag_cut_ns[c].release(); h->lag_cut_nsmin[c].release(); }
     h->lag_cut_mask = 0; h->lag_early = false;
+    h->head_G.release(); h->head_s.release(); delete h->head_work; h->head_work = nullptr; h->head_ready = false; h->head_host = false;
     if (h->gain_pinned) (void)hipHostFree(h->gain_pinned);
     for (int i = 0; i < 2; i++) { if (h->aux[i]) (void)hipStreamDestroy(h->aux[i]); if (h->ev_join[i]) (void)hipEventDestroy(h->ev_join[i]); }
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
@@ -159,7 +161,7 @@ int eval_device(ssde_handle* h, const double* par, int order, double* out_dev, h
     for (int k = 0; k < MAX_PAR + 16; k++) ra.map[k] = -1;
     // (a synchronous single-engine evaluation: the head's workgroups may hand their records to the host instead -- eval_iso decides)
     h->host_finish_ok = h->pub_request && !h->knobs.publish && !h->stamps && out_dev == h->out.p;
-    h->host_armed = false;
+    h->host_armed = false; h->head_armed = false; h->last_head_form = 0;
     if (h->pub_request && h->knobs.publish && out_dev == h->out.p) {
         // a synchronous evaluation: the reducing launch publishes the result itself (ssde_device.hpp: ReduceArgs.pub)
         ra.pub = h->pub_pinned; ra.pub_flag = h->pub_flag; ra.pub_seq = ++h->pub_seq; ra.pub_count = h->pub_count.p;
@@ -339,6 +341,34 @@ int ssde_lagstats_host_cut(const double* y, const int64_t* rows, int64_t n_track
     }
     lag_assemble_cut(Q.data(), D.data(), cut, M);
     *n_bulk = n;
+    return SSDE_OK;
+}
+
+int ssde_headstats_host(const double* y, const int64_t* rows, const double* a0, int64_t n_tracks, int d, double* G, double* s, double* n,
+                        int32_t* built, int32_t* n_comp) {
+    if (n_comp) *n_comp = HEAD_NW;
+    if (!y) return SSDE_OK;                                 // (a query for the sizes)
+    if (d < 1 || d > 2 || !rows || !a0 || !G || !s || !n || !built || n_tracks < 1) return SSDE_ERR_ARG;
+    for (int i = 0; i < HEAD_NW * HEAD_NW; i++) G[i] = 0.0;
+    for (int i = 0; i < 2 * HEAD_NW; i++) s[i] = 0.0;
+    *n = 0.0; *built = 0;
+    for (int64_t k = 0; k < n_tracks; k++)
+        if (rows[k] < HEAD_C) return SSDE_OK;               // not built: a track shorter than the statistics' rows
+    int64_t off = 0;
+    for (int64_t k = 0; k < n_tracks; k++) {
+        head_track_stats(y + off * d, a0 + k * 2 * d, d, G, s);
+        off += rows[k];
+    }
+    *n = (double)n_tracks; *built = 1;
+    return SSDE_OK;
+}
+
+int ssde_headstats_read(const ssde_handle* h, double* G, double* s, double* n) {
+    if (!h || !G || !s || !n || !h->head_ready) return SSDE_ERR_ARG;
+    if (hipSetDevice(h->device) != hipSuccess) return SSDE_ERR_HIP;
+    if (hipMemcpy(G, h->head_G.p, h->head_G.n * 8, hipMemcpyDeviceToHost) != hipSuccess) return SSDE_ERR_HIP;
+    if (hipMemcpy(s, h->head_s.p, h->head_s.n * 8, hipMemcpyDeviceToHost) != hipSuccess) return SSDE_ERR_HIP;
+    *n = h->head_n;
     return SSDE_OK;
 }
 
@@ -547,6 +577,18 @@ int run_once(ssde_handle* h, const double* par, int order, double* o) {
     // launches.  Rounds 1 and 2 had measured a pinned mirror as SLOWER; that was with the stamps on and a host that
     // synchronised the stream first.)  In the engine the two measure the same (round 3, fence-free counting); the blocking copy
     // stays the default and SSDE_PUBLISH=1 selects the spin.
+    if (h->head_armed) {
+        // The head's accumulators were formed on the host from the statistics (eval_iso, ssde_headforms.hpp) and nothing was launched:
+        // the sums in the device's order, group 0's record the head, the other groups' zero.
+        h->head_armed = false;
+        const ReduceArgs& ra = h->host_ra;
+        ReduceHostArgs rh;
+        rh.sums = h->head_rec.data(); rh.group_stride = NACC_MAX; rh.chk = h->head_chk.data(); rh.chk_stride = 1;
+        rh.n_groups = h->n_groups; rh.n_windows = ra.n_value_parts; rh.nacc = ra.nacc;
+        rh.lag_acc = ra.lag_part > 0 ? ra.lag_acc : nullptr; rh.lag_chk = ra.lag_chk;
+        rh.add = ra.add; rh.add_slot = ra.add_slot; rh.map = ra.map; rh.n_out = ra.n_out;
+        reduce_host(rh, o, h->reduce_scratch);
+    } else
     if (h->host_armed) {
         // The head's workgroups store their group's record into the pinned mailbox and this evaluation's sequence number after it
         // (iso_shared_wg_kernel): wait for every group's word, then form the sums here in the device's order (ssde_reduce_host.hpp).
@@ -828,6 +870,24 @@ int ssde_set_option(ssde_handle* h, int32_t option, int64_t value) {
                 if (st != SSDE_OK) { if (e != h) h->err = e->err; return st; }
             }
             e->lag_early = value == 1 && e->lag_cut_mask != 0;
+            e->memo_order = -1;
+        }
+        h->memo_order = -1;
+        return SSDE_OK;
+    }
+    if (option == SSDE_OPT_LAG_HEAD_HOST) {
+        if (value != 0 && value != 1) { h->err = "SSDE_OPT_LAG_HEAD_HOST: 0 or 1"; return SSDE_ERR_ARG; }
+        // 1: the head's statistics are built now where the handle holds the lag statistics and not yet these (synchronously); an engine
+        // they cannot be built for (another model, one response coordinate, a track shorter than their rows) keeps its kernel
+        std::vector<ssde_handle*> engines(h->shards.begin(), h->shards.end());
+        if (engines.empty()) engines.push_back(h);
+        for (ssde_handle* e : engines) {
+            if (value == 1 && e->lag_ready && !e->head_ready) {
+                if (hipSetDevice(e->device) != hipSuccess) { h->err = "SSDE_OPT_LAG_HEAD_HOST: hipSetDevice"; return SSDE_ERR_HIP; }
+                const int st = build_headstats(e);
+                if (st != SSDE_OK) { if (e != h) h->err = e->err; return st; }
+            }
+            e->head_host = value == 1 && e->head_ready;
             e->memo_order = -1;
         }
         h->memo_order = -1;

@@ -23,6 +23,8 @@
 #include "ssde_tv.hpp"
 #include "ssde_windows.hpp"
 
+namespace ssde { struct HeadFormWork; }     // ssde_headforms.hpp
+
 namespace ssde_engine {
 
 extern thread_local std::string g_create_error;   // message of the last failed ssde_create on this thread
@@ -334,6 +336,19 @@ struct ssde_handle {
     int lag_lead_n = 0;                    // groups g < lag_lead_n lie at g * lag_lead_stride doubles of the tiles (head_lead_groups)
     int64_t lag_lead_stride = 0;
     std::vector<int32_t> lag_host_glen, lag_host_ns;   // the uncapped lengths, kept for a later build of the early cuts
+    // The head's rows as Gram statistics (ssde_headforms.hpp; CTCRW, d = 2, every track >= HEAD_C rows): built with the early cuts where
+    // the dispatch rule builds those, or at ssde_set_option(SSDE_OPT_LAG_HEAD_HOST, 1).  A synchronous single-engine evaluation whose
+    // cut is <= HEAD_C then forms the head's accumulators on the host and launches nothing.
+    bool head_ready = false;               // the statistics exist
+    bool head_host = false;                // SSDE_OPT_LAG_HEAD_HOST: such an evaluation may take the host form
+    std::vector<double> head_G_host, head_s_host;   // [HEAD_LDW][HEAD_LDW], [2][HEAD_LDW]: zero-padded, as the forms read them
+    double head_n = 0.0;                   // tracks
+    DevBuf<double> head_G, head_s;         // the device copies ([HEAD_NW][HEAD_NW], [2][HEAD_NW]: ssde_headstats_read)
+    ssde::HeadFormWork* head_work = nullptr;   // the forms' work arrays (no allocation per evaluation)
+    std::vector<double> head_rec;          // [n_groups][NACC_MAX] the records reduce_host reads: group 0 the head's accumulators, zeros elsewhere
+    std::vector<double> head_chk;          // [n_groups] zeros: one window has no hand-over
+    bool head_armed = false;               // the evaluation just planned ends in head_rec (set by eval_iso, consumed by run_once)
+    int last_head_form = 0;                // the head of the last evaluation: 0 the kernel, 1 the statistics (ssde_last_head_form)
     int last_lag_cut = 0;                  // first bulk row of the last evaluation (0: streamed)
     int last_cut_parts = 0;                // > 0: its head ran as this many direction parts per group, one workgroup per padded group (iso_shared_cut_kernel)
     int last_kernel_id = 0;                   // SSDE_KERNEL_*: the family that ran the last evaluation's rows
@@ -378,6 +393,7 @@ int fail(ssde_handle* h, int code, const std::string& msg);
 int build(const ssde_desc* d, ssde_handle* h, const ParLayout* part_layout = nullptr);
 void destroy(ssde_handle* h);
 int build_lagstats_early(ssde_handle* h);     // the lag statistics at the early cuts (create, ssde_set_option(SSDE_OPT_LAG_EARLY, 1))
+int build_headstats(ssde_handle* h);          // the Gram statistics of the head's rows (create, ssde_set_option(SSDE_OPT_LAG_HEAD_HOST, 1))
 void attach_hess_companion(const ssde_desc* desc, ssde_handle* h);     // SSDE_FLAG_EXACT_HESS (ssde_engine.hip)
 void release_device(ssde_handle* h);          // everything the handle holds on the device / in pinned memory (the handle stays)
 int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipStream_t s, ReduceArgs& ra);   // ssde_engine_iso.hip

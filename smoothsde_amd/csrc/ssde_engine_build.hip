@@ -2,6 +2,7 @@
 // long format; Kalman tiles, lattice padding, clean-first dealing, drift columns), one-off upload + re-tiling, and the window /
 // buffer plan of the register path.  Nothing here runs per evaluation.
 #include "ssde_engine.hpp"
+#include "ssde_headforms.hpp"
 
 #include <chrono>
 #include <limits>
@@ -141,6 +142,8 @@ constexpr double LAG_MIN_BULK_ROWS = 4.4e6;
 constexpr double LAG_MIN_BULK_ROWS_OU_SSM = INFINITY, LAG_MIN_BULK_ROWS_BM_SSM = INFINITY;
 // SSDE_OPT_LAG_EARLY on a handle whose create built the early cuts (the dispatch rule, CTCRW, d = 2): on
 constexpr bool LAG_EARLY_DEFAULT = true;
+// SSDE_OPT_LAG_HEAD_HOST on a handle whose create built the head's statistics (the same rule): DESIGN.md §3.3d has the measurement
+constexpr bool LAG_HEAD_HOST_DEFAULT = true;
 // The statistics at the early cuts (ssde_lagstats.hpp; CTCRW): the late ones plus the head rows' own contribution, one pass per cut over
 // rows [0, LAG_A) of every track, the same fixed-order sums -- two builds give the same bits.  A device that cannot hold the
 // temporaries keeps the late cut (lag_cut_mask stays 0).  Synchronous; called at create and from ssde_set_option.
@@ -205,6 +208,58 @@ int build_lagstats_early(ssde_handle* h) {
     drop();
     HIPCHK(h, hipDeviceSynchronize());
     h->lag_cut_mask |= mask;
+    return SSDE_OK;
+}
+
+// The Gram statistics of the head's rows (ssde_headforms.hpp; k_lagstats.hip: head_gram_kernel): CTCRW with two response coordinates,
+// every track at least HEAD_C rows long (a shorter one leaves the handle as it is: the head keeps its kernel).  One pass over rows
+// [0, HEAD_C) of every track into the per-group temporaries of the lag statistics, the groups summed in order -- two builds give the same
+// bits.  A device that cannot hold the temporaries keeps the kernel.  Synchronous; called at create and from ssde_set_option.
+int build_headstats(ssde_handle* h) {
+    if (h->head_ready || !h->lag_ready || h->model != SSDE_MODEL_CTCRW || h->d != 2 || h->lag_host_ns.empty()) return SSDE_OK;
+    int64_t tracks = 0;
+    for (int32_t ns : h->lag_host_ns) {
+        if (ns > 0 && ns < HEAD_C) return SSDE_OK;
+        tracks += ns > 0 ? 1 : 0;
+    }
+    if (tracks == 0) return SSDE_OK;
+    const int G = h->n_groups;
+    TileView tv;
+    tv.tiles = h->tiles.p; tv.group_off = h->group_off.p; tv.group_len = h->group_len.p; tv.lane_nsteps = h->lane_nsteps.p;
+    tv.a0 = h->a0.p; tv.n_groups = G; tv.C = h->C; tv.c_obs = h->c_obs; tv.dt_all = h->dt_all;
+    const size_t NN = (size_t)LAG_N * LAG_N;
+    DevBuf<double> Dg, sg, sums;
+    auto drop = [&]() { Dg.release(); sg.release(); sums.release(); };
+    if (Dg.alloc((size_t)G * NN) != hipSuccess || sg.alloc((size_t)G * 2 * LAG_N) != hipSuccess || sums.alloc(NN + 2 * LAG_N) != hipSuccess) {
+        (void)hipGetLastError();
+        drop();
+        return SSDE_OK;
+    }
+    std::vector<double> host(sums.n);
+    hipError_t e = launch_headstats(tv, h->d, Dg.p, sg.p, sums.p, sums.p + NN, 0);
+    if (e == hipSuccess) e = hipMemcpy(host.data(), sums.p, host.size() * 8, hipMemcpyDeviceToHost);
+    drop();
+    if (e != hipSuccess) { h->err = std::string("head statistics: ") + hipGetErrorString(e); return SSDE_ERR_HIP; }
+    std::vector<double> Gc((size_t)HEAD_NW * HEAD_NW), sc(2 * HEAD_NW);
+    for (int p = 0; p < HEAD_NW; p++)
+        for (int q = 0; q < HEAD_NW; q++) Gc[(size_t)p * HEAD_NW + q] = host[(size_t)p * LAG_N + q];
+    for (int a = 0; a < 2; a++)
+        for (int p = 0; p < HEAD_NW; p++) sc[(size_t)a * HEAD_NW + p] = host[NN + (size_t)a * LAG_N + p];
+    h->head_G_host.assign((size_t)HEAD_LDW * HEAD_LDW, 0.0); h->head_s_host.assign(2 * HEAD_LDW, 0.0);
+    head_pad_stats(Gc.data(), sc.data(), h->head_G_host.data(), h->head_s_host.data());
+    e = h->head_G.upload(Gc);
+    if (e == hipSuccess) e = h->head_s.upload(sc);
+    if (e != hipSuccess) {                                   // (no room for the copies: the kernel stays)
+        (void)hipGetLastError();
+        h->head_G.release(); h->head_s.release();
+        return SSDE_OK;
+    }
+    if (!h->head_work) h->head_work = new (std::nothrow) HeadFormWork();
+    if (!h->head_work) { h->head_G.release(); h->head_s.release(); return SSDE_OK; }
+    h->head_rec.assign((size_t)G * NACC_MAX, 0.0); h->head_chk.assign((size_t)G, 0.0);
+    h->head_n = (double)tracks;
+    h->hbm_bytes += (int64_t)(Gc.size() + sc.size()) * 8;
+    h->head_ready = true;
     return SSDE_OK;
 }
 
@@ -281,6 +336,12 @@ static int build_lagstats(ssde_handle* h, int G, const std::vector<int32_t>& lan
         const int st = build_lagstats_early(h);
         if (st) return st;
         h->lag_early = LAG_EARLY_DEFAULT && h->lag_cut_mask != 0;
+        // ... and the head's own rows as Gram statistics, for the synchronous call that then launches nothing (ssde_headforms.hpp)
+        if (h->lag_cut_mask != 0) {
+            const int sth = build_headstats(h);
+            if (sth) return sth;
+            h->head_host = LAG_HEAD_HOST_DEFAULT && h->head_ready;
+        }
     }
     h->lag_create_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return SSDE_OK;

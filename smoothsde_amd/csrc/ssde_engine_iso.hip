@@ -3,6 +3,7 @@
 // the finalising launch (hand-over checks + fixed-order sums).  Called from eval_device (ssde_engine.hip).
 #include "ssde_engine.hpp"
 #include "ssde_lagforms.hpp"
+#include "ssde_headforms.hpp"
 #include "ssde_tf.hpp"
 
 #include <chrono>
@@ -505,6 +506,7 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
     // sent to its mailbox and forms the result on the host (run_once), every other caller gets them in device memory and a finalize
     // launch without check workgroups.  SSDE_FUSED_FINALIZE unset: this form; = 0: the two-launch form on iso_shared_kernel (A/B).
     static_assert(HEAD_WG_WAVES == WG_WAVES, "the plan credits the windows of one workgroup");
+    static_assert(HEAD_GROW == GAIN_ROW && HEAD_C == LAG_CUT_MAX && 4 + 2 <= NACC_MAX, "the head's forms read the gain table's rows and cover every early cut");
     // The bulk cut at the transient's end: window 0 alone, its direction parts on the waves of the group's workgroup
     // (iso_shared_cut_kernel) -- the same record, the same two ways out.  SSDE_FUSED_FINALIZE=0 / =1: the single wave of iso_shared_kernel
     // on that window (A/B -- bitwise the same).
@@ -519,6 +521,7 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
         a.wg_form = cut_wg ? 2 : 1;
         if (host_finish) { a.mbx = h->mbx_pinned; a.mbx_seq = ++h->mbx_seq; }
     }
+    bool head_form = false;                             // the head came from its statistics: nothing was launched
     HeadGain gv;
     gv.rows = 0;
     HeadLead lead = {nullptr, 0, 0};
@@ -575,6 +578,25 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
             // the bulk's forms, on the host: the single launch of the fused form needs them; the two-launch form computes them
             // while the head runs (below), for its finalize launch
             if (lag_K > 0 && fused) { const int st = lag_forms_into(h, a, order, lag_K, a.n_chunks, ra, lag_cut); if (st) return st; }
+            // The head from its Gram statistics (ssde_headforms.hpp): the synchronous single-engine call whose head would be the cut's
+            // workgroups finished on the host forms the same 4 + d accumulators here instead and launches nothing.  They stand in
+            // group 0's place of the reduction's order, the other groups' entries are zero.  (A table row that is not scored keeps
+            // the kernel; so does every other caller: ssde_eval_device, stamps, shards, a communicator, the wave clock.)
+            if (cut_wg && host_finish && h->head_ready && h->head_host && gain_deferred && lag_cut <= HEAD_C && !h->knobs.wave_clock && h->d == 2) {
+                const double th0 = h->knobs.trace ? tick() : 0.0;
+                HeadFormArgs hf;
+                hf.G = h->head_G_host.data(); hf.s = h->head_s_host.data(); hf.n = h->head_n; hf.cut = lag_cut; hf.d = h->d;
+                hf.mask = order >= 1 ? a.part_mask[0] : 0;
+                hf.gain = h->gain_scratch.data(); hf.gain_last = a.gain_last; hf.tr = a.ctr;
+                hf.mu[0] = a.mu[0]; hf.mu[1] = a.mu[1]; hf.full_probes = false;
+                HeadFormOut ho;
+                if (head_forms_host(hf, *h->head_work, ho)) {
+                    for (int k = 0; k < NACC_MAX; k++) h->head_rec[k] = k < 4 + h->d ? ho.acc[k] : 0.0;
+                    head_form = true;
+                }
+                if (h->knobs.trace) { const double t = tick(); h->trace_us[5] += t - th0; tk0 += t - th0; }
+            }
+            if (!head_form)
             HIPCHK(h, launch_iso_shared(h->model, h->d, b, ra, s, h->stamps ? h->ev_k0 : nullptr, h->stamps ? h->ev_k1 : nullptr,
                                         gv.rows > 0 ? &gv : nullptr, cut_wg ? &lead : nullptr));
         }
@@ -635,9 +657,10 @@ int eval_iso(ssde_handle* h, const double* par, int order, double* out_dev, hipS
     if (wg) ra.n_chk = h->n_groups;                     // (one check per group, from the main launch)
     if (!fused && lag_K > 0) { const int st = lag_forms_into(h, a, order, lag_K, a.n_chunks, ra, lag_cut); if (st) return st; }     // (the head is running: this overlaps it)
     // the hand-over checks and the final sums in one launch (unless the main launch has done them)
-    if (host_finish) { h->host_ra = ra; h->host_armed = true; }      // (run_once: the spin on the mailbox and reduce_host)
+    if (host_finish) { h->host_ra = ra; h->host_armed = !head_form; h->head_armed = head_form; }      // (run_once: the spin on the mailbox -- none where the head came from its statistics -- and reduce_host)
     else if (!fused) HIPCHK(h, launch_iso_finalize(h->model, h->d, a, ra, s));
     h->last_finish_form = host_finish ? 2 : fused ? 1 : 0;
+    h->last_head_form = head_form ? 1 : 0;
     if (h->knobs.trace) {
         const double t = tick(); h->trace_us[3] += t - tk0; h->trace_n++;
         if (h->trace_skip < 8) {                        // the first calls load code objects: not what is being measured
@@ -666,6 +689,52 @@ extern "C" int ssde_reduce_host(const double* sums, const double* group_chk, int
 extern "C" int ssde_last_finish_form(const ssde_handle* h) {
     if (!h) return -1;
     return h->shards.empty() ? h->last_finish_form : h->shards[0]->last_finish_form;
+}
+
+extern "C" int ssde_last_head_form(const ssde_handle* h) {
+    if (!h) return -1;
+    return h->shards.empty() ? h->last_head_form : h->shards[0]->last_head_form;
+}
+
+extern "C" int ssde_headforms_host(const double* G, const double* s, double n_tracks, int32_t d, const double* theta, double dt,
+                                   const double* p0, int32_t cut, int32_t mask, int32_t full_probes, double* acc, double* gain_out,
+                                   double* trans_out, int32_t* n_probe) {
+    if (!G || !s || !theta || !acc || d != 2 || cut < 1 || cut > HEAD_C || !(dt > 0.0) || !std::isfinite(dt)) return SSDE_ERR_ARG;
+    const double sig = exp(theta[0]);
+    const double h_obs = sig * sig, tau = exp(theta[1 + d]), nu = exp(theta[2 + d]);
+    CtcrwTrans tr;
+    ctcrw_trans(dt, tau, 1.0 / tau, 2.0 * nu / sqrt(M_PI * tau), tr);
+    // the gain table: the covariance half of the filter until it has stopped moving (as build_gain_table), at most the head's rows
+    std::vector<double> gain;
+    CtcrwCov<15> C;
+    if (p0) C.init(p0[0], p0[1], p0[2]); else C.init(1.0, 0.0, 1.0);
+    int last = 0, stable = 0;
+    for (int t = 0; t < HEAD_C && stable < GAIN_SETTLED_ROWS; t++) {
+        const CtcrwCov<15> prev = C;
+        CtcrwGain g;
+        ctcrw_cov_step<2, 15>(C, tr, h_obs, false, g);
+        double r[HEAD_GROW] = {g.iF, g.k1, g.k2, g.bm};
+        for (int j = 0; j < NDIRP; j++) { r[4 + j] = g.diF[j]; r[7 + j] = g.dk1[j]; r[10 + j] = g.dk2[j]; }
+        gain.insert(gain.end(), r, r + HEAD_GROW);
+        last = t;
+        stable = ctcrw_cov_settled(C, prev) ? stable + 1 : 0;
+    }
+    std::vector<double> Gp((size_t)HEAD_LDW * HEAD_LDW), sp(2 * HEAD_LDW);
+    head_pad_stats(G, s, Gp.data(), sp.data());
+    HeadFormArgs hf;
+    hf.G = Gp.data(); hf.s = sp.data(); hf.n = n_tracks; hf.cut = cut; hf.d = d;
+    hf.mask = mask < 0 ? (DIR_SIG | DIR_MU | DIR_P1 | DIR_P2) : mask;
+    hf.gain = gain.data(); hf.gain_last = last; hf.tr = tr; hf.mu[0] = theta[1]; hf.mu[1] = theta[2]; hf.full_probes = full_probes != 0;
+    std::vector<HeadFormWork> work(1);
+    HeadFormOut ho;
+    if (!head_forms_host(hf, work[0], ho)) return SSDE_ERR_ARG;      // (a row that is not scored: such an evaluation keeps the kernel)
+    for (int k = 0; k < 4 + d; k++) acc[k] = ho.acc[k];
+    if (gain_out)
+        for (int t = 0; t < cut; t++)
+            for (int k = 0; k < HEAD_GROW; k++) gain_out[(size_t)t * HEAD_GROW + k] = gain[(size_t)(t < last ? t : last) * HEAD_GROW + k];
+    if (trans_out) { trans_out[0] = tr.e; trans_out[1] = tr.t12; trans_out[2] = tr.b1; trans_out[3] = tr.b2; trans_out[4] = tr.de; trans_out[5] = tr.dt12; }
+    if (n_probe) *n_probe = ho.n_full;
+    return SSDE_OK;
 }
 
 extern "C" int ssde_last_gain_feed(const ssde_handle* h) {
