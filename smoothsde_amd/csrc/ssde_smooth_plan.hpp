@@ -1,7 +1,8 @@
 // ssde_smooth_plan.hpp -- the host-side plans of the calls that consume the smoother's records (ssde_engine_smooth.hip): how the
 // groups are cut into chunks under the budget, how many draws go into one batch, which form every wavefront group of
 // ssde_path_occupancy runs, where every query of ssde_predict lands, the distinct offsets of every slot of ssde_predict_draws, and the
-// slots, sub-steps and shares of ssde_path_occupancy_fine.
+// slots, sub-steps and shares of ssde_path_occupancy_fine; and, for a parent of several engines, which queries go to which engine and
+// where an engine's outputs land in the parent's arrays.
 // Plain C++17, no HIP: the engine uploads and launches what these return, tests/hostsim/hostsim_predict.cpp exports them to
 // tests/test_smooth_plan_host.py (hostsim_predict_draws.cpp the offsets to tests/test_predict_draws_plan_host.py, hostsim_occ_fine.cpp
 // the last to tests/test_occ_fine_plan_host.py).
@@ -11,6 +12,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <limits>
 #include <vector>
 
@@ -271,6 +273,72 @@ inline FineWeights plan_fine_weights(const QueryPlan& P, const std::vector<int64
 // each), next to the records and side rows the budget already pays for; any number of draws goes (unit 1), one always
 inline int occ_fine_batch_cap(int64_t budget, int64_t n_slots, int ez, int ch, int n_draws) {
     return batch_cap(budget, n_slots * ez, 1, ch, n_draws);
+}
+
+// ---- a parent of several engines: track shards own rows [lo, lo + m), column pairs own state columns from c0 -----------------------
+// Every array is column-major over its rows: element (i, c) of an [n x NCOL] array at i + n * c.
+// The queries on an engine's rows: idx their places in the caller's list, rows counted from lo, offs as given.
+struct QueryDeal {
+    std::vector<int64_t> idx, rows;
+    std::vector<double> offs;
+};
+inline QueryDeal deal_queries(int64_t lo, int64_t m, const int64_t* q_row, const double* q_off, int64_t nq) {
+    QueryDeal D;
+    for (int64_t i = 0; i < nq; i++)
+        if (q_row[i] >= lo && q_row[i] < lo + m) { D.idx.push_back(i); D.rows.push_back(q_row[i] - lo); D.offs.push_back(q_off[i]); }
+    return D;
+}
+
+// An engine's columns src [m x ncol] into columns c0 .. of dst [n x .]: its row i is the parent's row lo + i, or -- the dealt
+// queries -- row idx[i].
+inline void place_columns(double* dst, int64_t n, int c0, const double* src, int64_t m, int ncol, int64_t lo, const int64_t* idx = nullptr) {
+    for (int c = 0; c < ncol && m > 0; c++) {
+        double* to = dst + (size_t)n * (c0 + c);
+        const double* from = src + (size_t)m * c;
+        if (!idx) { memcpy(to + lo, from, (size_t)m * 8); continue; }
+        for (int64_t i = 0; i < m; i++) to[idx[i]] = from[i];
+    }
+}
+
+// An engine's covariances src [m x sd x sd] into the diagonal block (c0, c0) of dst [n x SD x SD] (the caller has zeroed dst: the
+// cross-pair blocks are exactly zero), rows as place_columns'.
+inline void place_block(double* dst, int64_t n, int SD, int c0, const double* src, int64_t m, int sd, int64_t lo, const int64_t* idx = nullptr) {
+    for (int c = 0; c < sd; c++) place_columns(dst + (size_t)n * SD * (c0 + c), n, c0, src + (size_t)m * sd * c, m, sd, lo, idx);
+}
+// ... and a row without a state (the engine left its block NaN) has no covariance at all: every element of the parent's row is NaN
+inline void place_cov_block(double* dst, int64_t n, int SD, int c0, const double* src, int64_t m, int sd, int64_t lo, const int64_t* idx = nullptr) {
+    place_block(dst, n, SD, c0, src, m, sd, lo, idx);
+    for (int64_t i = 0; i < m; i++)
+        if (std::isnan(src[i]))
+            for (int q = 0; q < SD * SD; q++) dst[(size_t)n * q + (idx ? idx[i] : lo + i)] = std::numeric_limits<double>::quiet_NaN();
+}
+
+// A track shard's statistics src [mt x n_stat x n_rep] at its tracks' places, track0 .., of dst [NT x n_stat x n_rep].  row_stat >= 0:
+// that statistic is the row of a maximum, which the shard counted in its own rows; its first row lo is added (whole numbers below 2^53,
+// so the sum is exact; NaN stays NaN).
+inline void place_track_stats(double* dst, int64_t NT, int64_t track0, const double* src, int64_t mt, int n_stat, int64_t n_rep, int row_stat,
+                              int64_t lo) {
+    for (int64_t q = 0; q < (int64_t)n_stat * n_rep && mt > 0; q++) {
+        double* to = dst + (size_t)NT * q + track0;
+        memcpy(to, src + (size_t)mt * q, (size_t)mt * 8);
+        if (row_stat >= 0 && q % n_stat == row_stat)
+            for (int64_t i = 0; i < mt; i++) to[i] += (double)lo;
+    }
+}
+
+// The most distinct offsets the queries of one caller's row hold.  (The distinct offsets of a slot of ssde_predict_draws are at most
+// those of one caller's row, and one more; the bridge deviates' counter holds the rank of an offset in 32 bits.)
+inline int64_t max_distinct_offsets(const int64_t* q_row, const double* q_off, int64_t nq) {
+    std::vector<int64_t> by((size_t)nq);
+    for (int64_t k = 0; k < nq; k++) by[(size_t)k] = k;
+    std::sort(by.begin(), by.end(), [&](int64_t a, int64_t b) { return q_row[a] != q_row[b] ? q_row[a] < q_row[b] : q_off[a] < q_off[b]; });
+    int64_t run_len = 0, most = 0;
+    for (int64_t k = 0; k < nq; k++) {
+        if (k == 0 || q_row[by[k]] != q_row[by[k - 1]]) run_len = 1;
+        else if (q_off[by[k]] != q_off[by[k - 1]]) run_len++;
+        most = std::max(most, run_len);
+    }
+    return most;
 }
 
 }  // namespace ssde_plan

@@ -100,4 +100,30 @@ int hostsim_chunk_groups(int n_groups, const int64_t* goff, int64_t budget, int3
 
 int hostsim_batch_cap(int64_t budget, int64_t per_draw, int unit, int ch, int n_draws) { return ssde_plan::batch_cap(budget, per_draw, unit, ch, n_draws); }
 
+// ---- a parent of several engines: the deal of the queries, the placement of an engine's outputs ------------------------------------
+// deal_queries: idx, rows, offs have room for nq; returns how many queries are on rows [lo, lo + m)
+int64_t hostsim_deal_queries(int64_t lo, int64_t m, const int64_t* q_row, const double* q_off, int64_t nq, int64_t* idx, int64_t* rows, double* offs) {
+    const ssde_plan::QueryDeal D = ssde_plan::deal_queries(lo, m, q_row, q_off, nq);
+    copy_out(D.idx, idx); copy_out(D.rows, rows); copy_out(D.offs, offs);
+    return (int64_t)D.idx.size();
+}
+
+// idx NULL: the engine's rows are the parent's lo ..
+void hostsim_place_columns(double* dst, int64_t n, int c0, const double* src, int64_t m, int ncol, int64_t lo, const int64_t* idx) {
+    ssde_plan::place_columns(dst, n, c0, src, m, ncol, lo, idx);
+}
+
+// nan_rule 1: place_cov_block (a row whose block is NaN has no covariance at all), 0: place_block
+void hostsim_place_block(double* dst, int64_t n, int SD, int c0, const double* src, int64_t m, int sd, int64_t lo, const int64_t* idx, int nan_rule) {
+    if (nan_rule) ssde_plan::place_cov_block(dst, n, SD, c0, src, m, sd, lo, idx);
+    else ssde_plan::place_block(dst, n, SD, c0, src, m, sd, lo, idx);
+}
+
+void hostsim_place_track_stats(double* dst, int64_t NT, int64_t track0, const double* src, int64_t mt, int n_stat, int64_t n_rep, int row_stat,
+                               int64_t lo) {
+    ssde_plan::place_track_stats(dst, NT, track0, src, mt, n_stat, n_rep, row_stat, lo);
+}
+
+int64_t hostsim_max_distinct_offsets(const int64_t* q_row, const double* q_off, int64_t nq) { return ssde_plan::max_distinct_offsets(q_row, q_off, nq); }
+
 }  // extern "C"

@@ -16,7 +16,12 @@ def load():
         "hostsim_plan_queries": (None, [C.c_int64, _lp, _ip, _lp, C.c_double, C.c_int64, _lp, _dp, C.c_int, _ip, C.c_int, _lp, _lp, _lp, _dp,
                                         _lp, _ip, _lp]),
         "hostsim_chunk_groups": (C.c_int, [C.c_int, _lp, C.c_int64, _ip]),
-        "hostsim_batch_cap": (C.c_int, [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int])})
+        "hostsim_batch_cap": (C.c_int, [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int]),
+        "hostsim_deal_queries": (C.c_int64, [C.c_int64, C.c_int64, _lp, _dp, C.c_int64, _lp, _lp, _dp]),
+        "hostsim_place_columns": (None, [_dp, C.c_int64, C.c_int, _dp, C.c_int64, C.c_int, C.c_int64, _lp]),
+        "hostsim_place_block": (None, [_dp, C.c_int64, C.c_int, C.c_int, _dp, C.c_int64, C.c_int, C.c_int64, _lp, C.c_int]),
+        "hostsim_place_track_stats": (None, [_dp, C.c_int64, C.c_int64, _dp, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int64]),
+        "hostsim_max_distinct_offsets": (C.c_int64, [_lp, _dp, C.c_int64])})
 
 
 def packet_doubles(model, d):
@@ -66,3 +71,42 @@ def chunk_groups(goff, budget):
 
 def batch_cap(budget, per_draw, unit, ch, n_draws):
     return load().hostsim_batch_cap(int(budget), int(per_draw), unit, ch, n_draws)
+
+
+# ---- a parent of several engines: the deal and the placement (csrc/ssde_smooth_plan.hpp) -------------------------------------------
+def deal_queries(lo, m, q_row, q_off):
+    """(idx, rows, offs) of the queries on rows [lo, lo + m)"""
+    q_row = np.ascontiguousarray(q_row, dtype=np.int64); q_off = np.ascontiguousarray(q_off, dtype=np.float64)
+    nq = len(q_row)
+    idx, rows, offs = np.zeros(nq, dtype=np.int64), np.zeros(nq, dtype=np.int64), np.zeros(nq)
+    k = load().hostsim_deal_queries(int(lo), int(m), ptr(q_row), ptr(q_off), nq, ptr(idx), ptr(rows), ptr(offs))
+    return idx[:k], rows[:k], offs[:k]
+
+
+def _idx(idx):
+    return None if idx is None else np.ascontiguousarray(idx, dtype=np.int64)
+
+
+def place_columns(dst, c0, src, lo=0, idx=None):
+    """src (m, ncol) into columns c0 .. of dst (n, NCOL), both Fortran-ordered, in place: at rows lo .., or at rows idx"""
+    assert dst.flags.f_contiguous and src.flags.f_contiguous and dst.dtype == src.dtype == np.float64
+    idx = _idx(idx)
+    load().hostsim_place_columns(ptr(dst), dst.shape[0], c0, ptr(src), src.shape[0], src.shape[1], int(lo), ptr(idx))
+
+
+def place_block(dst, c0, src, lo=0, idx=None, nan_rule=True):
+    """src (m, sd, sd) into the diagonal block at c0 of dst (n, SD, SD), both Fortran-ordered, in place; nan_rule: place_cov_block"""
+    assert dst.flags.f_contiguous and src.flags.f_contiguous and dst.dtype == src.dtype == np.float64
+    idx = _idx(idx)
+    load().hostsim_place_block(ptr(dst), dst.shape[0], dst.shape[1], c0, ptr(src), src.shape[0], src.shape[1], int(lo), ptr(idx), int(nan_rule))
+
+
+def place_track_stats(dst, track0, src, row_stat, lo):
+    """src (mt, n_stat, n_rep) at tracks track0 .. of dst (NT, n_stat, n_rep), both Fortran-ordered, in place"""
+    assert dst.flags.f_contiguous and src.flags.f_contiguous and dst.shape[1:] == src.shape[1:]
+    load().hostsim_place_track_stats(ptr(dst), dst.shape[0], int(track0), ptr(src), src.shape[0], src.shape[1], src.shape[2], row_stat, int(lo))
+
+
+def max_distinct_offsets(q_row, q_off):
+    q_row = np.ascontiguousarray(q_row, dtype=np.int64); q_off = np.ascontiguousarray(q_off, dtype=np.float64)
+    return int(load().hostsim_max_distinct_offsets(ptr(q_row), ptr(q_off), len(q_row)))

@@ -146,3 +146,107 @@ def test_batch_caps():
                     assert b % DRAW_CH == 0 or b == n_draws
                     if a > 1:
                         assert a * per_draw <= budget                                   # beyond the one that always goes, a batch fits
+
+
+# ---- a parent of several engines: the deal of the queries and the placement of the engines' outputs --------------------------------
+# Two track shards of 3 and 4 rows crossed with two column pairs: the parent has sd = 4 from engines of sd = 2, shard k = 2 * track
+# shard + pair, as the engine orders them.
+ROWS = [(0, 3), (3, 4)]
+N, SD, sd = 7, 4, 2
+
+
+def _engines():
+    return [(lo, m, 2 * pair) for lo, m in ROWS for pair in (0, 1)]
+
+
+def test_deal_queries():
+    q_row = np.array([4, 6, 3, 5, 4], dtype=np.int64)                    # five queries, none of them on the first shard's rows
+    q_off = np.array([0.5, 0.0, 1.25, 0.5, 0.75])
+    got = [predictsim_lib.deal_queries(lo, m, q_row, q_off) for lo, m in ROWS]
+    assert all(len(v) == 0 for v in got[0])
+    idx, rows, offs = got[1]
+    assert np.array_equal(idx, np.arange(5)) and np.array_equal(rows, q_row - 3) and np.array_equal(offs, q_off)
+    # ... and one on each side of the boundary, in the caller's order
+    q_row[[1, 3]] = [2, 0]
+    for lo, m in ROWS:
+        idx, rows, offs = predictsim_lib.deal_queries(lo, m, q_row, q_off)
+        mine = np.flatnonzero((q_row >= lo) & (q_row < lo + m))
+        assert np.array_equal(idx, mine) and np.array_equal(rows, q_row[mine] - lo) and np.array_equal(offs, q_off[mine])
+
+
+def test_place_columns_by_rows_and_by_queries():
+    rng = np.random.default_rng(1)
+    dst, ref = np.full((N, SD), np.nan, order="F"), np.full((N, SD), np.nan)
+    for lo, m, c0 in _engines():
+        src = np.asfortranarray(rng.standard_normal((m, sd)))
+        predictsim_lib.place_columns(dst, c0, src, lo=lo)
+        ref[lo:lo + m, c0:c0 + sd] = src
+    assert np.array_equal(dst, ref) and not np.isnan(dst).any()
+    # the dealt queries: five of them, the first shard gets none (so its rows of the output keep the preset)
+    q_row = np.array([4, 6, 3, 5, 4], dtype=np.int64)
+    dst, ref = np.full((5, SD), np.nan, order="F"), np.full((5, SD), np.nan)
+    for lo, m, c0 in _engines():
+        idx = np.flatnonzero((q_row >= lo) & (q_row < lo + m))
+        src = np.asfortranarray(rng.standard_normal((len(idx), sd)))
+        predictsim_lib.place_columns(dst, c0, src, idx=idx)
+        ref[idx, c0:c0 + sd] = src
+    assert np.array_equal(dst, ref) and not np.isnan(dst).any()
+
+
+@pytest.mark.parametrize("by_query", [False, True])
+def test_place_cov_block_and_the_all_nan_rule(by_query):
+    """Row 1 of the second track shard is NaN in the first pair only, row 2 of it in both.  The rule runs engine by engine, as the
+    engine runs it: a NaN block blanks the parent's whole row, and a pair placed later writes its own block over that."""
+    rng = np.random.default_rng(2)
+    dst, ref = np.zeros((N, SD, SD), order="F"), np.zeros((N, SD, SD))
+    perm = rng.permutation(N)                                             # by_query: row i of an engine is the parent's row perm[lo + i]
+    for lo, m, c0 in _engines():
+        src = np.asfortranarray(rng.standard_normal((m, sd, sd)))
+        if lo == 3:
+            src[2] = np.nan
+            if c0 == 0:
+                src[1] = np.nan
+        at = perm[lo:lo + m] if by_query else np.arange(lo, lo + m)
+        predictsim_lib.place_block(dst, c0, src, lo=0 if by_query else lo, idx=at if by_query else None)
+        ref[at, c0:c0 + sd, c0:c0 + sd] = src
+        ref[at[np.isnan(src[:, 0, 0])]] = np.nan
+    assert np.array_equal(dst, ref, equal_nan=True)
+    one, both, full = (perm[4], perm[5], perm[0]) if by_query else (4, 5, 0)
+    assert np.isnan(dst[both]).all()
+    assert np.isnan(dst[one]).sum() == SD * SD - sd * sd and not np.isnan(dst[one, 2:, 2:]).any()     # the later pair's block stands
+    assert np.all(dst[full, :2, 2:] == 0.0) and np.all(dst[full, 2:, :2] == 0.0) and not np.isnan(dst[full]).any()   # cross-pair blocks
+    # without the rule (ssde_smooth_loo's placement): the blocks alone
+    dst2 = np.zeros((N, SD, SD), order="F")
+    src = np.asfortranarray(np.full((4, sd, sd), np.nan))
+    predictsim_lib.place_block(dst2, 2, src, lo=3, nan_rule=False)
+    assert np.isnan(dst2[3:, 2:, 2:]).all() and np.isnan(dst2).sum() == 4 * sd * sd
+
+
+def test_place_track_stats_moves_the_row_of_a_maximum():
+    """track shards of 2 and 3 tracks whose rows start at 0 and 40; statistic 2 of 4 is the row of a maximum, NaN for one track"""
+    rng = np.random.default_rng(3)
+    NT, n_stat, n_rep = 5, 4, 3
+    dst, ref = np.full((NT, n_stat, n_rep), np.nan, order="F"), np.full((NT, n_stat, n_rep), np.nan)
+    for track0, mt, lo in ((0, 2, 0), (2, 3, 40)):
+        src = np.asfortranarray(rng.integers(0, 30, size=(mt, n_stat, n_rep)).astype(np.float64))
+        src[mt - 1, 2, 1] = np.nan
+        predictsim_lib.place_track_stats(dst, track0, src, 2, lo)
+        ref[track0:track0 + mt] = src
+        ref[track0:track0 + mt, 2] += lo
+    assert np.array_equal(dst, ref, equal_nan=True) and np.isnan(dst).sum() == 2 and np.all(dst[2:, 2, 0] >= 40)
+    plain = np.full((NT, n_stat, 1), np.nan, order="F")
+    src = np.asfortranarray(rng.standard_normal((3, n_stat, 1)))
+    predictsim_lib.place_track_stats(plain, 2, src, -1, 40)                            # ssde_path_stats: no row among the statistics
+    assert np.array_equal(plain[2:], src) and np.isnan(plain[:2]).all()
+
+
+def test_max_distinct_offsets_against_limits():
+    """rows with runs of 1, 2 and 3 distinct offsets (duplicates and the queries' order do not count); a slot holds at most one more
+    than its row's, and the entry points refuse where that reaches the limit (2^32 there, 3 and 4 here)"""
+    runs = {1: ([7, 7, 7], [0.5, 0.5, 0.5]), 2: ([3, 9, 3, 3], [0.25, 0.1, 0.0, 0.25]), 3: ([5, 2, 5, 5, 5, 2], [0.3, 0.0, 0.1, 0.2, 0.3, 0.0])}
+    for want, (rows, offs) in runs.items():
+        got = predictsim_lib.max_distinct_offsets(rows, offs)
+        assert got == want == max(len(set(o for r, o in zip(rows, offs) if r == row)) for row in set(rows))
+        assert (got + 1 >= 3) == (want >= 2) and (got + 1 >= 4) == (want >= 3)
+    assert predictsim_lib.max_distinct_offsets([], []) == 0
+    assert predictsim_lib.max_distinct_offsets([1, 1], [0.0, -0.0]) == 1                # +0.0 and -0.0 are one offset
