@@ -27,6 +27,9 @@
  *                         the reference's SDE$residuals() stops at (R/sde.R:1186-1228) and aest_all does not give
  *   ssde_smooth_loo    <- (new) leave-one-fix-out predictions of every fix from the rest of its track: deletion residuals, exact
  *                         leave-one-out log predictive densities and per-track outlier counts, from the smoother's own recursion
+ *   ssde_forecast_scores <- (new) k-step-ahead forecast errors of every fix from the data k rows back, standardised, with log scores
+ *                         and per-track calibration sums per horizon: what the reference gets by rebuilding the data with rows
+ *                         blanked to NA once per origin and horizon
  *   ssde_smooth_draws  <- (new) joint posterior draws of the whole state path (backward sampling over the smoother's records):
  *                         what speed, distance travelled, time in a region or multiple imputation are computed from
  *   ssde_predict       <- (new) the smoothed state at any time between or after the rows, from the smoother's records: what the
@@ -382,6 +385,38 @@ int ssde_smooth(ssde_handle *h, const double *par, int32_t n_par_full, double *a
 int ssde_smooth_loo(ssde_handle *h, const double *par, int32_t n_par_full,
                     double *loo_mean, double *loo_cov, double *loo_resid, double *lpd,
                     const double *thr, int32_t n_thr, double *stats, uint32_t flags);
+
+/* Multi-step-ahead forecast errors and scores of the Kalman families at `par` (definitions: DESIGN.md §3.21).  For a horizon k >= 1
+ * and a target row t of a track whose rows are first .. last, with t - k >= first, the forecast of row t from the data through row
+ * t - k is the one-step prediction of row r = t - k + 1 (the smoother's forward record of that row) pushed through the rows
+ * r .. t - 1 as the filter pushes it through NA rows -- a <- T_i a + drift, P <- T_i P T_i' + Q_i with row i's own parameters and the
+ * interval the handle holds for row i; the data of those rows are ignored -- then m = Z a, S = Z P Z' + H_t (sigma_obs^2 I or row
+ * t's H_array slice).  k = 1 is the filter's own innovation.  A target (t, k) is SCORED when y_t is not NA (the handle's na_mode), m
+ * and S are finite and the lower Cholesky factor C of the symmetrised S has finite, positive pivots; then z = C^-1 (y_t - m),
+ * q = z'z, lpd = -(n_dim log 2 pi + log det S + q) / 2: ssde_smooth_loo's conventions.  Horizons count the caller's rows: on a
+ * lattice-padded handle the chain steps through the padded rows, which are never starts or targets.
+ *   horizon   [n_h] host memory, strictly increasing, each 1 .. SSDE_AHEAD_MAX_STEP; n_h in 1 .. SSDE_AHEAD_MAX_H
+ *   z_ahead   [n x n_dim x n_h]  element (t, c, j) at t + n * (c + n_dim * j); NaN where (t, horizon[j]) is not scored
+ *   lpd_ahead [n x n_h]          NaN likewise
+ *   thr       [n_thr] host memory, on the q scale: finite, >= 0; n_thr in 0 .. SSDE_AHEAD_MAX_THR
+ *   stats     [n_tracks x n_stat x n_h], n_stat = 5 + n_thr, element (track, s, j) at track + n_tracks * (s + n_stat * j), track the ID
+ *             segment's ordinal in the caller's data: 0 the scored targets; 1 the sum of lpd; 2 of q; 3 of |y_t - m|^2; 4 of the lead
+ *             time (the handle's intervals of rows t - k .. t - 1 added up); 5 + r the scored targets with q > thr[r].  A track without
+ *             a scored target at that horizon: 0 in every slot.
+ * Any of the three outputs may be NULL, not all of them.  An uncoupled wide response (column pairs) serves z_ahead only (lpd_ahead
+ * and stats need a per-row sum across the pair handles: SSDE_ERR_MODEL, as ssde_smooth_loo); one coupled filter of three or more
+ * columns, the direct families and ESEAL_SSM: SSDE_ERR_MODEL.  SSDE_ERR_ARG, before anything touches the device: NULL h / par /
+ * horizon, n_h outside 1 .. SSDE_AHEAD_MAX_H, a horizon out of range or not strictly increasing, n_thr outside
+ * 0 .. SSDE_AHEAD_MAX_THR, thr NULL with n_thr > 0, a threshold that is not finite or < 0, n_thr > 0 without stats, all outputs NULL,
+ * flags != 0.  Isolation, chunking and buffers as ssde_smooth; the result is bitwise independent of the budget, of the devices, of
+ * repeated calls and of which outputs are asked for. */
+#define SSDE_AHEAD_MAX_H     8     /* horizons per call */
+#define SSDE_AHEAD_MAX_STEP 64     /* largest horizon */
+#define SSDE_AHEAD_MAX_THR   8
+int ssde_forecast_scores(ssde_handle *h, const double *par, int32_t n_par_full,
+                         const int32_t *horizon, int32_t n_h,
+                         double *z_ahead, double *lpd_ahead,
+                         const double *thr, int32_t n_thr, double *stats, uint32_t flags);
 
 /* Joint posterior draws of the whole state path at `par` (definitions: DESIGN.md §3.10): backward sampling over the smoother's own
  * forward records, so a draw carries the dependence BETWEEN rows that the row-wise a_smooth / P_smooth leave out.

@@ -516,6 +516,8 @@ def load_library():
     lib.ssde_smooth.restype = C.c_int
     lib.ssde_smooth_loo.argtypes = [C.c_void_p, _dp, C.c_int32, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, C.c_uint32]
     lib.ssde_smooth_loo.restype = C.c_int
+    lib.ssde_forecast_scores.argtypes = [C.c_void_p, _dp, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _dp, _dp, _dp, C.c_int32, _dp, C.c_uint32]
+    lib.ssde_forecast_scores.restype = C.c_int
     lib.ssde_smooth_draws.argtypes = [C.c_void_p, _dp, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.c_void_p, C.c_uint32]
     lib.ssde_smooth_draws.restype = C.c_int
     lib.ssde_predict.argtypes = [C.c_void_p, _dp, C.c_int32, C.POINTER(C.c_int64), _dp, C.c_int64, _dp, _dp]
@@ -637,6 +639,7 @@ class EngineError(RuntimeError):
 PATH_MAX_REGIONS = 8   # SSDE_PATH_MAX_REGIONS (include/ssde.h)
 SPEED_MAX_THR = 8      # SSDE_SPEED_MAX_THR: the most thresholds of one ssde_path_speed
 LOO_MAX_THR = 8        # SSDE_LOO_MAX_THR: the most thresholds of one ssde_smooth_loo
+AHEAD_MAX_H, AHEAD_MAX_STEP, AHEAD_MAX_THR = 8, 64, 8   # SSDE_AHEAD_MAX_*: horizons of one ssde_forecast_scores, the largest, thresholds
 DRAWS_DEVICE_OUT = 1   # ssde_smooth_draws flag: `draws` is an HBM pointer on the handle's device (include/ssde.h)
 OCC_FORCE_GLOBAL = 1   # ssde_path_occupancy flag: every wavefront group runs the global form (SSDE_OCC_FORCE_GLOBAL)
 PROX_MAX_RADII = 8     # SSDE_PROX_MAX_RADII: the most radii of one ssde_path_proximity
@@ -650,7 +653,7 @@ WINDOW_TOL = 1e-11  # largest tolerated relative hand-over disagreement between 
 
 EXPORTED_SYMBOLS = ("ssde_create", "ssde_eval", "ssde_eval_device", "ssde_penalty", "ssde_report", "ssde_widen_windows", "ssde_relax_windows",
                     "ssde_info", "ssde_destroy", "ssde_last_error", "ssde_abi_version", "ssde_comm_unique_id", "ssde_comm_init_rank", "ssde_forget", "ssde_laplace_eval", "ssde_last_kernel_ms", "ssde_kernel_ms_history",
-                    "ssde_simulate", "ssde_par_bands", "ssde_simulate_rows", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth", "ssde_smooth_loo", "ssde_smooth_draws", "ssde_predict", "ssde_predict_draws", "ssde_path_stats", "ssde_path_speed", "ssde_path_occupancy", "ssde_last_occupancy_form", "ssde_path_occupancy_fine", "ssde_last_occupancy_points", "ssde_last_hess_plan", "ssde_path_proximity", "ssde_last_proximity_plan",
+                    "ssde_simulate", "ssde_par_bands", "ssde_simulate_rows", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth", "ssde_smooth_loo", "ssde_forecast_scores", "ssde_smooth_draws", "ssde_predict", "ssde_predict_draws", "ssde_path_stats", "ssde_path_speed", "ssde_path_occupancy", "ssde_last_occupancy_form", "ssde_path_occupancy_fine", "ssde_last_occupancy_points", "ssde_last_hess_plan", "ssde_path_proximity", "ssde_last_proximity_plan",
                     "ssde_lagstats_host_m", "ssde_lagstats_read_m", "ssde_lagforms_host_m", "ssde_reduce_host", "ssde_last_finish_form", "ssde_last_gain_feed", "ssde_last_gain_rows",
                     "ssde_lagstats_host_cut", "ssde_lagstats_read_cut", "ssde_last_lag_cut",
                     "ssde_headstats_host", "ssde_headstats_read", "ssde_headforms_host", "ssde_last_head_form")
@@ -1343,6 +1346,32 @@ class Engine:
                                              len(thr), st.ctypes.data_as(_dp) if stats else None, 0))
         return {"mean": mean, "cov": V, "resid": e, "lpd": lp, "stats": None if st is None else st.T}
 
+    def forecast_scores(self, par, horizons, thresholds=None, z: bool = True, lpd: bool = True, stats: bool = True) -> dict:
+        """Multi-step-ahead forecast errors and scores at `par` (ssde_forecast_scores): fix t predicted from the
+        data through row t - k for every listed horizon k (strictly increasing, 1 .. AHEAD_MAX_STEP, at most AHEAD_MAX_H of them,
+        counted in the caller's rows).  {"z": (n x d x n_h) whitened forecast errors or None, "lpd": (n x n_h) log predictive
+        densities or None, "stats": (n_tracks, 5 + n_thr, n_h) or None -- per track and horizon the scored targets, the sums of
+        lpd, of q = |z|^2, of the squared error and of the lead time, then per threshold the targets with q above it}.  NaN where
+        a target is not scored (fewer than k rows into its track, a missing fix, no positive definite predictive covariance).
+        `thresholds`: at most AHEAD_MAX_THR finite numbers >= 0 on the q scale, or None.  An uncoupled wide response (column pairs)
+        serves "z" alone: pass lpd=False, stats=False there."""
+        par = np.ascontiguousarray(par, dtype=np.float64)
+        if par.shape != (self.n_par_full,):
+            raise ValueError(f"par must have length {self.n_par_full}")
+        hz = np.ascontiguousarray(horizons, dtype=np.int32)
+        thr = np.zeros(0) if thresholds is None else np.ascontiguousarray(thresholds, dtype=np.float64)
+        if hz.ndim != 1 or thr.ndim != 1:
+            raise ValueError("horizons and thresholds must be lists of numbers")
+        n, d, n_trk, nh = self.problem.n, self.problem.n_dim, self.problem.n_seg, len(hz)
+        zz = np.zeros((n, d, nh), order="F") if z else None
+        lp = np.zeros((n, nh), order="F") if lpd else None
+        st = np.zeros((nh, 5 + len(thr), n_trk)) if stats else None                       # element (t, s, j) at t + n_tracks (s + n_stat j)
+        self._check(self.lib.ssde_forecast_scores(self._h, par.ctypes.data_as(_dp), self.n_par_full, hz.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                  nh, zz.ctypes.data_as(_dp) if z else None, lp.ctypes.data_as(_dp) if lpd else None,
+                                                  thr.ctypes.data_as(_dp) if len(thr) else None, len(thr),
+                                                  st.ctypes.data_as(_dp) if stats else None, 0))
+        return {"z": zz, "lpd": lp, "stats": None if st is None else np.ascontiguousarray(st.transpose(2, 1, 0))}
+
     def smooth_draws(self, par, n_draws: int, seed: int = 0, draw0: int = 0, out=None):
         """Joint posterior draws of the whole state path at `par` (ssde_smooth_draws): an array of shape
         (n_draws, n, sdim), draw k being draw number draw0 + k of the stream `seed`; NaN on rows without a state (a track's first
@@ -1580,3 +1609,8 @@ class Engine:
             self.close()
         except Exception:
             pass
+
+
+def forecast_scores(engine, par, horizons, thresholds=None, z=True, lpd=True, stats=True):
+    """Engine.forecast_scores as a function of the engine (ssde_forecast_scores)"""
+    return engine.forecast_scores(par, horizons, thresholds=thresholds, z=z, lpd=lpd, stats=stats)

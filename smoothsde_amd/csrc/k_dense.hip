@@ -7,6 +7,7 @@
 // from the same time-major tile as the observations (coalesced 512-B wave loads).  This is
 // the coverage path (it is what makes every model configuration of the reference run on
 // the GPU); the throughput path for the headline configurations is k_iso.hip.
+#include "ssde_ahead.hpp"
 #include "ssde_dense.hpp"
 #include "ssde_device.hpp"
 #include "ssde_predict.hpp"
@@ -94,7 +95,10 @@ __global__ __launch_bounds__(WAVE) void dense_kernel(const DenseArgs A) {
             const int64_t goff = rec_group(A.rc, g);
             const bool upd = smooth_record_row<MODEL, D>(S, par, H, dt, y, is_na(y[0], A.any_nan), rec_row<SmoothRec<MODEL, D>::R>(A.rc, goff, lane, s0));
             if constexpr (D <= 2) {
-                if (A.rc.side)                                                   // ssde_predict: the row's linear predictors and interval
+                if (A.rc.side && A.rc.side_kind == REC_SIDE_AHEAD)               // ssde_forecast_scores: what a step through the row and a score at it need
+                    ahead_side_row<MODEL, D>(par, H, dt, y, is_na(y[0], A.any_nan),
+                                             rec_side_row<SmoothRec<MODEL, D>::R, AheadSide<MODEL, D>::SW>(A.rc, goff, lane, s0));
+                else if (A.rc.side)                                              // ssde_predict: the row's linear predictors and interval
                     predict_side_row<MODEL, D>(par, dt, is_na(y[0], A.any_nan), upd,
                                                rec_side_row<SmoothRec<MODEL, D>::R, PredictPk<MODEL, D>::SW>(A.rc, goff, lane, s0));
             }

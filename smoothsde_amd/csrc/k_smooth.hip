@@ -6,6 +6,7 @@
 // kernel with its loops kept as loops for five to eight columns (scratch, the rare coverage path, as k_dense_wide.hip).
 // Outputs go straight to the long format: lane l writes row row0_l + 1 + s, so a wave store touches 64 rows, but successive steps of
 // a lane fill the same cache lines and the outputs are a third of the bytes moved (DESIGN.md §3.9 has the measurement).
+#include "ssde_ahead.hpp"
 #include "ssde_device.hpp"
 #include "ssde_predict.hpp"
 #include "ssde_smooth.hpp"
@@ -89,7 +90,9 @@ __global__ __launch_bounds__(WAVE) void smooth_tv_record_kernel(const TvArgs T, 
         }
         const bool na = is_na(y[0], T.any_nan);
         const bool upd = smooth_record_row<MODEL, D>(S, par, H, dt, y, na, rec_row<RC::R>(A.rc, goff, lane, s));
-        if (A.rc.side)                                                           // ssde_predict: the row's linear predictors and interval
+        if (A.rc.side && A.rc.side_kind == REC_SIDE_AHEAD)                       // ssde_forecast_scores: what a step through the row and a score at it need
+            ahead_side_row<MODEL, D>(par, H, dt, y, na, rec_side_row<RC::R, AheadSide<MODEL, D>::SW>(A.rc, goff, lane, s));
+        else if (A.rc.side)                                                      // ssde_predict: the row's linear predictors and interval
             predict_side_row<MODEL, D>(par, dt, na, upd, rec_side_row<RC::R, PredictPk<MODEL, D>::SW>(A.rc, goff, lane, s));
         dense_step<MODEL, D, 0>(S, par, H, dt, y, na);
     }

@@ -717,6 +717,31 @@ struct LooArgs {
     double thr[SSDE_LOO_MAX_THR];
 };
 hipError_t launch_smooth_loo(const LooArgs& a, hipStream_t s);
+// ---- multi-step-ahead forecast errors and scores (k_smooth_ahead.hip, ssde_ahead.hpp) ----
+// The records, side rows (rc.side_kind = REC_SIDE_AHEAD), groups and lanes of a SmoothArgs `s` (its outputs are not read), every
+// group's start rows cut into blocks of ssde_plan::AHEAD_BLOCK: the grid is (the chunk's groups, max_blocks).  Per-row outputs on
+// the caller's n_rows rows, NaN-preset by the caller, each may be NULL.  part: the chunk's partial records [blocks][n_h * n_stat][64]
+// (n_stat = 5 + n_thr) or NULL; with it the launch ends in the kernel that adds every track's blocks in ascending order into stats
+// + lane_trk[l] + n_trk * (k + n_stat * j).  The horizons and thresholds travel by value.
+struct AheadArgs {
+    SmoothArgs s;
+    const int64_t* lane_trk;     // [groups * 64]: the lane's ID segment in the handle's data (ssde_handle::lane_seg)
+    const int64_t* row_map;      // as PathArgs
+    const double* lane_dt0;      // [groups * 64]: the interval of the lane's track's first row
+    const int64_t* blk_off;      // [groups + 1]: every group's first block, over ALL groups (ssde_plan::ahead_block_offsets)
+    int64_t blk_base;            // blk_off[rc.g0]
+    double* z;                   // [n_rows x d x n_h] or NULL
+    double* lpd;                 // [n_rows x n_h] or NULL
+    double* part;
+    double* stats;               // [n_trk x n_stat x n_h] (with part)
+    int64_t n_rows, n_trk;
+    int n_h, n_thr, hmax, max_blocks;   // hmax: the largest horizon; max_blocks: the most blocks of a group of the chunk
+    int hz[SSDE_AHEAD_MAX_H];
+    double thr[SSDE_AHEAD_MAX_THR];
+};
+int ahead_side_doubles(int model, int d);
+hipError_t launch_forecast_scores(const AheadArgs& a, hipStream_t s);
+hipError_t launch_ahead_dt0(const double* times, const int64_t* row0, int64_t n_lanes, int64_t n, double last_dt, double* out, hipStream_t s);
 // ---- joint posterior draws of the state path (k_smooth_draws.hip, ssde_draws.hpp) ----
 // The records, groups and lanes of a SmoothArgs `s` (its outputs are not read); a batch of n_draws draws, number draw0 + k of the
 // stream `seed`, draw k one [n_out x sdim] matrix at out + k * draw_stride (n_out * sdim, or more where the columns sit inside a wider

@@ -83,7 +83,7 @@ void release_device(ssde_handle* h) {
     if (h->ev_async) (void)hipEventDestroy(h->ev_async);
     for (auto& pr : h->ev_ring) { if (pr[0]) (void)hipEventDestroy(pr[0]); if (pr[1]) (void)hipEventDestroy(pr[1]); }
     h->tv_eh.release(); h->tv_eR.release(); h->tv_harr.release(); h->tv_rec.release(); h->tv_wdir.release(); h->tv_a0.release(); h->tv_bnd.release(); h->tv_chk.release();
-    h->tv_gval.release(); h->tv_gdir.release(); h->tv_stats.release(); h->tv_dirs.release(); h->tv_row0.release(); h->lane_seg.release();
+    h->tv_gval.release(); h->tv_gdir.release(); h->tv_stats.release(); h->tv_dirs.release(); h->tv_row0.release(); h->lane_seg.release(); h->lane_dt0.release();
     h->tv_ns.release(); h->tv_items_g.release(); h->tv_items_v.release();
     for (int i = 0; i < 2; i++) if (h->tv_gexec[i]) (void)hipGraphExecDestroy(h->tv_gexec[i]);
     if (h->tv_stream) (void)hipStreamDestroy(h->tv_stream);

@@ -249,6 +249,9 @@ struct ssde_handle {
     // [lanes] the ID segment (in the handle's data) of every lane's track, tiled routes and PATH_TV alike: a0 at create, and the
     // deviates' track counter of ssde_smooth_draws
     DevBuf<int64_t> lane_seg;
+    // [lanes] the interval the data hold for the first row of every lane's track, tiled routes (the tiles start at the second row;
+    // PATH_TV keeps the times): the lead time of a forecast from that row (ssde_forecast_scores)
+    DevBuf<double> lane_dt0;
     DevBuf<int32_t> tv_ns;
     DevBuf<TvItem> tv_items_g, tv_items_v;     // work items of a gradient / a value-only evaluation
     std::vector<int32_t> tv_ns_host;

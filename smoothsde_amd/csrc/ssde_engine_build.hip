@@ -1316,6 +1316,9 @@ static int build_impl(const ssde_desc* d, ssde_handle* h, const ParLayout* part_
         ia.a0_src = p_a0; ia.lane_seg = h->lane_seg.p; ia.n_seg = h->n_seg;
         ia.sdim = h->sdim; ia.model = d->model; ia.dt_minmax = mm.p; ia.ychunks = ych; ia.last_dt = h->last_dt;
         HIPCHK(h, launch_ingest(ia, 0));
+        // the interval of every track's first row, which no tile holds (ssde_forecast_scores' lead times)
+        HIPCHK(h, h->lane_dt0.alloc((size_t)G * WAVE));
+        HIPCHK(h, launch_ahead_dt0(p_times, h->lane_row0.p, (int64_t)G * WAVE, tn, h->last_dt, h->lane_dt0.p, 0));
         std::vector<double> mmh((size_t)G * ych * 3);
         HIPCHK(h, hipMemcpy(mmh.data(), mm.p, mmh.size() * 8, hipMemcpyDeviceToHost));  // also syncs
         double dmin = INFINITY, dmax = -INFINITY;

@@ -1,6 +1,7 @@
-// ssde_engine_smooth.hip -- the host side of the ten calls that consume the smoother's records:
+// ssde_engine_smooth.hip -- the host side of the eleven calls that consume the smoother's records:
 //     ssde_smooth               the fixed-interval smoother of the Kalman families                        DESIGN.md §3.9
 //     ssde_smooth_loo           leave-one-out residuals and predictive densities of every fix             §3.20
+//     ssde_forecast_scores      k-step-ahead forecast errors and scores of every fix                      §3.21
 //     ssde_smooth_draws         joint posterior draws of the state path                                   §3.10
 //     ssde_path_stats           the drawn paths reduced per track and draw                                §3.12
 //     ssde_path_speed           the speed along them (CTCRW), per track and draw and counted per row      §3.17
@@ -90,6 +91,17 @@ int check_weights(ssde_handle* h, const std::string& who, const double* weight, 
     return SSDE_OK;
 }
 
+// the thresholds of a call that counts them in its statistics (ssde_smooth_loo, ssde_forecast_scores): at most max_thr, each finite
+// and >= 0, and none without the statistics
+int check_thresholds(ssde_handle* h, const std::string& who, const double* thr, int32_t n_thr, int max_thr, const char* max_name, bool have_stats) {
+    if (n_thr < 0 || n_thr > max_thr || (n_thr > 0 && !thr))
+        return refuse(h, SSDE_ERR_ARG, who + ": 0 <= n_thr <= " + max_name + ", with a table of thresholds when there are any");
+    for (int k = 0; k < n_thr; k++)
+        if (!std::isfinite(thr[k]) || thr[k] < 0.0) return refuse(h, SSDE_ERR_ARG, who + ": a threshold that is not finite or negative");
+    if (n_thr > 0 && !have_stats) return refuse(h, SSDE_ERR_ARG, who + ": thresholds are counted in the statistics, which were not asked for");
+    return SSDE_OK;
+}
+
 // a quarter of the free memory, in doubles: the budget where SSDE_OPT_SMOOTH_BUDGET_MB sets none
 int free_budget(ssde_handle* h, int64_t& budget) {
     size_t free_b = 0, total_b = 0;
@@ -118,7 +130,12 @@ struct RecordRun {
     bool tv = false, have_records = false;
     int R = 0;
     int64_t nt = 0, n_lanes = 0, budget = 0;
-    int SW = 0;                        // > 0 (set before setup): the record pass also writes side rows of SW doubles (ssde_predict)
+    int SW = 0;                        // > 0 (set before setup): the record pass also writes side rows of SW doubles (ssde_predict) ...
+    int side_kind = 0;                 // ... of this kind (ssde_records.hpp: 0 ssde_predict's, REC_SIDE_AHEAD ssde_forecast_scores')
+    // set before setup: the doubles the call keeps per group beside its records and side rows, from the group's state rows; the
+    // chunks are then cut on the groups' whole cost
+    std::function<int64_t(int64_t)> extra;
+    std::vector<int64_t> gsteps;       // the groups' state rows (their longest track's)
     DevBuf<double> rec, pbuf, side;
     DevBuf<int64_t> offb;
     DevBuf<SlotTable> stb;
@@ -160,18 +177,25 @@ struct RecordRun {
         const int G = (int)glen.size();
         goff.assign((size_t)G + 1, 0);
         for (int g = 0; g < G; g++) goff[g + 1] = goff[g] + (int64_t)glen[g] * R * WAVE;
+        gsteps.assign(glen.begin(), glen.end());
         HIPCHK(h, offb.upload(goff));
         if (h->smooth_budget_mb > 0) budget = h->smooth_budget_mb * (int64_t)(1 << 20) / 8;
         else if (int st = free_budget(h, budget)) return st;
-        if (SW > 0) budget = budget / (R + SW) * R;                // the side rows share the budget
-        cut = chunk_groups(goff, budget);
+        if (extra) {
+            std::vector<int64_t> cost((size_t)G + 1, 0);
+            for (int g = 0; g < G; g++) cost[g + 1] = cost[g] + (int64_t)glen[g] * (R + SW) * WAVE + extra(glen[g]);
+            cut = chunk_groups(cost, budget);
+        } else {
+            if (SW > 0) budget = budget / (R + SW) * R;            // the side rows share the budget
+            cut = chunk_groups(goff, budget);
+        }
         int64_t biggest = 0;
         for (size_t c = 0; c + 1 < cut.size(); c++) biggest = std::max(biggest, goff[cut[c + 1]] - goff[cut[c]]);
         HIPCHK(h, rec.alloc((size_t)std::max<int64_t>(biggest, 1)));
         if (SW > 0) HIPCHK(h, side.alloc((size_t)std::max<int64_t>(biggest / R * SW, 1)));
 
         memset(&s, 0, sizeof(s));
-        s.model = h->model; s.d = d; s.rc.rec = rec.p; s.rc.side = side.p; s.rc.rec_off = offb.p;
+        s.model = h->model; s.d = d; s.rc.rec = rec.p; s.rc.side = side.p; s.rc.side_kind = side_kind; s.rc.rec_off = offb.p;
         s.n_out = nt; s.n_lanes = n_lanes;
         if (tv) {
             tv_base_args(h, ta);
@@ -584,6 +608,74 @@ int loo_single(ssde_handle* h, const double* par, double* loo_mean, double* loo_
     if (int st = eb.fetch(h, nt, d, loo_resid)) return st;
     if (int st = lb.fetch(h, nt, 1, lpd)) return st;
     if (stats && n_trk > 0) HIPCHK(h, hipMemcpy(stats, sb.p, (size_t)n_trk * n_stat * 8, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipStreamSynchronize(0));
+    return SSDE_OK;
+}
+
+// ---- ssde_forecast_scores -----------------------------------------------------------------------------------------------------
+// One engine's forecast scores into host memory (each output may be NULL): chunks of whole groups as ssde_smooth, over a run whose
+// record pass writes ssde_ahead.hpp's side rows; per chunk k_smooth_ahead.hip's launch, one wave per (group, block of AHEAD_BLOCK
+// start rows).  The per-row outputs live on the caller's rows on the device (preset to NaN; the kernel stores through the RowMap) and
+// come home in one copy each.  The statistics [n_seg x n_stat x n_h] are preset to 0 (a track without a state row reaches no lane);
+// each chunk's partial records are folded by the launch's second kernel.  The partial records are counted against the budget with the
+// records and side rows (RecordRun::extra).
+int ahead_single(ssde_handle* h, const double* par, const int32_t* hz, int n_h, double* z_ahead, double* lpd_ahead, const double* thr,
+                 int n_thr, double* stats) {
+    if (int st = open_call(h)) return st;
+    const int d = h->d;
+    const int64_t n = h->n, n_trk = h->n_seg;
+    const int n_stat = 5 + n_thr, n_slot = n_h * n_stat;
+    const bool sums = stats && n_trk > 0;
+    DevBuf<double> zb, lb, sb, part, dt0;
+    DevBuf<int64_t> bo;
+    RowMap map;
+    Release guard(zb, lb, sb, part, dt0, bo);
+    RecordRun run;
+    run.SW = ahead_side_doubles(h->model, d);
+    if (run.SW <= 0) { h->err = "ssde_forecast_scores: no kernels for this model and width"; return SSDE_ERR_MODEL; }
+    run.side_kind = REC_SIDE_AHEAD;
+    if (sums) run.extra = [=](int64_t steps) { return ahead_partial_doubles(steps, n_h, n_stat, WAVE); };
+    // (the outputs BEFORE the run's set-up, whose default budget is what they leave free)
+    if (z_ahead) { HIPCHK(h, zb.alloc((size_t)n * d * n_h)); HIPCHK(h, hipMemset(zb.p, 0xff, (size_t)n * d * n_h * 8)); }
+    if (lpd_ahead) { HIPCHK(h, lb.alloc((size_t)n * n_h)); HIPCHK(h, hipMemset(lb.p, 0xff, (size_t)n * n_h * 8)); }
+    if (sums) { HIPCHK(h, sb.alloc((size_t)n_trk * n_slot)); HIPCHK(h, hipMemset(sb.p, 0, (size_t)n_trk * n_slot * 8)); }
+    if (int st = run.setup(h, par, "ssde_forecast_scores")) return st;
+    if (sums) if (int st = check_track_ordinals(h, run.n_lanes, "ssde_forecast_scores")) return st;
+    if (int st = map.make(h, run.nt)) return st;
+    const double* dt0p = h->lane_dt0.p;
+    if (run.tv) {                                                           // PATH_TV keeps the times
+        HIPCHK(h, dt0.alloc((size_t)std::max<int64_t>(run.n_lanes, 1)));
+        HIPCHK(h, launch_ahead_dt0(h->times.p, run.s.lane_row0, run.n_lanes, h->n, h->last_dt, dt0.p, 0));
+        dt0p = dt0.p;
+    } else if ((int64_t)h->lane_dt0.n < run.n_lanes) {
+        return refuse(h, SSDE_ERR_ARG, "ssde_forecast_scores: the handle holds no first intervals for its lanes");
+    }
+    const std::vector<int64_t> blk_off = ahead_block_offsets(run.gsteps);
+    HIPCHK(h, bo.upload(blk_off));
+    if (sums) {
+        int64_t most = 0;
+        for (size_t c = 0; c < run.n_chunks(); c++) most = std::max(most, blk_off[run.cut[c + 1]] - blk_off[run.cut[c]]);
+        HIPCHK(h, part.alloc((size_t)std::max<int64_t>(most * n_slot * WAVE, 1)));
+    }
+    AheadArgs a;
+    memset(&a, 0, sizeof(a));
+    a.lane_trk = h->lane_seg.p; a.row_map = map.p; a.lane_dt0 = dt0p; a.blk_off = bo.p;
+    a.z = zb.p; a.lpd = lb.p; a.part = sums ? part.p : nullptr; a.stats = sums ? sb.p : nullptr;
+    a.n_rows = n; a.n_trk = n_trk; a.n_h = n_h; a.n_thr = n_thr; a.hmax = hz[n_h - 1];
+    for (int j = 0; j < n_h; j++) a.hz[j] = hz[j];
+    for (int k = 0; k < n_thr; k++) a.thr[k] = thr[k];
+    for (size_t c = 0; c < run.n_chunks(); c++) {
+        if (int st = run.produce(c)) return st;
+        a.s = run.s;
+        a.blk_base = blk_off[run.cut[c]];
+        int64_t mb = 0;
+        for (int g = run.cut[c]; g < run.cut[c + 1]; g++) mb = std::max(mb, blk_off[g + 1] - blk_off[g]);
+        a.max_blocks = (int)std::min<int64_t>(mb, std::numeric_limits<int>::max());
+        HIPCHK(h, launch_forecast_scores(a, 0));
+    }
+    if (z_ahead) HIPCHK(h, hipMemcpy(z_ahead, zb.p, (size_t)n * d * n_h * 8, hipMemcpyDeviceToHost));
+    if (lpd_ahead) HIPCHK(h, hipMemcpy(lpd_ahead, lb.p, (size_t)n * n_h * 8, hipMemcpyDeviceToHost));
+    if (sums) HIPCHK(h, hipMemcpy(stats, sb.p, (size_t)n_trk * n_slot * 8, hipMemcpyDeviceToHost));
     HIPCHK(h, hipStreamSynchronize(0));
     return SSDE_OK;
 }
@@ -1194,6 +1286,30 @@ int loo_sharded(ssde_handle* parent, const double* par, double* loo_mean, double
     return SSDE_OK;
 }
 
+// the shards' and column pairs' forecast scores, placed as loo_sharded places the leave-one-out outputs: a pair's columns of z_ahead
+// in the parent's wider layout horizon by horizon, a track shard's rows and tracks at their places.  lpd_ahead and stats are asked of
+// track shards only (the entry refuses them on column pairs).
+int ahead_sharded(ssde_handle* parent, const double* par, const int32_t* hz, int n_h, double* z_ahead, double* lpd_ahead,
+                  const double* thr, int n_thr, double* stats) {
+    const int64_t n = parent->n, NT = parent->n_seg;
+    const int D = parent->d, per = parent->model == SSDE_MODEL_CTCRW ? 2 : 1, n_stat = 5 + n_thr;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    if (z_ahead) std::fill(z_ahead, z_ahead + (size_t)n * D * n_h, nan);
+    if (lpd_ahead) std::fill(lpd_ahead, lpd_ahead + (size_t)n * n_h, nan);
+    if (stats) std::fill(stats, stats + (size_t)NT * n_stat * n_h, 0.0);
+    return for_each_shard(parent, [&](ssde_handle* sh, size_t k, int64_t lo, int64_t m, int64_t track0) -> int {
+        const int64_t mt = sh->n_seg;
+        const int d = sh->d, r0 = parent->shard_col0[k] / per;
+        std::vector<double> tz(z_ahead ? (size_t)m * d * n_h : 0), tl(lpd_ahead ? (size_t)m * n_h : 0), ts(stats ? (size_t)mt * n_stat * n_h : 0);
+        if (int st = ssde_forecast_scores(sh, par, parent->L.n_full, hz, n_h, z_ahead ? tz.data() : nullptr, lpd_ahead ? tl.data() : nullptr,
+                                          thr, n_thr, stats ? ts.data() : nullptr, 0)) return st;
+        for (int j = 0; z_ahead && j < n_h; j++) place_columns(z_ahead + (size_t)n * D * j, n, r0, tz.data() + (size_t)m * d * j, m, d, lo);
+        if (lpd_ahead) place_columns(lpd_ahead, n, 0, tl.data(), m, n_h, lo);
+        if (stats) place_track_stats(stats, NT, track0, ts.data(), mt, n_stat, n_h, -1, lo);
+        return SSDE_OK;
+    });
+}
+
 // the shards' and column pairs' draws, each counted by the GLOBAL track ordinal and state column, placed in the parent's layout
 int draws_sharded(ssde_handle* parent, const double* par, uint64_t seed, int64_t draw0, int n_draws, double* draws, bool dev_out) {
     const int64_t n = parent->n;
@@ -1465,13 +1581,7 @@ int ssde_smooth_loo(ssde_handle* h, const double* par, int32_t n_par_full, doubl
         return SSDE_ERR_ARG;
     }
     if (int st = check_par_len(h, n_par_full)) return st;
-    if (n_thr < 0 || n_thr > SSDE_LOO_MAX_THR || (n_thr > 0 && !thr)) {
-        h->err = "ssde_smooth_loo: 0 <= n_thr <= SSDE_LOO_MAX_THR, with a table of thresholds when there are any";
-        return SSDE_ERR_ARG;
-    }
-    for (int k = 0; k < n_thr; k++)
-        if (!std::isfinite(thr[k]) || thr[k] < 0.0) { h->err = "ssde_smooth_loo: a threshold that is not finite or negative"; return SSDE_ERR_ARG; }
-    if (n_thr > 0 && !stats) { h->err = "ssde_smooth_loo: thresholds are counted in the statistics, which were not asked for"; return SSDE_ERR_ARG; }
+    if (int st = check_thresholds(h, "ssde_smooth_loo", thr, n_thr, SSDE_LOO_MAX_THR, "SSDE_LOO_MAX_THR", stats != nullptr)) return st;
     if (flags != 0) { h->err = "ssde_smooth_loo: unknown flag"; return SSDE_ERR_ARG; }
     if (int st = check_kalman(h)) return st;
     if (!h->shards.empty()) {
@@ -1482,6 +1592,33 @@ int ssde_smooth_loo(ssde_handle* h, const double* par, int32_t n_par_full, doubl
         return loo_sharded(h, par, loo_mean, loo_cov, loo_resid, lpd, thr, n_thr, stats);
     }
     return loo_single(h, par, loo_mean, loo_cov, loo_resid, lpd, thr, n_thr, stats);
+}
+
+int ssde_forecast_scores(ssde_handle* h, const double* par, int32_t n_par_full, const int32_t* horizon, int32_t n_h, double* z_ahead,
+                         double* lpd_ahead, const double* thr, int32_t n_thr, double* stats, uint32_t flags) {
+    if (!h || !par || !horizon || (!z_ahead && !lpd_ahead && !stats)) {
+        if (h) h->err = "ssde_forecast_scores: no parameter vector, no horizons, or no output asked for";
+        return SSDE_ERR_ARG;
+    }
+    if (int st = check_par_len(h, n_par_full)) return st;
+    switch (check_horizons(horizon, n_h, SSDE_AHEAD_MAX_H, SSDE_AHEAD_MAX_STEP)) {
+        case 0: break;
+        case 1: return refuse(h, SSDE_ERR_ARG, "ssde_forecast_scores: 1 <= n_h <= SSDE_AHEAD_MAX_H is required");
+        case 2: return refuse(h, SSDE_ERR_ARG, "ssde_forecast_scores: a horizon outside 1 .. SSDE_AHEAD_MAX_STEP");
+        default: return refuse(h, SSDE_ERR_ARG, "ssde_forecast_scores: the horizons must be strictly increasing");
+    }
+    if (int st = check_thresholds(h, "ssde_forecast_scores", thr, n_thr, SSDE_AHEAD_MAX_THR, "SSDE_AHEAD_MAX_THR", stats != nullptr)) return st;
+    if (flags != 0) { h->err = "ssde_forecast_scores: unknown flag"; return SSDE_ERR_ARG; }
+    if (int st = check_kalman(h)) return st;
+    if (!h->shards.empty()) {
+        if ((lpd_ahead || stats) && std::max(h->n_dim_parts, 1) > 1) {
+            h->err = "ssde_forecast_scores: lpd_ahead and stats are not served for an uncoupled wide response run as column pairs (they need a per-row sum across the pair handles); z_ahead is";
+            return SSDE_ERR_MODEL;
+        }
+        return ahead_sharded(h, par, horizon, n_h, z_ahead, lpd_ahead, thr, n_thr, stats);
+    }
+    if (int st = check_not_coupled_wide(h, "ssde_forecast_scores")) return st;          // (every check before the device is touched)
+    return ahead_single(h, par, horizon, n_h, z_ahead, lpd_ahead, thr, n_thr, stats);
 }
 
 }  // extern "C"

@@ -4,7 +4,7 @@
 // R = SmoothRec<MODEL, D>::R doubles per state row, one group (64 lanes = tracks) after another, time-major and lane-coalesced:
 //
 //     double k of step s of a lane of group g:   rec  + (rec_off[g] - rec_base)          + (s * R  + k) * 64 + lane
-//     side row (ssde_predict, SW doubles a row):  side + (rec_off[g] - rec_base) / R * SW + (s * SW + k) * 64 + lane
+//     side row (SW doubles a row, by side_kind):  side + (rec_off[g] - rec_base) / R * SW + (s * SW + k) * 64 + lane
 //
 // so every load or store of one record double is a 512-B wave access.  rec_off counts doubles over ALL groups; a call produces and
 // consumes the records chunk by chunk, and rec_base = rec_off[g0] makes the addresses chunk-relative.  Only this header spells
@@ -19,14 +19,16 @@
 namespace ssde {
 
 constexpr int REC_WAVE = 64;     // lanes of a group (ssde_device.hpp: WAVE)
+constexpr int REC_SIDE_AHEAD = 1;
 
 // the chunk of records being written or read
 struct RecChunk {
     double* rec;
-    double* side;                // ssde_predict: the rows' side rows, or NULL (nothing is written)
+    double* side;                // the rows' side rows, or NULL (nothing is written) ...
     const int64_t* rec_off;      // [groups + 1] in doubles, over all groups
     int64_t rec_base;            // rec_off[g0]
     int g0, n_groups;            // this chunk's groups
+    int side_kind;               // ... 0: ssde_predict's (ssde_predict.hpp), REC_SIDE_AHEAD: ssde_forecast_scores' (ssde_ahead.hpp)
 };
 
 // one row of a lane: rec(k) is its double k

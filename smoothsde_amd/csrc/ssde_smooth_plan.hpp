@@ -275,6 +275,38 @@ inline int occ_fine_batch_cap(int64_t budget, int64_t n_slots, int ez, int ch, i
     return batch_cap(budget, n_slots * ez, 1, ch, n_draws);
 }
 
+// ---- ssde_forecast_scores ----------------------------------------------------------------------------------------
+// The start rows of a wavefront group are cut into blocks of AHEAD_BLOCK consecutive state rows, one wave each; a block's partial
+// sums are one record of n_h * n_stat doubles per lane.  The block length is part of the result's definition (a track's sums are
+// added block by block, ascending), so it is a constant and no tunable.
+constexpr int AHEAD_BLOCK = 32;
+
+// blocks of a group whose longest track has `steps` state rows
+inline int64_t ahead_blocks(int64_t steps) { return steps > 0 ? (steps + AHEAD_BLOCK - 1) / AHEAD_BLOCK : 0; }
+
+// the doubles of the partial sums of a group of `wave` lanes: what a group costs the budget beside its records and side rows
+inline int64_t ahead_partial_doubles(int64_t steps, int n_h, int n_stat, int wave) {
+    return ahead_blocks(steps) * (int64_t)n_h * n_stat * wave;
+}
+
+// every group's first block, counted over ALL groups (G + 1 entries), from the groups' state rows
+inline std::vector<int64_t> ahead_block_offsets(const std::vector<int64_t>& steps) {
+    std::vector<int64_t> off(steps.size() + 1, 0);
+    for (size_t g = 0; g < steps.size(); g++) off[g + 1] = off[g] + ahead_blocks(steps[g]);
+    return off;
+}
+
+// the horizon list of one call: 0 accepted; 1: n_h outside 1 .. max_h (or no list); 2: a horizon outside 1 .. max_step; 3: not
+// strictly increasing
+inline int check_horizons(const int32_t* horizon, int n_h, int max_h, int max_step) {
+    if (!horizon || n_h < 1 || n_h > max_h) return 1;
+    for (int j = 0; j < n_h; j++) {
+        if (horizon[j] < 1 || horizon[j] > max_step) return 2;
+        if (j > 0 && horizon[j] <= horizon[j - 1]) return 3;
+    }
+    return 0;
+}
+
 // ---- a parent of several engines: track shards own rows [lo, lo + m), column pairs own state columns from c0 -----------------------
 // Every array is column-major over its rows: element (i, c) of an [n x NCOL] array at i + n * c.
 // The queries on an engine's rows: idx their places in the caller's list, rows counted from lo, offs as given.

@@ -514,6 +514,31 @@ class SDE:
             rows = np.nonzero(q > thr)[0]
         return {"rows": rows, "q": q[rows], "threshold": thr, "counts": out["stats"][:, 4].astype(np.int64)}
 
+    def forecast_skill(self, horizons=(1, 2, 5, 10), level=0.95):
+        """Forecast skill of a state-space model (CTCRW, OU_SSM, BM_SSM) at the current parameters as a function of the lead
+        (ssde_forecast_scores): every fix predicted from the data `k` rows back, for every k of `horizons`,
+        without rebuilding the data.  Returns {"horizons", "level", "threshold": the chi-square quantile `level` with d degrees of
+        freedom, "pooled": {...}, "tracks": {...}}; each of the two holds, per horizon (pooled over the tracks: n_h numbers; per
+        track: n_tracks x n_h), "n": the scored targets, "log_score": their mean log predictive density, "mean_q": their mean
+        q = |z|^2 (about d under the model), "rmse": the root of their mean squared error, "lead": their mean lead time and
+        "coverage": the share of them inside the `level` predictive region (q <= threshold).  NaN where nothing was scored."""
+        if self.type_ not in ("CTCRW", "OU_SSM", "BM_SSM"):
+            raise NotImplementedError(f"forecast_skill: no latent state in the model {self.type_!r}")
+        if not 0.0 < level < 1.0:
+            raise ValueError("level must lie strictly between 0 and 1")
+        from scipy.stats import chi2
+        d = self.engine_.problem.n_dim
+        thr = float(chi2.ppf(level, d))
+        hz = [int(k) for k in horizons]
+        st = self.engine_.forecast_scores(self._current_par_full(), hz, thresholds=[thr], z=False, lpd=False)["stats"]
+
+        def ratios(s):                                                    # s: (..., 6, n_h) sums -> the means
+            with np.errstate(invalid="ignore", divide="ignore"):
+                cnt = s[..., 0, :]
+                return {"n": cnt.astype(np.int64), "log_score": s[..., 1, :] / cnt, "mean_q": s[..., 2, :] / cnt,
+                        "rmse": np.sqrt(s[..., 3, :] / cnt), "lead": s[..., 4, :] / cnt, "coverage": 1.0 - s[..., 5, :] / cnt}
+        return {"horizons": hz, "level": level, "threshold": thr, "pooled": ratios(st.sum(axis=0)), "tracks": ratios(st)}
+
     def _rows_and_offsets(self, ID, time):
         """(rows, offsets) of the queries (ID[k], time[k]): the last row of track ID[k] with a time stamp <= time[k] and the time past
         it; row -1 for an unknown ID, a time that is not finite or one before the track's first time stamp."""
