@@ -955,6 +955,12 @@ int ssde_lagstats_read(const ssde_handle *h, double *M, double *s, double *n_bul
    a stationary regime. */
 int ssde_lagforms_host(const double *M, const double *s, double n_bulk, int32_t d, const double *theta, double dt, const double *p0,
                        int32_t K, int32_t mask, int32_t taps_given, double *taps, double *raw, double *acc, double *chk);
+/* ssde_lagforms_host on one build of its sums: isa 0 the baseline instruction set, 1 the AVX2 build (SSDE_ERR_ARG on a host without
+   it, and for any other isa).  The two give the same bits; ssde_lagforms_host -- and an evaluation -- runs the wide one where the
+   host has it. */
+int ssde_lagforms_host_isa(int32_t isa, const double *M, const double *s, double n_bulk, int32_t d, const double *theta, double dt,
+                           const double *p0, int32_t K, int32_t mask, int32_t taps_given, double *taps, double *raw, double *acc,
+                           double *chk);
 /* The same three for every model the lag-statistics path serves (SSDE_MODEL_CTCRW, SSDE_MODEL_OU_SSM, SSDE_MODEL_BM_SSM; DESIGN.md
    §3.3d).  CTCRW and BM_SSM take the statistics of the INCREMENTS y_t - y_{t-1} (ssde_lagstats_host_m returns bitwise what
    ssde_lagstats_host returns for them; ref is ignored); OU_SSM takes those of the LEVELS z_{a,t} = y_{a,t} - ref[a]:
@@ -986,6 +992,11 @@ int ssde_lagforms_host_m(int32_t model, const double *M, const double *s, double
    infinity.  SSDE_ERR_ARG: a NULL pointer, a count < 1 or a slot >= n_out. */
 int ssde_reduce_host(const double *sums, const double *group_chk, int32_t n_groups, int32_t n_windows, int32_t nacc, const double *lag_acc,
                      double lag_chk, const double *add, const int16_t *add_slot, const int16_t *map, int32_t n_out, double *out);
+/* ssde_reduce_host where every record but group 0's is zero (the head formed from its statistics: nothing was launched), from that
+   record alone: sums0 [n_windows][nacc], chk0 its check; the other arguments as above.  out equals (==) what ssde_reduce_host gives
+   on the full array of n_groups records.  SSDE_ERR_ARG as there, and for more than 63 windows. */
+int ssde_reduce_host_head(const double *sums0, double chk0, int32_t n_groups, int32_t n_windows, int32_t nacc, const double *lag_acc,
+                          double lag_chk, const double *add, const int16_t *add_slot, const int16_t *map, int32_t n_out, double *out);
 /* What finished the handle's last evaluation: 0 a finalize launch after the main one, 1 the main launch itself
    (SSDE_FUSED_FINALIZE=1), 2 the host.  A multi-device parent reports its first shard; -1 for NULL. */
 int ssde_last_finish_form(const ssde_handle *h);

@@ -592,6 +592,11 @@ def load_library():
     lib.ssde_reduce_host.argtypes = [_dp, _dp, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_double, _dp, C.POINTER(C.c_int16), C.POINTER(C.c_int16),
                                      C.c_int32, _dp]
     lib.ssde_reduce_host.restype = C.c_int
+    lib.ssde_lagforms_host_isa.argtypes = [C.c_int32] + list(lib.ssde_lagforms_host.argtypes)
+    lib.ssde_lagforms_host_isa.restype = C.c_int
+    lib.ssde_reduce_host_head.argtypes = [_dp, C.c_double, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_double, _dp, C.POINTER(C.c_int16),
+                                          C.POINTER(C.c_int16), C.c_int32, _dp]
+    lib.ssde_reduce_host_head.restype = C.c_int
     lib.ssde_last_finish_form.argtypes = [C.c_void_p]
     lib.ssde_last_finish_form.restype = C.c_int
     for name in ("ssde_last_gain_feed", "ssde_last_gain_rows"):
@@ -656,7 +661,8 @@ EXPORTED_SYMBOLS = ("ssde_create", "ssde_eval", "ssde_eval_device", "ssde_penalt
                     "ssde_simulate", "ssde_par_bands", "ssde_simulate_rows", "ssde_set_option", "ssde_hess", "ssde_last_phase_ms", "ssde_comm_allreduce", "ssde_lagstats_host", "ssde_lagstats_read", "ssde_lagforms_host", "ssde_smooth", "ssde_smooth_loo", "ssde_forecast_scores", "ssde_smooth_draws", "ssde_predict", "ssde_predict_draws", "ssde_path_stats", "ssde_path_speed", "ssde_path_occupancy", "ssde_last_occupancy_form", "ssde_path_occupancy_fine", "ssde_last_occupancy_points", "ssde_last_hess_plan", "ssde_path_proximity", "ssde_last_proximity_plan",
                     "ssde_lagstats_host_m", "ssde_lagstats_read_m", "ssde_lagforms_host_m", "ssde_reduce_host", "ssde_last_finish_form", "ssde_last_gain_feed", "ssde_last_gain_rows",
                     "ssde_lagstats_host_cut", "ssde_lagstats_read_cut", "ssde_last_lag_cut",
-                    "ssde_headstats_host", "ssde_headstats_read", "ssde_headforms_host", "ssde_last_head_form")
+                    "ssde_headstats_host", "ssde_headstats_read", "ssde_headforms_host", "ssde_last_head_form",
+                    "ssde_lagforms_host_isa", "ssde_reduce_host_head")
 
 
 def reduce_host(sums, group_chk, n_out, map_, lag_acc=None, lag_chk=0.0, add=None, add_slot=None):
@@ -682,6 +688,29 @@ def reduce_host(sums, group_chk, n_out, map_, lag_acc=None, lag_chk=0.0, add=Non
     if st != 0:
         raise ValueError(f"ssde_reduce_host: status {st}")
     return out
+
+def reduce_host_head(sums0, chk0, n_groups, n_out, map_, lag_acc=None, lag_chk=0.0, add=None, add_slot=None):
+    """reduce_host where every group but group 0 holds zeros, from group 0's record alone: `sums0` [windows][accumulators], `chk0` its
+    check, `n_groups` the groups of the full array.  Equal (==) to reduce_host on that array."""
+    lib = load_library()
+    sums0 = np.ascontiguousarray(sums0, dtype=np.float64)
+    W, nacc = sums0.shape
+    mp = np.ascontiguousarray(map_, dtype=np.int16)
+    if mp.shape != (nacc - 1,):
+        raise ValueError("reduce_host_head: shapes")
+    ad = np.zeros(4); sl = np.full(4, -1, dtype=np.int16)
+    if add is not None:
+        ad[:len(add)] = add; sl[:len(add_slot)] = add_slot
+    la = None if lag_acc is None else np.ascontiguousarray(lag_acc, dtype=np.float64)
+    out = np.zeros(n_out + 1)
+    i16 = C.POINTER(C.c_int16)
+    st = lib.ssde_reduce_host_head(sums0.ctypes.data_as(_dp), float(chk0), int(n_groups), W, nacc, None if la is None else la.ctypes.data_as(_dp),
+                                   float(lag_chk), ad.ctypes.data_as(_dp), sl.ctypes.data_as(i16), mp.ctypes.data_as(i16), int(n_out),
+                                   out.ctypes.data_as(_dp))
+    if st != 0:
+        raise ValueError(f"ssde_reduce_host_head: status {st}")
+    return out
+
 
 def lagstats_host(tracks, model="CTCRW", ref=None):
     """The lag statistics ssde_create builds for a stationary batch, computed on the host: `tracks` is a list of
@@ -772,13 +801,14 @@ def headforms_host(G, s, n_tracks, theta, dt, cut, p0=None, mask=-1, full_probes
     return {"acc": acc, "gain": gain, "trans": trans, "n_probe": int(npb.value)}
 
 
-def lagforms_host(M, s, n_bulk, theta, dt, K, d=None, p0=None, mask=-1, taps=None, model="CTCRW", ref=None):
+def lagforms_host(M, s, n_bulk, theta, dt, K, d=None, p0=None, mask=-1, taps=None, model="CTCRW", ref=None, isa=None):
     """The bulk's forms of one evaluation on the lag-statistics path, on the host: CTCRW on a regular grid of
     step `dt` at theta = (log sigma_obs, mu_1 .. mu_d, log tau, log nu), cut at `K` taps (the check's cut: K - 16), from the
     statistics M, s, n_bulk.  `taps` (2 x taps: the impulse responses of u and r): used as they are when given, computed otherwise.
     Returns a dict: raw (2 x 6: S, C_1..3, su_1, su_2 of the cut K, then of K - 16), acc (the 4 + d accumulators), chk, taps.
     `model` "OU_SSM" (theta = log sigma_obs, mu, log tau, log kappa; `ref`: what the statistics were built with) or "BM_SSM" (theta =
-    log sigma_obs, mu, log sigma): taps is 3 x taps (u, A1, A3) and raw 2 x 5 (S, S1, S3, su_1, su_2)."""
+    log sigma_obs, mu, log sigma): taps is 3 x taps (u, A1, A3) and raw 2 x 5 (S, S1, S3, su_1, su_2).
+    `isa` (CTCRW): 0 the baseline build of the sums, 1 the AVX2 build (ValueError on a host without it); None: what an evaluation runs."""
     lib = load_library()
     M = np.ascontiguousarray(M, dtype=np.float64); s = np.ascontiguousarray(s, dtype=np.float64)
     theta = np.ascontiguousarray(theta, dtype=np.float64)
@@ -793,7 +823,13 @@ def lagforms_host(M, s, n_bulk, theta, dt, K, d=None, p0=None, mask=-1, taps=Non
         raise ValueError("lagforms_host: shapes")
     p0a = None if p0 is None else np.ascontiguousarray(np.atleast_1d(p0), dtype=np.float64)
     raw = np.zeros((2, nraw)); acc = np.zeros(4 + d); chk = np.zeros(1)
-    if not scal and ref is None:
+    if isa is not None:
+        if scal:
+            raise ValueError("lagforms_host: isa is CTCRW's")
+        st = lib.ssde_lagforms_host_isa(int(isa), M.ctypes.data_as(_dp), s.ctypes.data_as(_dp), float(n_bulk), d, theta.ctypes.data_as(_dp),
+                                        float(dt), None if p0a is None else p0a.ctypes.data_as(_dp), int(K), int(mask), 1 if given else 0,
+                                        tp.ctypes.data_as(_dp), raw.ctypes.data_as(_dp), acc.ctypes.data_as(_dp), chk.ctypes.data_as(_dp))
+    elif not scal and ref is None:
         st = lib.ssde_lagforms_host(M.ctypes.data_as(_dp), s.ctypes.data_as(_dp), float(n_bulk), d, theta.ctypes.data_as(_dp), float(dt),
                                     None if p0a is None else p0a.ctypes.data_as(_dp), int(K), int(mask), 1 if given else 0,
                                     tp.ctypes.data_as(_dp), raw.ctypes.data_as(_dp), acc.ctypes.data_as(_dp), chk.ctypes.data_as(_dp))

@@ -145,7 +145,7 @@ static void next_stamp_pair(ssde_handle* h) {
 }
 
 int eval_device(ssde_handle* h, const double* par, int order, double* out_dev, hipStream_t s) {
-    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->device_current) HIPCHK(h, hipSetDevice(h->device));  // (run_once sets the flag right after its own hipSetDevice and clears it after this call)
     h->n_evals++;
     next_stamp_pair(h);
     h->pub_armed = false;
@@ -539,9 +539,9 @@ int run_once(ssde_handle* h, const double* par, int order, double* o) {
     if (!h->comms.empty()) {
         // the collective sits between the finalize launch and the read-back, on the same stream
         HIPCHK(h, ph_mark(0));
-        h->sync_call = true;
+        h->sync_call = true; h->device_current = true;         // (hipSetDevice above, nothing between that changes the device)
         int st = eval_device(h, par, order, h->out.p, 0);
-        h->sync_call = false;
+        h->sync_call = false; h->device_current = false;
         if (st) return st;
         HIPCHK(h, ph_mark(1));
         st = reduce_ranks(h, h->out.p, 0);
@@ -559,10 +559,10 @@ int run_once(ssde_handle* h, const double* par, int order, double* o) {
         return eval_tv_graph(h, par, order, o);
     }
     HIPCHK(h, ph_mark(0));
-    h->sync_call = true;
+    h->sync_call = true; h->device_current = true;             // (hipSetDevice above, nothing between that changes the device)
     h->pub_request = true;
     int st = eval_device(h, par, order, h->out.p, 0);
-    h->sync_call = false;
+    h->sync_call = false; h->device_current = false;
     if (st) return st;
     HIPCHK(h, ph_mark(1));
     h->ph_host_enq_ms = ph_ms(ph_t0);
@@ -587,7 +587,8 @@ int run_once(ssde_handle* h, const double* par, int order, double* o) {
         rh.n_groups = h->n_groups; rh.n_windows = ra.n_value_parts; rh.nacc = ra.nacc;
         rh.lag_acc = ra.lag_part > 0 ? ra.lag_acc : nullptr; rh.lag_chk = ra.lag_chk;
         rh.add = ra.add; rh.add_slot = ra.add_slot; rh.map = ra.map; rh.n_out = ra.n_out;
-        reduce_host(rh, o, h->reduce_scratch);
+        // (the other groups' records are zeros: the same sums without the walk over them; the head is one window)
+        if (!reduce_host_head(rh, o)) { h->err = "the head's finish: more windows than the short form serves"; return SSDE_ERR_ARG; }
     } else
     if (h->host_armed) {
         // The head's workgroups store their group's record into the pinned mailbox and this evaluation's sequence number after it

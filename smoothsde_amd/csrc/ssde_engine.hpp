@@ -214,6 +214,7 @@ struct ssde_handle {
     std::vector<double> gain_scratch;        // a deferred table's rows (build_gain_table / feed_gain_table)
     bool par_ev_pending[PAR_RING] = {false, false, false, false, false, false, false, false};   // slot last used by an asynchronous call
     bool sync_call = false;        // set around the evaluation of a synchronous ssde_eval (single engine, null stream)
+    bool device_current = false;   // run_once has just made h->device the thread's current device: eval_device need not (set and cleared by run_once alone)
 
     // side streams: the kernels of one evaluation that do not depend on each other run concurrently
     hipStream_t aux[2] = {nullptr, nullptr};
@@ -348,8 +349,8 @@ struct ssde_handle {
     double head_n = 0.0;                   // tracks
     DevBuf<double> head_G, head_s;         // the device copies ([HEAD_NW][HEAD_NW], [2][HEAD_NW]: ssde_headstats_read)
     ssde::HeadFormWork* head_work = nullptr;   // the forms' work arrays (no allocation per evaluation)
-    std::vector<double> head_rec;          // [n_groups][NACC_MAX] the records reduce_host reads: group 0 the head's accumulators, zeros elsewhere
-    std::vector<double> head_chk;          // [n_groups] zeros: one window has no hand-over
+    std::vector<double> head_rec;          // [NACC_MAX] group 0's record, the head's accumulators: every other group's is zero and is not kept (reduce_host_head)
+    std::vector<double> head_chk;          // [1] zero: one window has no hand-over
     bool head_armed = false;               // the evaluation just planned ends in head_rec (set by eval_iso, consumed by run_once)
     int last_head_form = 0;                // the head of the last evaluation: 0 the kernel, 1 the statistics (ssde_last_head_form)
     int last_lag_cut = 0;                  // first bulk row of the last evaluation (0: streamed)

@@ -256,7 +256,7 @@ int build_headstats(ssde_handle* h) {
     }
     if (!h->head_work) h->head_work = new (std::nothrow) HeadFormWork();
     if (!h->head_work) { h->head_G.release(); h->head_s.release(); return SSDE_OK; }
-    h->head_rec.assign((size_t)G * NACC_MAX, 0.0); h->head_chk.assign((size_t)G, 0.0);
+    h->head_rec.assign((size_t)NACC_MAX, 0.0); h->head_chk.assign(1, 0.0);
     h->head_n = (double)tracks;
     h->hbm_bytes += (int64_t)(Gc.size() + sc.size()) * 8;
     h->head_ready = true;

@@ -686,6 +686,16 @@ extern "C" int ssde_reduce_host(const double* sums, const double* group_chk, int
     return SSDE_OK;
 }
 
+extern "C" int ssde_reduce_host_head(const double* sums0, double chk0, int32_t n_groups, int32_t n_windows, int32_t nacc,
+                                     const double* lag_acc, double lag_chk, const double* add, const int16_t* add_slot,
+                                     const int16_t* map, int32_t n_out, double* out) {
+    if (!sums0 || !add || !add_slot || !map || !out || n_groups < 1 || n_windows < 1 || n_windows > REDUCE_HEAD_MAX_WINDOWS || nacc < 1 || n_out < 1) return SSDE_ERR_ARG;
+    for (int k = 0; k + 1 < nacc; k++) if (map[k] >= n_out) return SSDE_ERR_ARG;
+    for (int i = 0; i < 4; i++) if (add_slot[i] >= n_out) return SSDE_ERR_ARG;
+    const ReduceHostArgs a = {sums0, (int64_t)n_windows * nacc, &chk0, 1, n_groups, n_windows, nacc, lag_acc, lag_chk, add, add_slot, map, n_out};
+    return reduce_host_head(a, out) ? SSDE_OK : SSDE_ERR_ARG;
+}
+
 extern "C" int ssde_last_finish_form(const ssde_handle* h) {
     if (!h) return -1;
     return h->shards.empty() ? h->last_finish_form : h->shards[0]->last_finish_form;
@@ -747,9 +757,10 @@ extern "C" int ssde_last_gain_rows(const ssde_handle* h) {
     return h->shards.empty() ? h->last_gain_rows : h->shards[0]->last_gain_rows;
 }
 
-extern "C" int ssde_lagforms_host(const double* M, const double* s, double n_bulk, int32_t d, const double* theta, double dt,
-                                  const double* p0, int32_t K, int32_t mask, int32_t taps_given, double* taps, double* raw,
-                                  double* acc, double* chk) {
+// (isa: lag_forms_host_isa -- < 0 the process's choice, which is what the engine calls)
+static int lagforms_host_entry(int isa, const double* M, const double* s, double n_bulk, int32_t d, const double* theta, double dt,
+                               const double* p0, int32_t K, int32_t mask, int32_t taps_given, double* taps, double* raw,
+                               double* acc, double* chk) {
     if (!M || !s || !theta || !taps || !raw || !acc || !chk || d < 1 || d > 2) return SSDE_ERR_ARG;
     if (K < LAG_CHECK || K > LAG_KMAX || !(dt > 0.0) || !std::isfinite(dt)) return SSDE_ERR_ARG;
     IsoArgs a;
@@ -786,12 +797,25 @@ extern "C" int ssde_lagforms_host(const double* M, const double* s, double n_bul
         for (int i = 0; i < LAG_N; i++) { taps[i] = f.lam[i]; taps[LAG_N + i] = f.rr[i]; }
     }
     f.M = M; f.s = s; f.n = n_bulk;
-    lag_forms_host(f, o);
+    if (isa < 0) lag_forms_host(f, o); else lag_forms_host_isa(f, o, isa);
     for (int c = 0; c < 2; c++)
         for (int j = 0; j < LAG_NRAW; j++) raw[c * LAG_NRAW + j] = o.raw[c][j];
     for (int k = 0; k < 4 + d; k++) acc[k] = o.acc[k];
     *chk = o.chk;
     return SSDE_OK;
+}
+
+extern "C" int ssde_lagforms_host(const double* M, const double* s, double n_bulk, int32_t d, const double* theta, double dt,
+                                  const double* p0, int32_t K, int32_t mask, int32_t taps_given, double* taps, double* raw,
+                                  double* acc, double* chk) {
+    return lagforms_host_entry(-1, M, s, n_bulk, d, theta, dt, p0, K, mask, taps_given, taps, raw, acc, chk);
+}
+
+extern "C" int ssde_lagforms_host_isa(int32_t isa, const double* M, const double* s, double n_bulk, int32_t d, const double* theta,
+                                      double dt, const double* p0, int32_t K, int32_t mask, int32_t taps_given, double* taps,
+                                      double* raw, double* acc, double* chk) {
+    if (isa < 0 || isa > 1 || (isa == 1 && !lag_forms_wide())) return SSDE_ERR_ARG;
+    return lagforms_host_entry(isa, M, s, n_bulk, d, theta, dt, p0, K, mask, taps_given, taps, raw, acc, chk);
 }
 
 extern "C" int ssde_lagforms_host_m(int32_t model, const double* M, const double* s, double n_bulk, const double* ref, int32_t d,

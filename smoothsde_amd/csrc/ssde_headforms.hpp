@@ -131,6 +131,8 @@ SSDE_HEAD_INLINE HeadP hp_add(const HeadP& u, const HeadP& v) { return {u.x + v.
 SSDE_HEAD_INLINE HeadP hp_scale(double f, const HeadP& v) { return {f * v.x, f * v.y}; }
 
 // false: a table row that is not scored (iF == 0) or predicts without B mu -- such an evaluation keeps the kernel
+// (SSDE_HEAD_TIME_NO_DOTS / _NO_PROBES / _NO_MOMENTS: tools/headforms_time.cpp alone defines them, to time the call without the dot
+//  products, the probe-column updates or the per-direction moment recursion; the result is then wrong)
 SSDE_HEAD_INLINE bool head_forms_body(const HeadFormArgs& A, HeadFormWork& W, HeadFormOut& o) {
     const int cut = A.cut, D = A.d, mask = A.mask;
     o.accq = 0.0;
@@ -185,8 +187,10 @@ SSDE_HEAD_INLINE bool head_forms_body(const HeadFormArgs& A, HeadFormWork& W, He
             for (int k = 0; k < HEAD_NS; k++) acc[k][0] = acc[k][1] = acc[k][2] = acc[k][3] = 0.0;
             // the probe columns (a column whose increment lies ahead holds zeros), then the columns past them: component c is the
             // last probe's state at row t - (c - (nf - 1)), c <= t
+#ifndef SSDE_HEAD_TIME_NO_DOTS
             head_dots(&W.z[0][0], HEAD_LDW + 8, grow, nf4, acc);
             if (t + 1 > nf) head_dots(&W.col[0][at + 1], HEAD_C + 8, grow + nf, (t + 1 - nf + 3) & ~3, acc);
+#endif
             for (int k = 0; k < HEAD_NS; k++) q[k] = head_hsum(acc[k]);
             for (int a = 0; a < D; a++) {
                 q[0] += zc[a].x * sg[a]; q[1] += zc[a].y * sg[a];
@@ -216,6 +220,7 @@ SSDE_HEAD_INLINE bool head_forms_body(const HeadFormArgs& A, HeadFormWork& W, He
             mu2 += A.mu[a] * A.mu[a];
             musg += A.mu[a] * sg[a];
         }
+#ifndef SSDE_HEAD_TIME_NO_MOMENTS
         for (int j = 0; j < NDIRP; j++) {
             if (!dir[j]) continue;
             const double de = (j == 1) ? tr.de : 0.0, dt12 = (j == 1) ? tr.dt12 : 0.0;
@@ -239,6 +244,7 @@ SSDE_HEAD_INLINE bool head_forms_body(const HeadFormArgs& A, HeadFormWork& W, He
             Pcd[j] = P;
             for (int a = 0; a < D; a++) md[j][a] = mdn[a];
         }
+#endif
         {
             // P_cc' = F P_cc F' + (F q_c) g' + g (F q_c)' + G_tt g g' + sum_a mu_a (w_a h' + h w_a') + n sum_a mu_a^2 h h'
             Head2 P = h2_mul(h2_mul(F, Pcc), h2_t(F));
@@ -265,6 +271,7 @@ SSDE_HEAD_INLINE bool head_forms_body(const HeadFormArgs& A, HeadFormWork& W, He
             mx = nx; mv = nv;
         }
         if (t >= 1 && 1 + t < nf) W.din[1 + t] = 1.0;
+#ifndef SSDE_HEAD_TIME_NO_PROBES
         for (int j = 0; j < NDIRP; j++) {
             if (!dir[j]) continue;
             const double de = (j == 1) ? tr.de : 0.0, dt12 = (j == 1) ? tr.dt12 : 0.0;
@@ -282,6 +289,7 @@ SSDE_HEAD_INLINE bool head_forms_body(const HeadFormArgs& A, HeadFormWork& W, He
             const double nv = (F.c * W.z[0][c] + F.d * W.z[1][c]) + g.y * W.din[c];
             W.z[0][c] = nx; W.z[1][c] = nv;
         }
+#endif
         if (t >= 1 && 1 + t < nf) W.din[1 + t] = 0.0;
     }
     // what the lanes finish with: ctcrw_finish_parts on the summed accumulators (no log-determinant terms: those are data-free)

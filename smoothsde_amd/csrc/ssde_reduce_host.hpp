@@ -77,5 +77,59 @@ inline void reduce_host(const ReduceHostArgs& a, double* out, std::vector<double
     std::memcpy(&out[a.n_out], &w, 8);
 }
 
+// reduce_host where every record but group 0's and the by-value lag entry is zero (the head from its statistics: eval_iso): the
+// same sums from those entries alone.  a.sums and a.chk are read for group 0 only.  Entry i of the device's order sits in the
+// 1024-block i / 1024, on virtual thread i % 256, as term (i % 1024) / 256 of that thread's (v0 + v1) + (v2 + v3); the live entries
+// are i = c G (window c) and i = n_windows G (the lag entry).  They are grouped by (block, thread) once, in ascending i -- a group is
+// one addition of reduce_host --, then each fed slot adds its groups and runs the 256-wide tree whole.  Every addition reduce_host
+// makes that is left out here adds +0.0, which changes no value (a sum that is -0.0 there may be +0.0 here or the reverse: equal
+// by ==).  false, nothing written: more windows than REDUCE_HEAD_MAX_WINDOWS.
+constexpr int REDUCE_HEAD_MAX_WINDOWS = 63;
+inline bool reduce_host_head(const ReduceHostArgs& a, double* out) {
+    if (a.n_windows > REDUCE_HEAD_MAX_WINDOWS) return false;
+    const int n_live = a.n_windows + (a.lag_acc ? 1 : 0);
+    struct Group { int64_t blk; int thr; int entry[4]; };          // entry[term]: the live entry that is this term, or -1
+    Group grp[REDUCE_HEAD_MAX_WINDOWS + 1];
+    int n_grp = 0;
+    for (int e = 0; e < n_live; e++) {
+        const int64_t i = (int64_t)e * a.n_groups;
+        const int64_t blk = i / 1024;
+        const int thr = (int)(i % 256), term = (int)(i % 1024) / 256;
+        int g = 0;
+        while (g < n_grp && (grp[g].blk != blk || grp[g].thr != thr)) g++;
+        if (g == n_grp) { grp[n_grp++] = {blk, thr, {-1, -1, -1, -1}}; }
+        grp[g].entry[term] = e;
+    }
+    double acc[256];
+    for (int slot = 0; slot <= a.n_out; slot++) out[slot] = 0.0;
+    for (int slot = 0; slot < a.n_out; slot++) {
+        bool fed = slot == 0;
+        for (int k = 1; k < a.nacc && !fed; k++) fed = a.map[k - 1] == slot;
+        if (fed) {
+            for (int t = 0; t < 256; t++) acc[t] = 0.0;
+            for (int k = 0; k < a.nacc; k++) {
+                if (slot == 0 ? k != 0 : (k == 0 || a.map[k - 1] != slot)) continue;
+                for (int g = 0; g < n_grp; g++) {                  // (a thread's groups come block after block, as in reduce_host)
+                    double v[4];
+                    for (int u = 0; u < 4; u++) {
+                        const int e = grp[g].entry[u];
+                        v[u] = e < 0 ? 0.0 : e < a.n_windows ? a.sums[(int64_t)e * a.nacc + k] : a.lag_acc[k];
+                    }
+                    acc[grp[g].thr] += (v[0] + v[1]) + (v[2] + v[3]);
+                }
+            }
+            for (int o = 128; o > 0; o >>= 1)
+                for (int t = 0; t < o; t++) acc[t] += acc[t + o];
+            out[slot] = acc[0];
+        }
+        for (int i = 0; i < 4; i++)
+            if (a.add_slot[i] == slot) out[slot] += a.add[i];
+    }
+    uint64_t w = check_bits(a.chk[0]);
+    if (a.lag_acc) w = std::max(w, check_bits(a.lag_chk));
+    std::memcpy(&out[a.n_out], &w, 8);
+    return true;
+}
+
 }  // namespace ssde_engine
 #endif

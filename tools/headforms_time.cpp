@@ -2,6 +2,9 @@
 // theta (sigma_obs 0.1, tau 2, nu 1, unit grid, mu fixed: directions sigma_obs / tau / nu), the cut given on the command line
 // (default 64).  Build with the library's host flags:  hipcc -O3 -std=c++17 -x c++ tools/headforms_time.cpp -o headforms_time
 // Prints the gain rows, the probe columns and the microseconds per call (best and median of 21 batches of 2000 calls).
+// The per-part account: build it again with -DSSDE_HEAD_TIME_NO_DOTS, -DSSDE_HEAD_TIME_NO_PROBES, -DSSDE_HEAD_TIME_NO_MOMENTS (the dot
+// products, the probe-column updates, the per-direction moment recursion compiled out) and with all three (the rest); a part's cost
+// is the full call's time less the time without it, and the parts overlap where those differences sum to less than the call.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -63,6 +66,19 @@ int main(int argc, char** argv) {
         us.push_back(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() / 2000.0);
     }
     std::sort(us.begin(), us.end());
+    const char* without =
+#if defined(SSDE_HEAD_TIME_NO_DOTS) && defined(SSDE_HEAD_TIME_NO_PROBES) && defined(SSDE_HEAD_TIME_NO_MOMENTS)
+        "without dots, probe updates and moments: ";
+#elif defined(SSDE_HEAD_TIME_NO_DOTS)
+        "without the dots: ";
+#elif defined(SSDE_HEAD_TIME_NO_PROBES)
+        "without the probe updates: ";
+#elif defined(SSDE_HEAD_TIME_NO_MOMENTS)
+        "without the moment recursion: ";
+#else
+        "";
+#endif
+    std::printf("%s", without);
     std::printf("head forms on the host: cut %d, mask %d, gain rows %d, probe columns %d (+2 offsets): best %.2f us, median %.2f us per call (sink %.3g)\n",
                 cut, mask, last + 1, o.n_full, us.front(), us[us.size() / 2], sink);
     delete W;
